@@ -10,10 +10,17 @@ collective on the path).  Default workload = BASELINE.json configs[2]: 1080p fra
 One JSON line on stdout (rank 0).  `roofline` prices the fused kernel against HBM as the
 contract asks (algorithmic bytes = input tile u8 + 8 B result per window) and also
 reports the FP32-VALU fraction, which is the bound that actually binds.
-`cpu_baseline` times the oracle's dense Float64 statement of the reference algorithm
-(kind "port": Julia is not available) on a bounded sample on all host cores, threaded inside a
-window (the reference's CPUThreads model) and across windows (value = the faster), plus the
-oracle's separable Float64 statement for the algorithmic-vs-hardware split.
+
+A plain run sets up, warms up, times the steps and prints that line.  `--full` adds what the
+headline figure does not need: the checks of the positions (the synthetic targets, rank 0's
+gathered shard, the CPU oracle on a sample) and `cpu_baseline`, which times the oracle's dense
+Float64 statement of the reference algorithm (kind "port": Julia is not available) on a bounded
+sample on all host cores, threaded inside a window (the reference's CPUThreads model) and across
+windows (value = the faster), plus the oracle's separable Float64 statement for the
+algorithmic-vs-hardware split (`--no-cpu` leaves the baseline out of a `--full` run).
+`--dump-outputs DIR` writes the positions the last timed step returned (1-based, [n, 2]) as
+DIR/positions.npy in float64; the synthetic inputs are seeded, so runs with the same arguments
+compare output for output.
 """
 import argparse
 import json
@@ -35,6 +42,7 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_PEAK_FMA = 78.6e12        # 157.3 TFLOP/s FP32 vector = 78.6 T FMA/s (v_pk_fma_f32)
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: larger outputs are written as a fixed, seeded sample of rows
 
 
 def make_frames(torch, n, h, w, tw, radii, seed, noise, device):
@@ -170,7 +178,11 @@ def parse_args():
     ap.add_argument("--noise", type=int, default=3, help="± uniform noise levels on the synthetic frames")
     ap.add_argument("--variant", type=int, default=-1, help="force a kernel specialisation")
     ap.add_argument("--target-width", type=float, default=0.0, help="override the workload's target_width (tuning: other kernel lengths)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the positions (synthetic targets, gathered shard, CPU oracle) and time the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the positions of the last timed step as DIR/positions.npy (float64, 1-based, [n, 2])")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg of --full")
     ap.add_argument("--tuning", action="append", default=[], metavar="KEY=0|1",
                     help="pin one of the library's alternative code paths for a same-session A/B (pdog_set_tuning), e.g. --tuning no_fold=1")
     ap.add_argument("--no-exact", action="store_true", help="exact mode off (pdog_set_exact(t, 0)): the raw FP32 ranking, for the A/B of its cost")
@@ -212,6 +224,19 @@ def tracking_sanity(np, got, centres, guesses_h, fh, fw, tw, radii, noise):
     err = np.abs(got[inside] - centres[inside]).max() if inside.any() else 0
     if not os.environ.get("PDOG_BENCH_NOCHECK"):   # timing-only ablation builds produce wrong positions
         assert err <= (1 if noise else 0), f"tracking sanity failed: max |pos - centre| = {err}"
+
+
+def dump_outputs(np, args, positions):
+    """--dump-outputs DIR: the int32[n, 2] positions a caller of the timed path received from its last step, as
+    DIR/positions.npy in float64 (exact for these integers); above DUMP_LIMIT_BYTES a fixed, seeded sample of rows."""
+    if not args.dump_outputs:
+        return
+    pos = np.asarray(positions, np.float64)
+    if pos.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // pos[0].nbytes
+        pos = pos[np.sort(np.random.Generator(np.random.PCG64(0)).choice(len(pos), keep, replace=False))]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "positions.npy"), pos)
 
 
 def result_line(args, desc, world, dt, kern_ms, batch, info, kernel_for_batch, fh, fw, tw, sharding, traffic_key=None):
@@ -297,8 +322,11 @@ def run_group(args):
         torch.cuda.synchronize(r)
     dt = time.perf_counter() - t0
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    got = out.cpu().numpy()
-    tracking_sanity(np, got, np.concatenate(centres), np.concatenate(guesses_h), fh, fw, tw, radii, args.noise)
+    if args.full or args.dump_outputs:
+        got = out.cpu().numpy()
+        if args.full:
+            tracking_sanity(np, got, np.concatenate(centres), np.concatenate(guesses_h), fh, fw, tw, radii, args.noise)
+        dump_outputs(np, args, got)
     res = result_line(args, desc, world, dt, kern_ms, batch, info, gt.kernel_for_batch(batch), fh, fw, tw,
                       f"frames x{world} from one process (pdog_group_*), in-process RCCL ncclGather of int32[n,2] to device 0")
     res["roofline"]["note"] += "; group mode: kernel_ms = rank 0's kernels + its part of the gather"
@@ -373,9 +401,10 @@ def run_chain(args):
     dt = time.perf_counter() - t0
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     got = out.cpu().numpy()
-    err = np.abs(got - centres).max()
-    if not os.environ.get("PDOG_BENCH_NOCHECK"):
+    if args.full and not os.environ.get("PDOG_BENCH_NOCHECK"):
+        err = np.abs(got - centres).max()
         assert err <= (1 if args.noise else 0), f"chain lost the target: max |pos - centre| = {err}"
+    dump_outputs(np, args, got)
     res = result_line(args, desc + f" [--chain: one clip of {n_frames} frames walked serially]", 1, dt, kern_ms, n_frames, info, "chain", fh, fw, tw,
                       "single GPU, one clip (a serial chain does not shard: replicas only)", traffic_key=args.workload + "_chain")
     res["config"]["chain"] = True
@@ -384,7 +413,7 @@ def run_chain(args):
     res["us_per_frame"] = dt / args.steps / n_frames * 1e6
     on, thr, refined1 = bt.exact_stats()
     res["exact"] = {"on": on, "threshold_2delta": thr, "refined_windows_per_step": (refined1 - refined0) / args.steps}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle.dog_oracle import Oracle, build
         build()
         o, strict = Oracle(fast=True), Oracle(fast=False)
@@ -531,12 +560,15 @@ def main():
         dt = float(t.item())
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))   # HIP events on the launch stream
 
-    got = out.cpu().numpy()
-    tracking_sanity(np, got, centres, guesses_h, fh, fw, tw, radii, args.noise)
-    if world > 1 and rank == 0:   # the gathered list is the shards in rank order: rank 0's block must be its own answers
-        g0 = gathered.cpu().numpy()
-        assert g0.shape == (n_total, 2) and np.array_equal(g0[:batch], got), "gathered positions: rank 0's shard differs from its own results"
+    if args.full:
+        got = out.cpu().numpy()
+        tracking_sanity(np, got, centres, guesses_h, fh, fw, tw, radii, args.noise)
+        if world > 1 and rank == 0:   # the gathered list is the shards in rank order: rank 0's block must be its own answers
+            g0 = gathered.cpu().numpy()
+            assert g0.shape == (n_total, 2) and np.array_equal(g0[:batch], got), "gathered positions: rank 0's shard differs from its own results"
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(np, args, (gathered if world > 1 else out).cpu().numpy())
     if rank == 0:
         sharding = (f"frames x{world}, one process per GPU, gather int32[n,2] to rank 0" + ("" if backend == "nccl" else f" ({backend} rehearsal)")) \
             if world > 1 else "single GPU"
@@ -547,7 +579,7 @@ def main():
                         "since_create": dict(zip(("windows", "column_blocks", "candidates", "sequential_chains"), bt.exact_detail())),
                         "note": "windows whose two best FP32 responses lay within 2*delta and were re-decided in the reference's Float64 "
                                 "arithmetic inside the timed region (rank 0's shard)"}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             ns = min(256, batch)
             cb = cpu_baseline(frames[:ns].cpu().numpy(), guesses_h[:ns], fill, tw, radii)
             cpos = cb["pos"]

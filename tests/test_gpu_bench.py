@@ -26,7 +26,7 @@ def _run(cmd, extra_env=None):
 
 
 def test_bench_single_gpu_contract():
-    r = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "256"])
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--batch", "256"])
     for k in CONTRACT + ("cpu_baseline",):
         assert k in r, k
     assert r["n_gpus"] == 1 and r["steps"] == 3 and r["unit"] == "frames/s" and r["vs_baseline"] is None
@@ -37,13 +37,30 @@ def test_bench_single_gpu_contract():
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run prints the headline line without the --full legs; --dump-outputs writes the positions of the last
+    timed step, and the seeded inputs make them the same in another run (here one with --full's checks, which passed)."""
+    import numpy as np
+    args = ["--steps", "4", "--warmup", "1", "--batch", "256"]
+    a = _run([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run([sys.executable, "bench.py", "--full", "--no-cpu"] + args + ["--dump-outputs", str(tmp_path / "b")])
+    for k in CONTRACT:
+        assert k in a, k
+    assert "cpu_baseline" not in a and "cpu_baseline" not in b and a["steps"] == 4
+    assert abs(a["value"] - 256 * 4 / (a["ms_per_step"] * 4e-3)) < 1e-6 * a["value"]
+    pa, pb = np.load(tmp_path / "a" / "positions.npy"), np.load(tmp_path / "b" / "positions.npy")
+    assert pa.dtype == np.float64 and pa.shape == (256, 2) and np.array_equal(pa, np.rint(pa))
+    assert (pa >= 1).all() and (pa <= np.array(b["config"]["frame"])).all()
+    assert np.array_equal(pa, pb)
+
+
 def test_bench_two_rank_rehearsal():
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-              "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "128"],
+              "--master-port", str(port), "bench.py", "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--batch", "128"],
              {"PDOG_BENCH_BACKEND": "gloo"})
     for k in CONTRACT:
         assert k in r, k

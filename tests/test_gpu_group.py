@@ -147,7 +147,7 @@ def test_gather_positions_on_the_nccl_backend_world1():
 def test_bench_group_mode_and_refusal():
     import torch
     env = dict(os.environ)
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--group", "--steps", "3", "--warmup", "1", "--batch", "256"],
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--group", "--full", "--steps", "3", "--warmup", "1", "--batch", "256"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

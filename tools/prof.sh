@@ -5,6 +5,7 @@
 # The un-profiled bench line (with its cpu_baseline) is taken first, in the same session on the same board:
 # gpurun_out/prof_<tag>_bench_unprofiled.json.  Kernel statistics leave the warm-up dispatches out (tools/kernel_times.py).
 TAG=$1; WL=$2; shift 2
+set -- --full "$@"   # every bench run below checks its positions; the un-profiled one (no --no-cpu) also takes the cpu_baseline
 P=/tmp/prof_$TAG; mkdir -p $P gpurun_out
 STEPS=3; WARM=1; KT_WARM=3
 python bench.py --workload $WL "$@" > gpurun_out/prof_${TAG}_bench_unprofiled.json 2> $P/bench.err || { tail -5 $P/bench.err; exit 1; }
