@@ -268,6 +268,45 @@ int pdog_group_sync(pdog_group *g);
  * d_out: int32[n_total][2], both on the current device) — the one step of pdog_group_detect_batch a one-GPU box cannot reach. */
 int pdog_group_test_compact(const int32_t *d_gathered, int n_total, int ndev, int32_t *d_out);
 
+/* ---- diagnostic overlay (the reference's `Diagnose`, src/diagnose.jl) ----
+ * For every frame the reference's dia(img, point) (:30-38) runs on, it resizes the frame into a 360 x 640
+ * Gray{N0f8} buffer (imresize!), pushes the scaled position onto a 100-entry trace and draws the label, a
+ * radius-2 dot at the position and the path of the trace in the target colour (255 for a dark target, 0 for a
+ * bright one, :17).  These entry points draw everything but the label (renderstring! needs FreeType and the
+ * reference's font asset; this library does not rasterise text) into device buffers; encoding the video stays
+ * with the host (VideoIO's writer, :19).  Exact, bit for bit, against this project's restatement
+ * (tests/diag_restatement.py), which rests on five recollections of the Julia packages, none checked here:
+ *  (a) Float64(::N0f8) is raw / 255.0 (as for the DoG path);
+ *  (b) imresize! (ImageTransformations 0.10: bilinear, no antialiasing, centre-aligned) computes coordinates
+ *      and weights with a separate multiply and add and combines the four taps with the row index innermost;
+ *  (c) the conversion back to N0f8 is round(v * 255), ties to even;
+ *  (d) ImageDraw's filled ellipse draws ((a-qi)/2)^2 + ((b-qj)/2)^2 < 1 (strict): the 3 x 3 block;
+ *  (e) each segment of ImageDraw's Path is its Bresenham walk from the older point to the newer one.
+ * (a)-(c) can move a pixel by at most one grey level, and only at an exact tie; (d) and (e) decide which pixels
+ * are drawn.  Positions outside the frame are clamped into it before scaling (the tracker's outputs are, :61). */
+#define PDOG_DIAG_H 360     /* DIAGNOSTIC_VIDEO_SIZE, src/diagnose.jl:2 */
+#define PDOG_DIAG_W 640
+#define PDOG_DIAG_TRACE 100 /* TRACE_BUFFER_SIZE, src/diagnose.jl:3 */
+typedef struct pdog_diag pdog_diag; /* opaque; `struct Diagnose` (:5-23) minus label and writer */
+
+/* A handle with an empty trace on HIP device `device`; darker_target picks the colour (:17). */
+int pdog_diag_create(int device, int darker_target, pdog_diag **out);
+/* Waits for the last stream the handle rendered on, then frees it. */
+int pdog_diag_destroy(pdog_diag *d);
+/* Host arithmetic of :31 with the ratio of :27: out = round.(ij .* (360 / frame_h, 640 / frame_w)), ties to
+ * even, ij clamped into the frame first.  The result lies in [0, 360] x [0, 640]; 0 is off the buffer. */
+int pdog_diag_point(int frame_h, int frame_w, const int32_t ij[2], int32_t out[2]);
+/* n_frames frames (device; frame k at d_frames + k*frame_stride, rows row_stride bytes apart) and their 1-based
+ * positions d_ij (n_frames x 2 int32, device: what pdog_detect_chain / pdog_detect_batch wrote) -> d_out,
+ * n_frames x 360 x 640 uint8, contiguous (device).  Frame k is drawn with the trace of the handle's previous
+ * points and the positions 0 ... k of this call (the last 100 in all).  Asynchronous on hip_stream (NULL = the
+ * null stream); the trace carries over to the next call at any frame size, in stream order, with no host wait.
+ * PDOG_E_ARG for a null pointer, a non-positive frame size, row_stride < frame_w or a negative frame_stride or
+ * n_frames; n_frames == 0 does nothing. */
+int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, int64_t frame_stride,
+                     int64_t row_stride, int frame_h, int frame_w, int n_frames, const int32_t *d_ij,
+                     uint8_t *d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ SYMBOLS = (
     "pdog_group_create", "pdog_group_destroy", "pdog_group_size", "pdog_group_tracker", "pdog_group_shard",
     "pdog_group_detect_batch", "pdog_group_sync", "pdog_shard_range", "pdog_shard_owner", "pdog_group_test_compact",
     "pdog_set_exact", "pdog_get_exact", "pdog_get_exact_detail", "pdog_dense_kernel", "pdog_set_tuning",
+    "pdog_diag_create", "pdog_diag_destroy", "pdog_diag_point", "pdog_diag_render",
 )
 
 
@@ -133,6 +134,11 @@ def lib():
         L.pdog_set_exact.restype = i; L.pdog_set_exact.argtypes = [p, i]
         L.pdog_get_exact.restype = i; L.pdog_get_exact.argtypes = [p, C.POINTER(i), C.POINTER(d), C.POINTER(C.c_uint64)]
         L.pdog_get_exact_detail.restype = i; L.pdog_get_exact_detail.argtypes = [p, C.POINTER(C.c_uint64)]
+    if hasattr(L, "pdog_diag_create"):
+        L.pdog_diag_create.restype = i; L.pdog_diag_create.argtypes = [i, i, C.POINTER(p)]
+        L.pdog_diag_destroy.restype = i; L.pdog_diag_destroy.argtypes = [p]
+        L.pdog_diag_point.restype = i; L.pdog_diag_point.argtypes = [i, i, p, p]
+        L.pdog_diag_render.restype = i; L.pdog_diag_render.argtypes = [p, p, p, i64, i64, i, i, i, p, p]
     _lib = L
     return L
 

@@ -162,11 +162,59 @@ def get_start_ij_and_tracker(start_location, img, target_width, window_size, dar
 
 
 def track_frames(frames, target_width=25, start_location=None, window_size=None, darker_target=True,
-                 sar=1.0, device=0):
+                 sar=1.0, device=0, diagnostic=None):
     """The frame loop of track_one (src/PawsomeTracker.jl:159-169) on already-decoded GRAY8
     frames (decode stays with the host application): indices[1] from the bootstrap (:161),
     then indices[k] = trckr(indices[k-1]) per frame (:166-167, the intended loop).
-    `frames` is an iterable of h x w uint8 arrays.  Returns a list of 1-based (row, col)."""
+    `frames` is an iterable of h x w uint8 arrays.  Returns a list of 1-based (row, col).
+    `diagnostic` stands in for the reference's diagnostic_file (:126): None, or a callable that receives, for
+    frames 2 ... n in order, the 360 x 640 uint8 numpy buffer dia(img, point) draws (src/diagnose.jl:30-38,
+    rendered on the GPU by Diagnose); encoding it is the caller's business."""
+    if diagnostic is None:
+        return _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, None, None)
+    from .diagnose import Diagnose
+    with Diagnose(darker_target, device) as dia:
+        return _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic)
+
+
+def track_segments(segments, start_locations=None, target_width=25, window_size=None, darker_target=True,
+                   sar=1.0, device=0, diagnostic=None):
+    """track(files::AbstractVector; ...) (src/PawsomeTracker.jl:181-214) on already-decoded segments: `segments` is a
+    list of frame iterables, `start_locations` one start location per segment (default all None).  A None after the
+    first segment takes the previous segment's last position (coalesce(loc, end_location), :204-206).  One overlay
+    trace spans every segment (one `Diagnose`, :201), across frame sizes.  Returns the concatenated positions."""
+    segments = list(segments)
+    locs = [None] * len(segments) if start_locations is None else list(start_locations)
+    if len(locs) != len(segments):
+        raise ValueError(f"{len(segments)} segments but {len(locs)} start locations")     # :196
+    dia = None
+    if diagnostic is not None:
+        from .diagnose import Diagnose
+        dia = Diagnose(darker_target, device)
+    out, end = [], None
+    try:
+        for seg, loc in zip(segments, locs):
+            if loc is None and end is not None:
+                loc = ("ij", end)                                 # a CartesianIndex, :205
+            ijs = _track_one(seg, target_width, loc, window_size, darker_target, sar, device, dia, diagnostic)
+            end = ijs[-1]                                         # :206
+            out.extend(ijs)
+    finally:
+        if dia is not None:
+            dia.close()
+    return out
+
+
+def _overlay(dia, frame, ij, device):
+    """dia(trckr.img.data, indices[k]) for one host frame: it goes up, the 360 x 640 buffer comes back."""
+    import torch
+    dev = torch.device("cuda", device)
+    f = torch.from_numpy(np.ascontiguousarray(frame, np.uint8)).to(dev).unsqueeze(0)
+    p = torch.tensor([ij], dtype=torch.int32, device=dev)
+    return dia(f, p)[0].cpu().numpy()
+
+
+def _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic):
     if window_size is None:
         window_size = guess_window_size(target_width)            # :136
     window_size = fix_window_size(window_size)                   # :142
@@ -178,6 +226,8 @@ def track_frames(frames, target_width=25, start_location=None, window_size=None,
         for frame in it:
             trckr.img.data[...] = frame                          # :166
             indices.append(trckr(indices[-1]))                   # :167
+            if dia is not None:
+                diagnostic(_overlay(dia, trckr.img.data, indices[-1], device))   # :168
     finally:
         trckr.close()
     return indices
