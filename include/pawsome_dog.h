@@ -149,6 +149,7 @@ int pdog_set_exact(pdog_tracker *t, int on);
  *   "fault_inject" tests: one workgroup of a tiled chain skips an arrival (the bounded device-side waits must give up)
  *   "no_roll_map"  hard batches keep recomputing their refinement candidates
  *   "no_fold" / "fold_always"  a single remainder column always / never goes to the remainder-column kernel
+ *   "measure_global" pdog_measure reads the frame itself instead of staging each position's pixels in LDS (its path for l > 93)
  * Unknown key: PDOG_E_ARG.  Drains the tracker's stream. */
 int pdog_set_tuning(pdog_tracker *t, const char *key, int value);
 int pdog_get_exact(pdog_tracker *t, int *out_on, double *out_threshold, uint64_t *out_refined);
@@ -169,6 +170,34 @@ int pdog_get_exact_detail(pdog_tracker *t, uint64_t out[4]);
 int pdog_detect_batch(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride,
                       int64_t row_stride, int n_frames, const int32_t *d_frame_index,
                       const int32_t *d_guesses, int n, int32_t *d_out_ij, float *d_out_resp);
+
+/* ---- response and sub-pixel position at tracked points ----
+ * `findmax` (src/PawsomeTracker.jl:59) returns (value, index) and the reference keeps the index; these two entry points
+ * hand out the value, and the position to better than a pixel.  The five values of a position — the response at (i, j)
+ * and at (i-1, j), (i+1, j), (i, j-1), (i, j+1) — are this repository's RESTATEMENT of the reference's buff[I] (:57)
+ * bit for bit: dense l x l Float64, kernel column-major order, product and sum rounded apart, PaddedView fill (:48); they
+ * stand on the same two last-bit assumptions as exact mode (above).  The SUB-PIXEL RULE is this library's addition, not the
+ * reference's: per axis, with m the lower-index neighbour, p the higher one and c the centre, den = (m - c) + (p - c),
+ * num = m - p; the offset is 0 unless den < 0 (not a strict maximum along the axis, a flat patch, a NaN), otherwise
+ * (0.5 * num) / den clamped to [-0.5, 0.5]; the result is (i + offset_i, j + offset_j), 1-based (row, col) like every
+ * other position.  At a true 3-point maximum the clamp never acts. */
+/* host arithmetic of the sub-pixel rule, no GPU: resp5 = {c, up, down, left, right}.  PDOG_E_ARG for a null pointer. */
+int pdog_subpixel(const double resp5[5], const int32_t ij[2], double out_sub[2]);
+/* n positions on device-resident frames; arguments as for the detect-batch entry point above.
+ *  d_ij         n x 2 int32, 1-based (row, col): what the detect entry points wrote (batch, chain, chains); a position
+ *               outside the frame is clamped into it first (:61), its neighbours may then lie one pixel outside
+ *  d_out_resp5  NULL, or n x 5 float64 {c, up, down, left, right}
+ *  d_out_sub    NULL, or n x 2 float64, 1-based (row, col)
+ * Asynchronous on the tracker's stream: queued behind a detect call on the same tracker it needs no host wait in
+ * between.  Reads the tracker's geometry, fill and kernel table only: exact-mode counters, workspace and the chosen
+ * variant are untouched.  PDOG_E_ARG for a null tracker, null frames or null d_ij, both outputs NULL, n < 0,
+ * n_frames <= 0, row_stride < frame_w, a negative frame_stride, or more positions than frames with no frame index;
+ * n == 0 does nothing.  A frame index outside [0, n_frames) is handled as the detect-batch entry point handles it: the
+ * index array lives on the device and is NOT read by the host, so its range is the caller's responsibility (an entry
+ * outside it reads memory outside d_frames). */
+int pdog_measure(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
+                 int n_frames, const int32_t *d_frame_index, const int32_t *d_ij, int n,
+                 double *d_out_resp5, double *d_out_sub);
 
 /* One frame from HOST memory: ingest (:166) + functor (:167) + result back on
  * the host.  Synchronous.  h_resp may be NULL.  This is what the Julia shim's

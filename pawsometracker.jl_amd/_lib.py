@@ -23,6 +23,7 @@ SYMBOLS = (
     "pdog_group_detect_batch", "pdog_group_sync", "pdog_shard_range", "pdog_shard_owner", "pdog_group_test_compact",
     "pdog_set_exact", "pdog_get_exact", "pdog_get_exact_detail", "pdog_dense_kernel", "pdog_set_tuning",
     "pdog_diag_create", "pdog_diag_destroy", "pdog_diag_point", "pdog_diag_render",
+    "pdog_subpixel", "pdog_measure",
 )
 
 
@@ -139,6 +140,9 @@ def lib():
         L.pdog_diag_destroy.restype = i; L.pdog_diag_destroy.argtypes = [p]
         L.pdog_diag_point.restype = i; L.pdog_diag_point.argtypes = [i, i, p, p]
         L.pdog_diag_render.restype = i; L.pdog_diag_render.argtypes = [p, p, p, i64, i64, i, i, i, p, p]
+    if hasattr(L, "pdog_measure"):
+        L.pdog_subpixel.restype = i; L.pdog_subpixel.argtypes = [p, p, p]
+        L.pdog_measure.restype = i; L.pdog_measure.argtypes = [p, p, i64, i64, i, p, p, i, p, p]
     _lib = L
     return L
 

@@ -160,6 +160,36 @@ class BatchTracker:
                                                  nf, nc, C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
+    def measure(self, frames, ij, frame_index=None, want_resp=False):
+        """Sub-pixel positions (and peak responses) at tracked points (pdog_measure).  frames: uint8 cuda tensor
+        [nf, h, w] (row stride may exceed w); ij: int32 cuda [n, 2], 1-based (row, col) — what detect / detect_chain
+        returned; position b looks at frame frame_index[b] (int32 cuda [n]; None: frame b).  Returns float64 cuda [n, 2],
+        1-based (row, col) — and float64 [n, 5], the response {c, up, down, left, right} at the position and its four
+        neighbours, when want_resp: resp[:, 0] is the value `findmax` (src/PawsomeTracker.jl:59) drops.  Runs on torch's
+        current stream like every detect*: behind a detect call it needs no synchronisation in between.  For the
+        positions of detect_chains (frames [n_clips, n_frames, h, w], out [n_clips, n_frames, 2]):
+
+            sub = bt.measure(frames.flatten(0, 1), out.view(-1, 2)).view(n_clips, n_frames, 2)
+        """
+        import torch
+        self.use_torch_stream()
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
+        assert frames.stride(2) == 1 and frames.shape[1] == self.frame_h and frames.shape[2] == self.frame_w
+        assert ij.is_cuda and ij.dtype == torch.int32 and ij.is_contiguous() and ij.dim() == 2 and ij.shape[1] == 2
+        n = ij.shape[0]
+        sub = torch.empty((n, 2), dtype=torch.float64, device=frames.device)
+        resp = torch.empty((n, 5), dtype=torch.float64, device=frames.device) if want_resp else None
+        fi = None
+        if frame_index is not None:
+            assert frame_index.is_cuda and frame_index.dtype == torch.int32 and frame_index.is_contiguous()
+            assert frame_index.shape == (n,)
+            fi = C.c_void_p(frame_index.data_ptr())
+        _lib.check(_lib.lib().pdog_measure(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
+            C.c_void_p(ij.data_ptr()), n, C.c_void_p(resp.data_ptr()) if want_resp else None,
+            C.c_void_p(sub.data_ptr())))
+        return (sub, resp) if want_resp else sub
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().pdog_destroy(self._h)

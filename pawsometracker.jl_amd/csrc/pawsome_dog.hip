@@ -12,6 +12,7 @@
 #include "dog_fused.hpp"
 #include "dog_exact.hpp"
 #include "dog_tiled.hpp"
+#include "dog_measure.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -85,6 +86,7 @@ struct Switches {
     bool no_fold = false;                 // a single remainder column always goes to dog_thin_kernel
     bool fold_always = false;             // … always into the last strip, also below 8 strips per window
     bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
+    bool measure_global = false;          // pdog_measure reads the frame itself instead of staging each position's pixel tile in LDS
     bool fault_inject = false;            // tests: one sub-window of a tiled chain never delivers its second frame's partial (the device-side waits must give up)
     // tuning and diagnosis (diagnostic build only)
     bool host_trace = false, hpass16 = false, ingest_no_nt = false, ingest_trace = false, fused_diag = false;
@@ -1659,6 +1661,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "no_fold") t->sw.no_fold = on;
     else if (k == "fold_always") t->sw.fold_always = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
+    else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "no_fused_c") {
         t->sw.no_fused_c = on;
         t->fused_resident = 0;
@@ -1722,6 +1725,58 @@ int pdog_detect_batch(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_st
         if (rc) return rc;
     }
     return launch_detect(t, d_frames, frame_stride, row_stride, d_frame_index, d_guesses, n, d_out_ij, d_out_resp);
+}
+
+// ---- response and sub-pixel position at tracked points (dog_measure.hpp) ----
+int pdog_subpixel(const double resp5[5], const int32_t ij[2], double out_sub[2])
+{
+    if (!resp5 || !ij || !out_sub) return fail(PDOG_E_ARG, "pdog_subpixel: null pointer");
+    subpixel_rule(resp5, ij[0], ij[1], out_sub);
+    return PDOG_OK;
+}
+
+// Reads the tracker's geometry, fill and Float64 kernel table and nothing else: no workspace, no counter, no variant.
+int pdog_measure(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride, int n_frames,
+                 const int32_t *d_frame_index, const int32_t *d_ij, int n, double *d_out_resp5, double *d_out_sub)
+{
+    if (!t) return fail(PDOG_E_ARG, "pdog_measure: null tracker");
+    if (!d_frames || !d_ij) return fail(PDOG_E_ARG, "pdog_measure: null pointer");
+    if (!d_out_resp5 && !d_out_sub) return fail(PDOG_E_ARG, "pdog_measure: both outputs are null");
+    if (n < 0 || n_frames <= 0 || row_stride < t->fw || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_measure: bad size/stride");
+    if (!d_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_measure: more positions than frames and no frame index");
+    if (n == 0) return PDOG_OK;
+    HIP_TRY(hipSetDevice(t->device));
+    MeasureGeo g;
+    g.frames = d_frames;
+    g.frame_stride = frame_stride;
+    g.row_stride = row_stride;
+    g.frame_index = d_frame_index;
+    g.ij = d_ij;
+    g.n = n;
+    g.fh = t->fh;
+    g.fw = t->fw;
+    g.fill = t->fill;
+    g.L = t->L;
+    g.K64 = t->d_K64;
+    g.out_resp5 = d_out_resp5;
+    g.out_sub = d_out_sub;
+    // positions per wave: as many tiles as leave four workgroups per CU their LDS.  Below MEASURE_MIN_PPW tiles per wave
+    // (l > 93) the kernel reads the frame itself: a wave of one tile (l = 293) keeps 5 lanes of a CU busy and measured
+    // 45–72 ms per 4096 positions against 33 ms in place; 8 tiles per wave (l = 65) measured 2.5× faster than in place
+    const size_t tile = (size_t)measure_tile_bytes(t->L);
+    g.tile_pitch = measure_tile_pitch(t->L);
+    g.tile_bytes = (int)tile;
+    g.ppw = (int)std::min<size_t>(MEASURE_PPW, MEASURE_WG_LDS / tile);
+    if (g.ppw < MEASURE_MIN_PPW || t->sw.measure_global) {
+        g.ppw = MEASURE_PPW;
+        g.tile_pitch = g.tile_bytes = 0;
+    }
+    const size_t lds = (size_t)g.ppw * g.tile_bytes;
+    if (lds > 48 * 1024)
+        if (int rc = raise_lds_limit((const void *)dog_measure_kernel, lds)) return rc;
+    hipLaunchKernelGGL(dog_measure_kernel, dim3((n + g.ppw - 1) / g.ppw), dim3(MEASURE_NT), lds, t->stream, g);
+    HIP_TRY(hipGetLastError());
+    return PDOG_OK;
 }
 
 int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride, const int32_t guess[2],

@@ -47,6 +47,17 @@ def mode(img):
     return out.value
 
 
+def subpixel(resp5, ij):
+    """The sub-pixel rule (pdog_subpixel; this library's addition, not the reference's): resp5 = the response
+    {c, up, down, left, right} at the 1-based position ij and its four neighbours -> (row, col) floats.  Per axis the
+    vertex of the parabola through the three values, within half a pixel of ij; ij itself where it is no strict maximum."""
+    r = (C.c_double * 5)(*[float(v) for v in resp5])
+    src = (C.c_int32 * 2)(int(ij[0]), int(ij[1]))
+    out = (C.c_double * 2)()
+    _lib.check(_lib.lib().pdog_subpixel(r, src, out))
+    return float(out[0]), float(out[1])
+
+
 class _PaddedFrame:
     """Stands in for the PaddedView at :48: `.data` is the live frame buffer the
     caller overwrites in place each frame (:166); everything outside reads as `fillvalue`."""
@@ -75,6 +86,7 @@ class Tracker:
                                           int(self.darker_target), fillvalue, C.byref(h)))
         self._h = h
         self._resp = None
+        self.device = int(device)
 
     # -- the functor, :55-62 --
     def __call__(self, guess, want_resp=False):
@@ -89,6 +101,23 @@ class Tracker:
         _lib.check(_lib.lib().pdog_detect_host(self._h, data.ctypes.data, data.strides[0], g, out, resp_ptr))
         ij = (int(out[0]), int(out[1]))
         return (ij, resp) if want_resp else ij
+
+    def measure(self, ij, want_resp=False):
+        """Sub-pixel position (row, col) of the 1-based position ij on the current frame (`img.data`) — and, with
+        want_resp, the five responses {c, up, down, left, right} there (pdog_measure).  The frame goes up through torch,
+        the kernel runs on the tracker's own stream.  Synchronous, like the functor."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        f = torch.from_numpy(np.ascontiguousarray(self.img.data, np.uint8)).to(dev).unsqueeze(0)
+        p = torch.tensor([[int(ij[0]), int(ij[1])]], dtype=torch.int32, device=dev)
+        out = torch.empty((1, 7), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()          # the upload is on torch's stream
+        _lib.check(_lib.lib().pdog_measure(self._h, C.c_void_p(f.data_ptr()), f.stride(0), f.stride(1), 1, None,
+                                           C.c_void_p(p.data_ptr()), 1, C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(out.data_ptr() + 5 * 8)))
+        _lib.check(_lib.lib().pdog_sync(self._h))
+        v = [float(x) for x in out[0].cpu()]
+        return ((v[5], v[6]), tuple(v[:5])) if want_resp else (v[5], v[6])
 
     def info(self):
         o = _lib.PdogInfo()
@@ -162,27 +191,33 @@ def get_start_ij_and_tracker(start_location, img, target_width, window_size, dar
 
 
 def track_frames(frames, target_width=25, start_location=None, window_size=None, darker_target=True,
-                 sar=1.0, device=0, diagnostic=None):
+                 sar=1.0, device=0, diagnostic=None, subpixel=False):
     """The frame loop of track_one (src/PawsomeTracker.jl:159-169) on already-decoded GRAY8
     frames (decode stays with the host application): indices[1] from the bootstrap (:161),
     then indices[k] = trckr(indices[k-1]) per frame (:166-167, the intended loop).
     `frames` is an iterable of h x w uint8 arrays.  Returns a list of 1-based (row, col).
     `diagnostic` stands in for the reference's diagnostic_file (:126): None, or a callable that receives, for
     frames 2 ... n in order, the 360 x 640 uint8 numpy buffer dia(img, point) draws (src/diagnose.jl:30-38,
-    rendered on the GPU by Diagnose); encoding it is the caller's business."""
+    rendered on the GPU by Diagnose); encoding it is the caller's business.
+    With subpixel=True the return value is (indices, sub): sub holds one (row, col) float pair per frame, the first
+    frame included — Tracker.measure at each returned position (this library's addition; the indices are unchanged)."""
+    sub = [] if subpixel else None
     if diagnostic is None:
-        return _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, None, None)
-    from .diagnose import Diagnose
-    with Diagnose(darker_target, device) as dia:
-        return _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic)
+        ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, None, None, sub)
+    else:
+        from .diagnose import Diagnose
+        with Diagnose(darker_target, device) as dia:
+            ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub)
+    return (ijs, sub) if subpixel else ijs
 
 
 def track_segments(segments, start_locations=None, target_width=25, window_size=None, darker_target=True,
-                   sar=1.0, device=0, diagnostic=None):
+                   sar=1.0, device=0, diagnostic=None, subpixel=False):
     """track(files::AbstractVector; ...) (src/PawsomeTracker.jl:181-214) on already-decoded segments: `segments` is a
     list of frame iterables, `start_locations` one start location per segment (default all None).  A None after the
     first segment takes the previous segment's last position (coalesce(loc, end_location), :204-206).  One overlay
-    trace spans every segment (one `Diagnose`, :201), across frame sizes.  Returns the concatenated positions."""
+    trace spans every segment (one `Diagnose`, :201), across frame sizes.  Returns the concatenated positions — and,
+    with subpixel=True, (positions, sub) as track_frames does."""
     segments = list(segments)
     locs = [None] * len(segments) if start_locations is None else list(start_locations)
     if len(locs) != len(segments):
@@ -192,17 +227,18 @@ def track_segments(segments, start_locations=None, target_width=25, window_size=
         from .diagnose import Diagnose
         dia = Diagnose(darker_target, device)
     out, end = [], None
+    sub = [] if subpixel else None
     try:
         for seg, loc in zip(segments, locs):
             if loc is None and end is not None:
                 loc = ("ij", end)                                 # a CartesianIndex, :205
-            ijs = _track_one(seg, target_width, loc, window_size, darker_target, sar, device, dia, diagnostic)
+            ijs = _track_one(seg, target_width, loc, window_size, darker_target, sar, device, dia, diagnostic, sub)
             end = ijs[-1]                                         # :206
             out.extend(ijs)
     finally:
         if dia is not None:
             dia.close()
-    return out
+    return (out, sub) if subpixel else out
 
 
 def _overlay(dia, frame, ij, device):
@@ -214,7 +250,7 @@ def _overlay(dia, frame, ij, device):
     return dia(f, p)[0].cpu().numpy()
 
 
-def _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic):
+def _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub=None):
     if window_size is None:
         window_size = guess_window_size(target_width)            # :136
     window_size = fix_window_size(window_size)                   # :142
@@ -223,9 +259,13 @@ def _track_one(frames, target_width, start_location, window_size, darker_target,
     trckr, ij = get_start_ij_and_tracker(start_location, img, target_width, window_size, darker_target, sar, device)
     indices = [ij]
     try:
+        if sub is not None:
+            sub.append(trckr.measure(ij))                        # (sub: one float pair per frame, appended in place)
         for frame in it:
             trckr.img.data[...] = frame                          # :166
             indices.append(trckr(indices[-1]))                   # :167
+            if sub is not None:
+                sub.append(trckr.measure(indices[-1]))
             if dia is not None:
                 diagnostic(_overlay(dia, trckr.img.data, indices[-1], device))   # :168
     finally:
