@@ -41,8 +41,8 @@ constexpr int ROLL_P = 8;    // row-pass outputs per lane
 constexpr int ROLL_TW = 64;  // strip width = lanes
 constexpr int ROLL_PR = 65;  // R pitch (f2)
 constexpr int ROLL_LMIN = 17, ROLL_LMAX = PDOG_ROLL_LMAX; // kernel lengths with a roll instance (l = 4m+1): the l + 7 accumulators, the row-pass
-                                              // windows and the loop state fit 168 VGPRs up to l = 81 (three waves per SIMD) and 256 up to l = 97
-                                              // (two); longer kernels go to dog_twopass.hpp (round 2's l = 101 / 105 instances spilled and lost to it)
+                                              // windows and the loop state fit 168 VGPRs up to l = 81 (three waves per SIMD) and 256 from there to
+                                              // l = 149 (two; roll_lengths.def builds every length, none spills); longer kernels go to dog_twopass.hpp
 __host__ __device__ constexpr int roll_waves(int L) { return L <= 81 ? 3 : 2; } // waves per SIMD the instance is compiled for
 // Kernel lengths whose instances can FOLD a single remainder column into the last strip (LaunchGeo::fold_r).  The second
 // row-pass variant costs ≈18 VGPRs: l = 65 (the reference's default target_width) absorbs them inside its three-waves budget

@@ -6,7 +6,7 @@
 // a call reads one and writes the other).  The host keeps only their count and which one is current, so a call needs
 // no host synchronisation; the ratio (:26-28) is computed per call from its frame size, as update_ratio! does per file.
 // The kernels are in dog_diag.hpp; this file uses nothing else of the library.
-#include "../../include/pawsome_dog.h"
+#include "pdog_host.hpp"
 #include "dog_diag.hpp"
 #include <algorithm>
 #include <cmath>
@@ -14,15 +14,13 @@
 
 #pragma clang fp contract(off)
 
-extern "C" __attribute__((visibility("hidden"))) void pdog_set_error_text(const char *msg); // pawsome_dog.hip
-
 using namespace pdog;
 
 struct pdog_diag {
     int device = 0;
     int color = 255;
-    int2 *d_hist = nullptr;    // 2 x kDiagHist scaled points
-    double *d_lut = nullptr;   // raw / 255.0 for raw = 0 ... 255
+    DeviceBuffer<int2> d_hist;   // 2 x kDiagHist scaled points
+    DeviceBuffer<double> d_lut;  // raw / 255.0 for raw = 0 ... 255
     int cur = 0, hcnt = 0;     // current history buffer, points in it
     hipStream_t last = nullptr;
     bool launched = false;
@@ -30,17 +28,6 @@ struct pdog_diag {
 };
 
 namespace {
-
-int dfail(int code, const std::string &msg)
-{
-    pdog_set_error_text(msg.c_str());
-    return code;
-}
-#define D_HIP(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e__ = (expr);                                                                      \
-        if (e__ != hipSuccess) return dfail(PDOG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 constexpr int kMaxFramesPerLaunch = 1 << 15; // resize grid: 57 workgroups per frame
 
@@ -50,7 +37,7 @@ extern "C" {
 
 int pdog_diag_point(int frame_h, int frame_w, const int32_t ij[2], int32_t out[2])
 {
-    if (!ij || !out || frame_h <= 0 || frame_w <= 0) return dfail(PDOG_E_ARG, "pdog_diag_point: bad argument");
+    if (!ij || !out || frame_h <= 0 || frame_w <= 0) return fail(PDOG_E_ARG, "pdog_diag_point: bad argument");
     const int i = std::min(std::max((int)ij[0], 1), frame_h), j = std::min(std::max((int)ij[1], 1), frame_w);
     const double ry = (double)kDiagH / frame_h, rx = (double)kDiagW / frame_w; // ratio first (:27), then the product (:31)
     out[0] = (int32_t)std::nearbyint(i * ry);
@@ -60,24 +47,24 @@ int pdog_diag_point(int frame_h, int frame_w, const int32_t ij[2], int32_t out[2
 
 int pdog_diag_create(int device, int darker_target, pdog_diag **out)
 {
-    if (!out) return dfail(PDOG_E_ARG, "pdog_diag_create: out is null");
+    if (!out) return fail(PDOG_E_ARG, "pdog_diag_create: out is null");
     *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(PDOG_E_NODEV, "pdog_diag_create: no HIP device");
-    if (device < 0 || device >= ndev) return dfail(PDOG_E_ARG, "pdog_diag_create: device ordinal out of range");
-    D_HIP(hipSetDevice(device));
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDOG_E_NODEV, "pdog_diag_create: no HIP device");
+    if (device < 0 || device >= ndev) return fail(PDOG_E_ARG, "pdog_diag_create: device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
     pdog_diag *d = new pdog_diag;
     d->device = device;
     d->color = darker_target ? 255 : 0; // :17
     double lut[256];
     for (int r = 0; r < 256; ++r) lut[r] = r / 255.0;
-    hipError_t e = hipMalloc(&d->d_hist, sizeof(int2) * 2 * kDiagHist);
-    if (e == hipSuccess) e = hipMalloc(&d->d_lut, sizeof lut);
-    if (e == hipSuccess) e = hipMemcpy(d->d_lut, lut, sizeof lut, hipMemcpyHostToDevice);
+    hipError_t e = d->d_hist.try_reserve(2 * kDiagHist, nullptr);
+    if (e == hipSuccess) e = d->d_lut.try_reserve(256, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(d->d_lut.get(), lut, sizeof lut, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         pdog_diag_destroy(d);
-        return dfail(e == hipErrorOutOfMemory ? PDOG_E_ALLOC : PDOG_E_HIP, std::string("pdog_diag_create: ") + hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? PDOG_E_ALLOC : PDOG_E_HIP, std::string("pdog_diag_create: ") + hipGetErrorString(e));
     }
     *out = d;
     return PDOG_OK;
@@ -88,8 +75,6 @@ int pdog_diag_destroy(pdog_diag *d)
     if (!d) return PDOG_OK;
     (void)hipSetDevice(d->device);
     if (d->launched) (void)hipStreamSynchronize(d->last);
-    if (d->d_hist) (void)hipFree(d->d_hist);
-    if (d->d_lut) (void)hipFree(d->d_lut);
     if (d->ev) (void)hipEventDestroy(d->ev);
     delete d;
     return PDOG_OK;
@@ -98,16 +83,16 @@ int pdog_diag_destroy(pdog_diag *d)
 int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
                      int frame_h, int frame_w, int n_frames, const int32_t *d_ij, uint8_t *d_out)
 {
-    if (!d) return dfail(PDOG_E_ARG, "pdog_diag_render: null handle");
-    if (frame_h <= 0 || frame_w <= 0 || n_frames < 0) return dfail(PDOG_E_ARG, "pdog_diag_render: bad size");
+    if (!d) return fail(PDOG_E_ARG, "pdog_diag_render: null handle");
+    if (frame_h <= 0 || frame_w <= 0 || n_frames < 0) return fail(PDOG_E_ARG, "pdog_diag_render: bad size");
     if (n_frames == 0) return PDOG_OK;
-    if (!d_frames || !d_ij || !d_out) return dfail(PDOG_E_ARG, "pdog_diag_render: null pointer");
-    if (row_stride < frame_w || frame_stride < 0) return dfail(PDOG_E_ARG, "pdog_diag_render: bad stride");
+    if (!d_frames || !d_ij || !d_out) return fail(PDOG_E_ARG, "pdog_diag_render: null pointer");
+    if (row_stride < frame_w || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_diag_render: bad stride");
     hipStream_t s = (hipStream_t)hip_stream;
-    D_HIP(hipSetDevice(d->device));
+    HIP_TRY(hipSetDevice(d->device));
     if (d->launched && s != d->last) { // the trace state was last touched on another stream: order behind it
-        D_HIP(hipEventRecord(d->ev, d->last));
-        D_HIP(hipStreamWaitEvent(s, d->ev, 0));
+        HIP_TRY(hipEventRecord(d->ev, d->last));
+        HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
     }
     DiagResizeGeo rg;
     rg.frame_stride = frame_stride;
@@ -121,8 +106,8 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
     rg.offx = 0.5 - rg.sx * 0.5;
     DiagOverlayGeo og;
     og.ij = d_ij;
-    og.hist_in = d->d_hist + d->cur * kDiagHist;
-    og.hist_out = d->d_hist + (d->cur ^ 1) * kDiagHist;
+    og.hist_in = d->d_hist.get() + d->cur * kDiagHist;
+    og.hist_out = d->d_hist.get() + (d->cur ^ 1) * kDiagHist;
     og.out = d_out;
     og.n = n_frames;
     og.hcnt = d->hcnt;
@@ -137,14 +122,14 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
         rg.frames = d_frames + (int64_t)k0 * frame_stride;
         rg.out = d_out + (int64_t)k0 * kDiagFrameBytes;
         if (aligned)
-            hipLaunchKernelGGL(dog_diag_resize_kernel<true>, dim3(nk * kDiagBlocksPerFrame), dim3(kDiagResizeThreads), 0, s, rg, (const double *)d->d_lut);
+            hipLaunchKernelGGL(dog_diag_resize_kernel<true>, dim3(nk * kDiagBlocksPerFrame), dim3(kDiagResizeThreads), 0, s, rg, (const double *)d->d_lut.get());
         else
-            hipLaunchKernelGGL(dog_diag_resize_kernel<false>, dim3(nk * kDiagBlocksPerFrame), dim3(kDiagResizeThreads), 0, s, rg, (const double *)d->d_lut);
-        D_HIP(hipGetLastError());
+            hipLaunchKernelGGL(dog_diag_resize_kernel<false>, dim3(nk * kDiagBlocksPerFrame), dim3(kDiagResizeThreads), 0, s, rg, (const double *)d->d_lut.get());
+        HIP_TRY(hipGetLastError());
         og.k0 = k0;
         og.write_hist = k0 + nk == n_frames;
         hipLaunchKernelGGL(dog_diag_overlay_kernel, dim3(nk), dim3(kDiagOverlayThreads), 0, s, og);
-        D_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     d->cur ^= 1;
     d->hcnt = std::min(kDiagHist, d->hcnt + n_frames);

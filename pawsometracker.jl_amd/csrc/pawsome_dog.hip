@@ -5,7 +5,7 @@
 // exactly as the reference builds them, rounded to f32 once, and kept on the
 // device; the functor (:55-62) becomes kernel launches on a HIP stream.
 // There is NO CPU fallback: without a gfx950 device pdog_create fails.
-#include "../../include/pawsome_dog.h"
+#include "pdog_host.hpp"
 #include "dog_kernels.hpp"
 #include "dog_roll.hpp"
 #include "dog_twopass.hpp"
@@ -20,9 +20,9 @@
 #include <cstring>
 #include <cstdlib>
 #include <atomic>
-#include <emmintrin.h>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -58,14 +58,6 @@ PDOG_EPI_CLASSES(PDOG_EPI_DECL)
 } // namespace pdog
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
 
 // Run-time configuration.  The PRODUCT build reads four RESOURCE limits from the environment, once, when a tracker is
 // created (never on the launch path: a functor call's whole budget is ≈23 µs).  Everything that selects a code path is
@@ -143,41 +135,6 @@ Switches read_switches()
     return w;
 }
 
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e__ = (expr);                                                            \
-        if (e__ != hipSuccess)                                                              \
-            return fail(PDOG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));    \
-    } while (0)
-
-// ---- Float64 host arithmetic, as the reference does it ----
-double sigma_of(double tw) { return tw / (2.0 * std::sqrt(2.0 * std::log(2.0))); } // :30
-int kernel_len_of_sigma(double s) { return 4 * (int)std::ceil(s * std::sqrt(2.0)) + 1; } // Kernel.DoG
-void gaussian_1d(double s, int l, double *g)
-{ // KernelFactors.gaussian: exp(-x²/2σ²) / sum
-#pragma clang fp contract(off)
-    const int w = l >> 1;
-    for (int x = -w; x <= w; ++x) g[x + w] = std::exp(-((double)x * (double)x) / (2.0 * s * s));
-    double sum = 0.0;
-    for (int i = 0; i < l; ++i) sum += g[i];
-    for (int i = 0; i < l; ++i) g[i] /= sum;
-}
-
-// The reference's dense kernel, K = dir·(g₊⊗g₊ − g₋⊗g₋) (src/PawsomeTracker.jl:41-43), column-major, every product and
-// the difference rounded separately as Julia evaluates them: hipcc contracts a·b − c·d into an FMA by default, which
-// changes last bits — and last bits are exactly what decides the ties exact mode exists for.
-void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, double *K)
-{
-#pragma clang fp contract(off)
-    const double dir = darker ? -1.0 : 1.0;
-    for (int j = 0; j < l; ++j)
-        for (int i = 0; i < l; ++i) {
-            const double a = gp[i] * gp[j];
-            const double b = gm[i] * gm[j];
-            K[i + (size_t)l * j] = dir * (a - b);
-        }
-}
-
 // MaxDynamicSharedMemorySize is a per-function (per-device) attribute shared by every tracker in the
 // process: only ever raise it, so that a tracker with a small window cannot shrink the limit under a
 // live tracker with a large one.
@@ -197,6 +154,8 @@ int raise_lds_limit(const void *fn, size_t bytes)
 }
 
 // ---- compiled kernel specialisations ----
+// path ids that pdog_kernel_for_batch reports beside the variant ids: the fused, two-pass and tiled kernel families
+constexpr int kPathFused = 300, kPathTwoPass = 200, kPathTiled = 400;
 typedef void (*kernel_fn)(const LaunchGeo, const f2 *, const f2 *);
 struct Variant {
     int id, P, XG, Q, CH, LT, NT;
@@ -241,9 +200,9 @@ const Variant kVariants[] = {
 #include "roll_lengths.def"
 #undef PDOG_ROLL_L
     // any l: two launches with the intermediate in HBM (long kernels, target_width ≳ 40)
-    Variant { 200, 13, 16, 16, 16, 0, 256, nullptr, nullptr, false, nullptr, nullptr, 16 },
+    Variant { kPathTwoPass, 13, 16, 16, 16, 0, 256, nullptr, nullptr, false, nullptr, nullptr, 16 },
     // any l, windows whose padded tile fits in LDS: one workgroup per window, one launch (latency path)
-    Variant { 300, 1, 1, 1, 1, 0, FUSED_NT, nullptr, nullptr, false, nullptr, nullptr, 0, nullptr, true },
+    Variant { kPathFused, 1, 1, 1, 1, 0, FUSED_NT, nullptr, nullptr, false, nullptr, nullptr, 0, nullptr, true },
 #ifdef PDOG_ABLATIONS
     Variant { 101, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 1>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
     Variant { 102, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 2>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
@@ -290,7 +249,7 @@ struct pdog_tracker {
     int fused_resident = 0;        // workgroups of the fused kernel the device keeps resident (its grid is capped there: a workgroup walks several windows)
     bool fused_c = false;          // … through its compile-time-l instance (dog_fused.hpp: l = 65, the default tracker's), whose tile layout is wider
     int hp_rows = HP_ROWS;         // RT rows (window columns) per column-pass workgroup: 16 (P = 13) or 8 (P = 7)
-    int32_t *d_chain_tmp = nullptr; // [2][n_clips][2]: current guesses / step results of multi-clip chains
+    DeviceBuffer<int32_t> d_chain_tmp; // [2][n_clips][2]: current guesses / step results of multi-clip chains
     int tp_ph1 = 13, tp_php = 7;   // outputs per task of the two-pass row / column pass (pick_twopass_p)
     // tiled kernel (dog_tiled.hpp): one large window cut into sub-windows, a workgroup each, one launch per batch / clip
     bool tiled_ok = false;
@@ -298,75 +257,84 @@ struct pdog_tracker {
     int tiled_ref_cbw = 1, tiled_ref_rows = 8, tiled_resident = 0; // refinement scratch geometry; workgroups the device keeps resident
     size_t tiled_lds = 0;
     bool tiled_c = false;          // the tiled kernel's compile-time-l instance (l = 65) and tile layout
-    int *d_tiled_ctl = nullptr;    // [cap][4]: current guess (2), partial arrivals, frame flag
-    int tiled_ctl_cap = 0;
-    unsigned long long *d_tiled_slots = nullptr; // [clips][2][nsub][2] tagged partials of the tiled kernel's clips (dog_tiled.hpp)
-    long long tiled_slots_cap = 0; // in slots (clips × sub-windows)
+    DeviceBuffer<int> d_tiled_ctl; // [cap][4]: current guess (2), partial arrivals, frame flag; then the abort word
+    int tiled_ctl_cap() const { return (int)(d_tiled_ctl.capacity() / 4); }
+    DeviceBuffer<unsigned long long> d_tiled_slots; // [clips][3][nsub][2] tagged partials of the tiled kernel's clips (dog_tiled.hpp): two sets by frame parity + the V set
     unsigned tiled_tag = 0;        // advanced by chain_len + 1 per clip launch: a frame's tag never repeats
-    int chain_tmp_cap = 0;
     // two-pass path scratch
-    f2 *d_V = nullptr;
-    size_t v_bytes = 0;
+    DeviceBuffer<f2> d_V;
     // exact mode on the batch kernels of short kernels (roll / ring): windows flagged per batch as the finishing kernel reports
     // them (h_pinned[6], cumulative); batches of HARD windows (noise only, ±1-level targets: every window flagged) switch to
     // the response-map refinement like the two-pass path — 81–206 ms per 4096 windows of 257×257 without it
     unsigned flag_last = 0, win_last = 0, win_launched = 0; // flagged / finished windows last seen (h_pinned[6], [7]); windows handed to finishing kernels so far
     int flag_calm = 0;
     bool roll_map = false;
-    float *d_map = nullptr; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
-    size_t map_bytes = 0;
-    int *d_dc = nullptr;
-    int dc_cap = 0;
-    int *d_counter = nullptr;  // [kLowLatMax] zero between launches: delivered column-pass partials per window (low-latency two-pass)
+    DeviceBuffer<float> d_map; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
+    DeviceBuffer<int> d_dc;    // [cap] DC levels, then [cap] the windows' own V (exact mode)
+    DeviceBuffer<int> d_counter; // [kLowLatMax] zero between launches: delivered column-pass partials per window (low-latency two-pass)
     hipStream_t own_stream = nullptr, stream = nullptr;
     // side stream + fork/join events: the thin-remainder kernel runs beside the strips (its waves fit in
     // the registers the 2-waves-per-SIMD roll kernel leaves free) instead of after them
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    f2 *d_taps_row = nullptr, *d_taps_col = nullptr;
-    f2 *d_taps_roll = nullptr; // paired column-tap table of dog_roll.hpp
-    f2 *d_fold_r = nullptr;    // [n][n1 + l − 1] row-pass outputs of a folded remainder column (LaunchGeo::fold_r)
-    size_t fold_bytes = 0;
-    float *d_part_val = nullptr, *d_part_sec = nullptr;
-    unsigned long long *d_part_mask = nullptr;
-    int *d_part_idx = nullptr;
-    int cap_windows = 0;
+    DeviceBuffer<f2> d_taps_row, d_taps_col;
+    DeviceBuffer<f2> d_taps_roll; // paired column-tap table of dog_roll.hpp
+    DeviceBuffer<f2> d_fold_r;    // [n][n1 + l − 1] row-pass outputs of a folded remainder column (LaunchGeo::fold_r)
+    // the kernels' partials, [n][part_slots] each (ensure_capacity): part_slots is the most slots per window any variant or
+    // the tiled kernel writes, so that a later pdog_set_variant never reallocates
+    DeviceBuffer<float> d_part_val, d_part_sec;
+    DeviceBuffer<unsigned long long> d_part_mask;
+    DeviceBuffer<int> d_part_idx;
+    int part_slots = 1;
     // exact mode (dog_exact.hpp): windows whose two best FP32 responses lie within 2δ are re-decided in the
     // reference's own Float64 arithmetic
     bool exact = true;
     bool exact_all = false;           // pdog_set_exact(t, 2): refine every window with an infinite threshold (tests: the whole reference computation on the device)
     std::vector<double> h_gp, h_gm;   // the two Float64 Gaussians (host copy): the error bounds follow the kernels' operation order over THESE taps
     double F_sym_int = 0, F_sym_sep = 0, F_ring = 0, F_rescan = 0; // error-bound factors per kernel family (exact_factors)
-    double *d_K64 = nullptr;          // dir·(g₊⊗g₊ − g₋⊗g₋), l×l column-major, Float64 (:41-43)
-    double *d_g64 = nullptr;          // [2][l] the two normalised Gaussians in Float64 (the refinement's separable stage)
-    RefineParams *d_rp = nullptr;     // {K64, g64, dir, T64} for the kernels that refine inline
+    DeviceBuffer<double> d_K64;       // dir·(g₊⊗g₊ − g₋⊗g₋), l×l column-major, Float64 (:41-43)
+    DeviceBuffer<double> d_g64;       // [2][l] the two normalised Gaussians in Float64 (the refinement's separable stage)
+    DeviceBuffer<RefineParams> d_rp;  // {K64, g64, dir, T64} for the kernels that refine inline
     double exact_T64 = 0.0;           // 2δ64: separable Float64 against the reference's dense Float64
-    unsigned long long *d_ref_stat = nullptr;
+    DeviceBuffer<unsigned long long> d_ref_stat;
     int ref_cbw = 1, ref_rows = 8;    // refinement: window columns per block; rows of the block's pixel tile resident in LDS at a time
     int fused_ref_cbw = 1, fused_ref_rows = 8; // the same inside the fused kernel (its scratch is that kernel's LDS)
     // host-path staging (pdog_detect_host / chain seed)
-    uint8_t *d_frame = nullptr;
-    int32_t *d_small = nullptr; // [0..1] guess, [2..3] result
-    int32_t *h_pinned = nullptr; // pinned, host-coherent mailbox: [0..1] guess, [2..3] result, [4] completion ticket of the functor
+    DeviceBuffer<uint8_t> d_frame;
+    DeviceBuffer<int32_t> d_small; // [0..1] guess, [2..3] result
+    // pinned, host-coherent, device-mapped mailbox: [0..1] guess, [2..3] result, [4] completion ticket of the functor,
+    // [5] raised by kernels (drain_and_check), [6] / [7] flagged / finished windows (launch_strips)
+    PinnedBuffer<int32_t> h_pinned{hipHostMallocMapped | hipHostMallocCoherent};
     int32_t ticket = 0;
-    float *d_resp = nullptr;
-    uint8_t *h_tile = nullptr;   // pinned, device-mapped: the functor's window tile when the fused kernel reads it in place
-    uint8_t *d_tile_map = nullptr; // device addresses of h_tile and of the h_pinned mailbox
-    int32_t *d_mail_map = nullptr;
+    DeviceBuffer<float> d_resp;
+    PinnedBuffer<uint8_t> h_tile{hipHostMallocMapped}; // the functor's window tile when the kernels read it in place
     // host-batch ingest (pdog_detect_batch_host): rotating pinned staging / device tile slots
     static constexpr int kIngestSlots = 3;
-    uint8_t *h_stage[kIngestSlots] = {nullptr, nullptr, nullptr};
-    uint8_t *d_tiles[kIngestSlots] = {nullptr, nullptr, nullptr};
-    size_t ingest_slot_bytes = 0;
-    int32_t *d_ingest_guess = nullptr, *d_ingest_out = nullptr, *h_ingest_out = nullptr;
-    int ingest_cap = 0, ingest_guess_cap = 0;
+    PinnedBuffer<uint8_t> h_stage[kIngestSlots];
+    DeviceBuffer<uint8_t> d_tiles[kIngestSlots];
+    DeviceBuffer<int32_t> d_ingest_guess, d_ingest_out;
+    PinnedBuffer<int32_t> h_ingest_out;
     hipStream_t h2d_stream = nullptr;
     hipEvent_t ev_h2d[kIngestSlots] = {nullptr, nullptr, nullptr}, ev_used[kIngestSlots] = {nullptr, nullptr, nullptr};
+
+    // Drains and destroys the streams and events; the buffers free themselves after that.
+    ~pdog_tracker()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (hipStream_t s : {h2d_stream, aux_stream})
+            if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+        for (int k = 0; k < kIngestSlots; ++k)
+            for (hipEvent_t e : {ev_h2d[k], ev_used[k]})
+                if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_fork, ev_join, ev_switch})
+            if (e) (void)hipEventDestroy(e);
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
 };
 
 namespace {
 
-void pack_tile(const pdog_tracker *t, const uint8_t *frame, int64_t row_stride, int g1, int g2, uint8_t *dst, int pitch);
 typedef void (*fused_fn_t)(const FusedGeo, const f2 *, const f2 *);
 fused_fn_t fused_kernel_for(const pdog_tracker *t, bool resp);
 
@@ -438,6 +406,8 @@ tp_fn hpass8_kernel_for(int P, bool resp, bool fin, int U, bool flush)
 #undef PDOG_HP8
 #undef PDOG_HP8F
 }
+tp_fn h1_kernel(const pdog_tracker *t, bool dcin) { return h1_kernel_for(t->tp_ph1, dcin, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L); }
+tp_fn hpass8_kernel(const pdog_tracker *t, bool resp, bool fin) { return hpass8_kernel_for(t->tp_php, resp, fin, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L); }
 int pick_h1_outputs(int nout)
 {
     auto fill = [&](int p) { return (double)nout / (double)(round_up(nout, 16 * p)); };
@@ -513,6 +483,10 @@ const void *tiled_kernel_for(const pdog_tracker *t, bool resp)
 int setup_tiled(pdog_tracker *t)
 {
     t->tiled_ok = false;
+    // partial slots per window: the most over all variants, so that a later pdog_set_variant never reallocates …
+    t->part_slots = (t->n2 + 7) / 8;
+    for (int i = 0; i < kNumVariants; ++i)
+        if (!kVariants[i].fused) t->part_slots = std::max(t->part_slots, (t->n2 + kVariants[i].tw() - 1) / kVariants[i].tw() + kThinMax);
     if ((t->fused_ok && !t->sw.tiled_force) || t->sw.no_tiled || t->fw < 4) return PDOG_OK;
     // Sub-window edge: ≈32 measured best for a 257×257 window (81 workgroups: 13.9 µs per frame; 48: 15.3), but beyond
     // ≈128 workgroups the partial exchange costs more than smaller tiles save (513×513: 121 workgroups of 47 → 17.8 µs,
@@ -570,47 +544,72 @@ int setup_tiled(pdog_tracker *t)
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tiled_kernel_for(t, false), FUSED_NT, base) == hipSuccess && per_cu >= 1 &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess)
         t->tiled_resident = per_cu * cus;
+    t->part_slots = std::max(t->part_slots, 2 * ns1 * ns2); // … and the tiled kernel's partials: two sets per window
     t->tiled_ok = true;
     return PDOG_OK;
 }
 
-// n windows (chain_len = 1: independent; ordinary launch) or n clips of chain_len frames (cooperative launch: the
+// What a launch works on.  A caller sets the fields it uses; the rest keep these defaults.
+struct Request {
+    const uint8_t *frames = nullptr;
+    int64_t frame_stride = 0, row_stride = 0;
+    const int32_t *frame_index = nullptr;  // may stay null: window b looks at frame b
+    const int32_t *guesses = nullptr;      // n x 2 (chains: the clips' start guesses)
+    int n = 0;                             // windows, or clips of chain_len frames
+    int chain_len = 1;
+    int32_t *out_ij = nullptr;
+    float *out_resp = nullptr;
+    int fh = 0, fw = 0;                    // frame size as the kernels see it (0: the tracker's; the packed window tiles of the host paths differ)
+    int32_t *done_flag = nullptr;          // published with done_value after the answer (single-window paths), or, with
+    int32_t done_value = 0;                // `progress`, with k + 1 after frame k of a chain
+    bool progress = false;
+    int dc_host = -1;                      // the window's DC level where the host already sampled it
+};
+
+// The LaunchGeo fields every path fills the same way; everything else is zero.  A path then sets what it uses: the
+// partial arrays, ex, nstrips / nslots / nblocks and its own geometry.
+LaunchGeo base_geo(const pdog_tracker *t, const Request &req)
+{
+    LaunchGeo g;
+    std::memset(&g, 0, sizeof g);
+    g.frames = req.frames;
+    g.frame_stride = req.frame_stride;
+    g.row_stride = req.row_stride;
+    g.frame_index = req.frame_index;
+    g.guesses = req.guesses;
+    g.resp = req.out_resp;
+    g.fh = req.fh ? req.fh : t->fh; g.fw = req.fw ? req.fw : t->fw;
+    g.r1 = t->r1; g.r2 = t->r2; g.n1 = t->n1; g.n2 = t->n2;
+    g.L = t->L; g.fill = t->fill; g.n = req.n;
+    return g;
+}
+void use_partials(const pdog_tracker *t, LaunchGeo &g)
+{
+    g.part_val = t->d_part_val.get();
+    g.part_idx = t->d_part_idx.get();
+    g.part_sec = t->d_part_sec.get();
+    g.part_mask = t->d_part_mask.get();
+}
+
+// req.n windows (chain_len = 1: independent; ordinary launch) or req.n clips of chain_len frames (cooperative launch: the
 // workgroups of a clip wait for each other's partials frame by frame).  *launched = false: not taken, the caller goes on.
-int launch_tiled(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride, const int32_t *d_frame_index,
-                 const int32_t *d_guesses, int n, int chain_len, int32_t *d_out_ij, float *d_out_resp, int FH, int FW,
-                 int32_t *d_done_flag, int32_t done_value, bool progress, bool *launched, int dc_host = -1)
+int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
 {
     *launched = false;
+    const int n = req.n, chain_len = req.chain_len;
     if (!t->tiled_ok || n < 1) return PDOG_OK;
     const int nsub = t->tiled_ns1 * t->tiled_ns2;
     if (chain_len > 1 && (long long)n * nsub > t->tiled_resident) return PDOG_OK;
-    if (t->cap_windows < n || t->tiled_ctl_cap < n) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (t->cap_windows < n) { if (int rc = ensure_capacity(t, n)) return rc; }
-        if (t->tiled_ctl_cap < n) {
-            if (t->d_tiled_ctl) (void)hipFree(t->d_tiled_ctl);
-            t->d_tiled_ctl = nullptr; t->tiled_ctl_cap = 0;
-            HIP_TRY(hipMalloc(&t->d_tiled_ctl, sizeof(int) * (4 * (size_t)n + 1)));
-            HIP_TRY(hipMemset(t->d_tiled_ctl, 0, sizeof(int) * (4 * (size_t)n + 1))); // the kernel leaves its counters at zero; the last word is the abort word
-            t->tiled_ctl_cap = n;
-        }
-    }
+    if (int rc = ensure_capacity(t, n)) return rc;
+    // the kernel leaves its counters at zero; the last word is the abort word
+    if (int rc = t->d_tiled_ctl.reserve(4 * (size_t)n + 1, &t->stream, true)) return rc;
     TiledGeo tg;
     std::memset(&tg, 0, sizeof tg);
     LaunchGeo &g = tg.g;
-    g.frames = d_frames;
-    g.frame_stride = frame_stride;
-    g.row_stride = row_stride;
-    g.frame_index = d_frame_index;
-    g.guesses = d_guesses;
-    g.resp = d_out_resp;
-    g.part_val = t->d_part_val;
-    g.part_idx = t->d_part_idx;
-    g.part_sec = t->d_part_sec;
-    g.part_mask = t->d_part_mask;
+    g = base_geo(t, req);
+    use_partials(t, g);
     g.ex = exact_ctl(t, kFamFused);
-    g.fh = FH; g.fw = FW; g.r1 = t->r1; g.r2 = t->r2; g.n1 = t->n1; g.n2 = t->n2;
-    g.L = t->L; g.fill = t->fill; g.nstrips = nsub; g.nslots = nsub; g.n = n; g.nblocks = n * nsub;
+    g.nstrips = nsub; g.nslots = nsub; g.nblocks = n * nsub;
     tg.NA = t->n1 + t->L - 1;
     tg.TWin = t->n2 + t->L - 1;
     tg.sn1 = t->tiled_sn1; tg.sn2 = t->tiled_sn2; tg.ns1 = t->tiled_ns1; tg.ns2 = t->tiled_ns2;
@@ -620,36 +619,28 @@ int launch_tiled(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride,
     tg.pr = t->tiled_pr;
     tg.pc = t->tiled_pc;
     tg.chain_len = chain_len;
-    tg.out_ij = d_out_ij;
-    tg.done_flag = d_done_flag;
-    tg.done_value = done_value;
-    tg.progress = progress ? 1 : 0;
-    tg.rp = t->exact ? t->d_rp : nullptr;
+    tg.out_ij = req.out_ij;
+    tg.done_flag = req.done_flag;
+    tg.done_value = req.done_value;
+    tg.progress = req.progress ? 1 : 0;
+    tg.rp = t->exact ? t->d_rp.get() : nullptr;
     tg.ref_cbw = t->tiled_ref_cbw;
     tg.ref_rows = t->tiled_ref_rows;
-    tg.dc_host = dc_host;
-    tg.cur = t->d_tiled_ctl;
-    tg.sync = reinterpret_cast<unsigned *>(t->d_tiled_ctl + 2 * (size_t)t->tiled_ctl_cap);
-    tg.abort = reinterpret_cast<unsigned *>(t->d_tiled_ctl + 4 * (size_t)t->tiled_ctl_cap);
+    tg.dc_host = req.dc_host;
+    tg.cur = t->d_tiled_ctl.get();
+    tg.sync = reinterpret_cast<unsigned *>(t->d_tiled_ctl.get() + 2 * (size_t)t->tiled_ctl_cap());
+    tg.abort = reinterpret_cast<unsigned *>(t->d_tiled_ctl.get() + 4 * (size_t)t->tiled_ctl_cap());
     tg.fault_inject = t->sw.fault_inject ? 1 : 0;
     tg.slots = nullptr;
     tg.tag_base = 0;
     if (chain_len > 1) {
-        if (t->tiled_slots_cap < (long long)n * nsub) {
-            HIP_TRY(hipStreamSynchronize(t->stream));
-            if (t->d_tiled_slots) (void)hipFree(t->d_tiled_slots);
-            t->d_tiled_slots = nullptr; t->tiled_slots_cap = 0;
-            const size_t bytes = sizeof(unsigned long long) * (size_t)n * 3 * nsub * 2; // two partial sets by frame parity + the V set
-            HIP_TRY(hipMalloc(&t->d_tiled_slots, bytes));
-            HIP_TRY(hipMemset(t->d_tiled_slots, 0, bytes)); // tag 0 is never a frame's
-            t->tiled_slots_cap = (long long)n * nsub;
-        }
-        tg.slots = t->d_tiled_slots;
+        if (int rc = t->d_tiled_slots.reserve((size_t)n * 3 * nsub * 2, &t->stream, true)) return rc; // zeroed: tag 0 is never a frame's
+        tg.slots = t->d_tiled_slots.get();
         tg.tag_base = t->tiled_tag;
         t->tiled_tag += (unsigned)chain_len + 1u;
     }
-    const void *fn = tiled_kernel_for(t, d_out_resp != nullptr);
-    const f2 *tr = t->d_taps_row, *tc = t->d_taps_col;
+    const void *fn = tiled_kernel_for(t, req.out_resp != nullptr);
+    const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
     if (chain_len > 1) {
         void *args[] = {(void *)&tg, (void *)&tr, (void *)&tc};
         const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(n * nsub), dim3(FUSED_NT), args, (unsigned)t->tiled_lds, t->stream);
@@ -663,9 +654,8 @@ int launch_tiled(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride,
     return PDOG_OK;
 }
 
-// Longest kernel with a roll instance (dog_roll.hpp, roll_lengths.def).  Round 2 also built l = 101 / 105: they spilled in
-// their loop and measured 3.95 / 4.15 ms per 4096 windows of 257×257 against 3.54 / 3.65 ms for the two-pass kernels, so
-// they are gone; longer kernels take the two-pass path.
+// Kernel lengths with a roll instance: l = 17 … 149 (dog_roll.hpp, roll_lengths.def; l = 101 … 149 at two waves per SIMD,
+// without spills); longer kernels take the two-pass path.
 
 int choose_variant(pdog_tracker *t, int forced)
 {
@@ -732,9 +722,9 @@ int choose_variant(pdog_tracker *t, int forced)
             }
             for (bool resp : {false, true})
                 for (bool fin : {false, true})
-                    if (int rc = raise_lds_limit((const void *)hpass8_kernel_for(t->tp_php, resp, fin, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L), hl8)) return rc;
+                    if (int rc = raise_lds_limit((const void *)hpass8_kernel(t, resp, fin), hl8)) return rc;
             for (bool dcin : {false, true})
-                if (int rc = raise_lds_limit((const void *)h1_kernel_for(t->tp_ph1, dcin, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L), h1l)) return rc;
+                if (int rc = raise_lds_limit((const void *)h1_kernel(t, dcin), h1l)) return rc;
             t->small_twopass = true;
         }
     }
@@ -762,27 +752,17 @@ int choose_variant(pdog_tracker *t, int forced)
     return PDOG_OK;
 }
 
+// Room for the partials of n windows.  Growing drains the tracker's stream first, once (the four arrays grow together;
+// a failure leaves the later ones empty, so the smallest capacity decides).
 int ensure_capacity(pdog_tracker *t, int n)
 {
-    if (n <= t->cap_windows) return PDOG_OK;
-    // worst case strips over all variants so a later pdog_set_variant never reallocates
-    int max_strips = 1;
-    for (int i = 0; i < kNumVariants; ++i)
-        if (!kVariants[i].fused) max_strips = std::max(max_strips, (t->n2 + kVariants[i].tw() - 1) / kVariants[i].tw() + kThinMax);
-    max_strips = std::max(max_strips, (t->n2 + 7) / 8);
-    if (t->tiled_ok) max_strips = std::max(max_strips, 2 * t->tiled_ns1 * t->tiled_ns2); // the tiled kernel's partials: two sets per window
-    for (void *p : {(void *)t->d_part_val, (void *)t->d_part_idx, (void *)t->d_part_sec, (void *)t->d_part_mask})
-        if (p) (void)hipFree(p);
-    t->d_part_val = t->d_part_sec = nullptr;
-    t->d_part_idx = nullptr;
-    t->d_part_mask = nullptr;
-    t->cap_windows = 0;
-    HIP_TRY(hipMalloc(&t->d_part_val, sizeof(float) * (size_t)n * max_strips));
-    HIP_TRY(hipMalloc(&t->d_part_sec, sizeof(float) * (size_t)n * max_strips));
-    HIP_TRY(hipMalloc(&t->d_part_idx, sizeof(int) * (size_t)n * max_strips));
-    HIP_TRY(hipMalloc(&t->d_part_mask, sizeof(unsigned long long) * (size_t)n * max_strips));
-    t->cap_windows = n;
-    return PDOG_OK;
+    const size_t need = (size_t)n * t->part_slots;
+    if (need <= std::min({t->d_part_val.capacity(), t->d_part_sec.capacity(), t->d_part_idx.capacity(), t->d_part_mask.capacity()})) return PDOG_OK;
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    if (int rc = t->d_part_val.reserve(need, nullptr)) return rc;
+    if (int rc = t->d_part_sec.reserve(need, nullptr)) return rc;
+    if (int rc = t->d_part_idx.reserve(need, nullptr)) return rc;
+    return t->d_part_mask.reserve(need, nullptr);
 }
 
 // fused-kernel instance (runtime kernel length)
@@ -797,11 +777,10 @@ fused_fn_t fused_kernel_for(const pdog_tracker *t, bool resp)
     return resp ? (fused_fn_t)dog_fused_kernel<true> : (fused_fn_t)dog_fused_kernel<false>;
 }
 
-// Which kernel family a batch of n windows runs on (variant ids: 300 fused, 200 two-pass, otherwise the tracker's
+// Which kernel family a batch of n windows runs on (kPathFused, kPathTiled, kPathTwoPass, otherwise the tracker's
 // batch kernel).  A batch of fewer than ≈1000 strip-waves cannot fill 256 CUs × 8 waves with one wave per strip:
 // windows that fit in LDS then go to the fused kernel (one workgroup per window, one launch), larger ones to the
 // two-pass kernels (dozens of workgroups per window).  pdog_set_variant pins the tracker's kernel.
-constexpr int kPathFused = 300, kPathTwoPass = 200, kPathTiled = 400;
 int path_for_batch(const pdog_tracker *t, int n)
 {
     const Variant &v = *t->var;
@@ -819,40 +798,7 @@ int path_for_batch(const pdog_tracker *t, int n)
     return v.id;
 }
 
-// ---- exact mode's FP32 error bounds, per kernel family (dog_exact.hpp: the guarantee) ----
-// An FMA chain ŝ_i = fl(ŝ_{i−1} + a_i·b̂_i) satisfies |ŝ_n − s_n| ≤ u·(1 + u)·Σ_i |ŝ_i| (each step rounds its own result once), and
-// |ŝ_i| ≤ V·W_i·(1 + nu) where W_i = Σ_{j ≤ i} |b_j|·max|a_j|/V is the cumulative tap weight IN THE ORDER THE KERNEL ADDS THEM.  The
-// Gaussians sum to 1, so Σ_i W_i is far below the chain length n that the order-blind bound n·u·V charges: the kernels add the
-// smallest taps (the kernel's edges) first.  The factors below are Σ_i W_i evaluated numerically over the tracker's own Float64
-// taps for each family's operation order (+1 per rounded tap table, +2 for a final channel addition); δ = u·(V/255)·F·1.02:
-//   row pass, symmetric pairs from the edge inwards, centre last (roll, thin, fused, tiled, two-pass):  W_i = Σ_{j ≤ i} 2g[j]
-//   row pass, plain chain over the l taps (ring kernels; the refinement's FP32 rescan):               W_i = Σ_{j ≤ i} g[j]
-//   column pass, one f32 per output taking (+, −) terms alternately (roll, thin, folded column, rescan): both cumulative weights per step
-//   column pass, the two Gaussians in separate chains, added at the end (ring, fused, tiled, two-pass)
-//   two-pass: every chain is one trip of the register ring long, the chains' sums are added up (dog_twopass.hpp) — per chain its own
-//   cumulative weights from zero, plus the running total's weight per addition
-// l = 65: 157 (roll) / 94 (fused, tiled) / 138 (ring) against the order-blind 6l + 4 = 394;  l = 293 two-pass: 72 against 1762.
-struct ExactFactors { double sym_int, sym_sep, ring, rescan; };
-ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm)
-{
-    const int l = (int)gp.size(), H = l / 2;
-    auto row_sym = [&](const std::vector<double> &g) { double W = 0, F = 0; for (int k = 0; k <= H; ++k) { W += (k < H ? 2.0 : 1.0) * g[k]; F += W; } return F + 1.0; };
-    auto row_plain = [&](const std::vector<double> &g) { double W = 0, F = 0; for (int k = 0; k < l; ++k) { W += g[k]; F += W; } return F + 1.0; };
-    double Gp = 0, Gm = 0, c_sep = 4.0, c_int = 2.0;
-    for (int t = 0; t < l; ++t) {
-        Gp += gp[t];
-        c_int += Gp + Gm; // after the + term of tap t
-        Gm += gm[t];
-        c_int += Gp + Gm; // after the − term
-        c_sep += Gp + Gm;
-    }
-    ExactFactors f;
-    f.sym_int = row_sym(gp) + row_sym(gm) + c_int;
-    f.sym_sep = row_sym(gp) + row_sym(gm) + c_sep;
-    f.ring = row_plain(gp) + row_plain(gm) + c_sep;
-    f.rescan = row_plain(gp) + row_plain(gm) + c_int;
-    return f;
-}
+// ---- exact mode's FP32 error bounds: exact_factors (pdog_math.cpp) per kernel family, and here ----
 // the two-pass kernels' factor for the tracker's task sizes (hr8: the 8-row column-pass kernels, else the 16-row form <13, 16>)
 double twopass_factor(const pdog_tracker *t, bool hr8)
 {
@@ -883,8 +829,8 @@ double twopass_factor(const pdog_tracker *t, bool hr8)
 ExactCtl exact_ctl(const pdog_tracker *t, KernelFamily fam)
 {
     ExactCtl x;
-    x.stat = t->d_ref_stat;
-    x.range_err = t->d_mail_map ? t->d_mail_map + 5 : nullptr;
+    x.stat = t->d_ref_stat.get();
+    x.range_err = t->h_pinned.device() ? t->h_pinned.device() + 5 : nullptr;
     const double F = fam == kFamRoll ? t->F_sym_int : fam == kFamRing ? t->F_ring : fam == kFamFused ? t->F_sym_sep : twopass_factor(t, fam == kFamTwoPass8);
     const double u = std::ldexp(1.0, -24);
     x.T = t->exact_all ? __builtin_huge_valf() : std::nextafter((float)(2.0 * u * F * 1.02 + 2e-9), 1.0f);
@@ -897,28 +843,35 @@ ExactCtl exact_ctl(const pdog_tracker *t, KernelFamily fam)
 // partial slots the main kernels wrote map to window columns (the refinement only rescans column blocks whose slot
 // can hold a near-maximal pixel).  With done_flag set the kernel also publishes the host functor's ticket with
 // window 0's final answer.
-int launch_finish(pdog_tracker *t, const LaunchGeo &g, int slot_w, int slot_last, int32_t *d_out_ij, int32_t *d_done_flag, int32_t done_value,
-                  bool use_mask = false, const float *map = nullptr, const int *vmax = nullptr)
+struct Finish {
+    int slot_w = 0, slot_last = 1 << 30;
+    bool use_mask = false;
+    const float *map = nullptr; // the batch's FP32 responses (exact mode reads its candidates off them), or null
+    const int *vmax = nullptr;  // the windows' own max |pixel − dc|, where the row pass collected it
+    int32_t *out_ij = nullptr, *done_flag = nullptr;
+    int32_t done_value = 0;
+};
+int launch_finish(pdog_tracker *t, const LaunchGeo &g, const Finish &f)
 {
     FinishGeo fg;
     fg.g = g;
-    fg.map = map;
-    fg.vmax = vmax;
-    fg.K64 = t->exact ? t->d_K64 : nullptr;
-    fg.g64 = t->d_g64;
+    fg.map = t->exact ? f.map : nullptr;
+    fg.vmax = f.vmax;
+    fg.K64 = t->exact ? t->d_K64.get() : nullptr;
+    fg.g64 = t->d_g64.get();
     fg.dir = t->darker ? -1.0 : 1.0;
     fg.T64 = t->exact_T64;
     fg.cbw = t->ref_cbw;
     fg.tile_rows = t->ref_rows;
-    fg.slot_w = slot_w;
-    fg.slot_last = slot_last;
+    fg.slot_w = f.slot_w;
+    fg.slot_last = f.slot_last;
     fg.nmain = g.nslots - g.nthin;
     fg.thin_x0 = g.thin_x0;
-    fg.use_mask = use_mask ? 1 : 0;
+    fg.use_mask = f.use_mask ? 1 : 0;
     fg.v_after = t->sw.v_after;
-    fg.out_ij = d_out_ij;
-    fg.done_flag = d_done_flag;
-    fg.done_value = done_value;
+    fg.out_ij = f.out_ij;
+    fg.done_flag = f.done_flag;
+    fg.done_value = f.done_value;
     fg.seq_windows = (int)t->win_launched;
     t->win_launched += (unsigned)g.n;
     size_t lds = t->exact ? refine_lds_bytes(t->n1, t->L, t->ref_cbw, t->ref_rows) : 0;
@@ -926,80 +879,57 @@ int launch_finish(pdog_tracker *t, const LaunchGeo &g, int slot_w, int slot_last
         lds = std::max(lds, (size_t)FINISH_WPB * (t->n1 + t->L - 1 + FOLD_GO) * sizeof(f2));
         if (int rc = raise_lds_limit((const void *)dog_finish_kernel, lds)) return rc;
     }
-    hipLaunchKernelGGL(dog_finish_kernel, dim3((g.n + FINISH_WPB - 1) / FINISH_WPB), dim3(REFINE_NT), lds, t->stream, fg, (const f2 *)t->d_taps_row,
-                       (const f2 *)t->d_taps_col);
+    hipLaunchKernelGGL(dog_finish_kernel, dim3((g.n + FINISH_WPB - 1) / FINISH_WPB), dim3(REFINE_NT), lds, t->stream, fg, (const f2 *)t->d_taps_row.get(),
+                       (const f2 *)t->d_taps_col.get());
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
 }
 
 // One workgroup per window (chain_len = 1) or per clip (chain_len frames, frame k > 0 starts at frame k−1's answer).
-int launch_fused(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
-                 const int32_t *d_frame_index, const int32_t *d_guesses, int n, int chain_len, int32_t *d_out_ij,
-                 float *d_out_resp, int FH, int FW, int32_t *d_done_flag = nullptr, int32_t done_value = 0, bool progress = false, int dc_host = -1)
+int launch_fused(pdog_tracker *t, const Request &req)
 {
+    const int n = req.n, chain_len = req.chain_len;
     FusedGeo fg;
+    fg.g = base_geo(t, req);
     LaunchGeo &g = fg.g;
-    std::memset(&g, 0, sizeof g);
-    g.frames = d_frames;
-    g.frame_stride = frame_stride;
-    g.row_stride = row_stride;
-    g.frame_index = d_frame_index;
-    g.guesses = d_guesses;
-    g.resp = d_out_resp;
-    g.fh = FH; g.fw = FW; g.r1 = t->r1; g.r2 = t->r2; g.n1 = t->n1; g.n2 = t->n2;
-    g.L = t->L; g.fill = t->fill; g.nstrips = 1; g.n = n; g.nslots = 1; g.nblocks = n;
+    g.nstrips = 1; g.nslots = 1; g.nblocks = n;
     fg.NA = t->n1 + t->L - 1;
     fg.TWin = t->n2 + t->L - 1;
     fg.pitchA = t->fused_c ? fusedc_pitch_a(t->n2, t->L) : fused_pitch_a(t->n2, t->L);
     fg.pitchV = fused_pitch_v(t->n1, t->L);
     fg.cshift = 0;
     while ((1 << fg.cshift) < (fg.TWin + 3) / 4) ++fg.cshift;
-    // outputs per task: fewest rounds of 1024 tasks, then least work per task (≈ P outputs + 2 of fixed cost)
-    auto pick = [](int lines, int nout, std::initializer_list<int> ps, double fixed) {
-        int best = 0;
-        double best_cost = 0;
-        for (int p : ps) {
-            const long long tasks = (long long)lines * ((nout + p - 1) / p);
-            const double cost = (double)((tasks + FUSED_NT - 1) / FUSED_NT) * (p + fixed);
-            if (!best || cost < best_cost) { best = p; best_cost = cost; }
-        }
-        return best;
-    };
-    fg.pr = pick(fg.NA, t->n2, {3, 4, 5, 6, 8}, 2.0);
-    fg.pc = pick(t->n2, t->n1, {2, 3, 4, 6, 8}, 1.5);
-    if (t->fused_c) fg.pr = fusedc_row_outputs(fg.NA, t->n2);
+    fg.pr = t->fused_c ? fusedc_row_outputs(fg.NA, t->n2) : pick_outputs_per_task(fg.NA, t->n2, {3, 4, 5, 6, 8}, 2.0);
+    fg.pc = pick_outputs_per_task(t->n2, t->n1, {2, 3, 4, 6, 8}, 1.5);
     if (t->sw.fused_pr) { fg.pr = t->sw.fused_pr; fg.pc = t->sw.fused_pc; } // tuning switch PDOG_FUSED_P
     fg.chain_len = chain_len;
-    fg.out_ij = d_out_ij;
-    fg.done_flag = d_done_flag;
-    fg.done_value = done_value;
-    fg.progress = progress ? 1 : 0;
-    fg.rp = t->exact ? t->d_rp : nullptr;
+    fg.out_ij = req.out_ij;
+    fg.done_flag = req.done_flag;
+    fg.done_value = req.done_value;
+    fg.progress = req.progress ? 1 : 0;
+    fg.rp = t->exact ? t->d_rp.get() : nullptr;
     fg.ref_cbw = t->fused_ref_cbw;
     fg.ref_rows = t->fused_ref_rows;
-    fg.dc_host = dc_host;
+    fg.dc_host = req.dc_host;
     g.ex = exact_ctl(t, kFamFused);
     const size_t lds = fused_total_lds(t);
-    typedef fused_fn_t fused_fn;
-    fused_fn fn = fused_kernel_for(t, d_out_resp != nullptr);
+    fused_fn_t fn = fused_kernel_for(t, req.out_resp != nullptr);
+    const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
 #ifdef PDOG_ABLATIONS
-    if (d_out_resp && t->sw.fused_diag) { // phase stamps instead of the response (tools/fused_phases.py)
-        fn = (t->fused_c && t->L == 65) ? (fused_fn)dog_fused_kernel<true, 1, 65> : (fused_fn)dog_fused_kernel<true, 1>;
+    if (req.out_resp && t->sw.fused_diag) { // phase stamps instead of the response (tools/fused_phases.py)
+        fn = (t->fused_c && t->L == 65) ? (fused_fn_t)dog_fused_kernel<true, 1, 65> : (fused_fn_t)dog_fused_kernel<true, 1>;
         if (int rc = raise_lds_limit((const void *)fn, lds)) return rc;
     }
-#endif
-#ifdef PDOG_ABLATIONS
-    if (!d_out_resp && t->sw.fused_diag && chain_len > 8) { // a chain's steady state: stamps of every frame, the median printed per phase
-        float *d_st = nullptr;
-        HIP_TRY(hipMalloc(&d_st, sizeof(float) * (16 * chain_len + 64)));
-        fg.g.resp = d_st;
-        fn = (t->fused_c && t->L == 65) ? (fused_fn)dog_fused_kernel<true, 1, 65> : (fused_fn)dog_fused_kernel<true, 1>;
-        if (int rc = raise_lds_limit((const void *)fn, lds)) return rc;
-        hipLaunchKernelGGL(fn, dim3(n), dim3(FUSED_NT), lds, t->stream, fg, (const f2 *)t->d_taps_row, (const f2 *)t->d_taps_col);
-        HIP_TRY(hipStreamSynchronize(t->stream));
+    if (!req.out_resp && t->sw.fused_diag && chain_len > 8) { // a chain's steady state: stamps of every frame, the median printed per phase
+        DeviceBuffer<float> d_st;
         std::vector<float> st(16 * (size_t)chain_len + 64);
-        HIP_TRY(hipMemcpy(st.data(), d_st, st.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipFree(d_st));
+        if (int rc = d_st.reserve(st.size(), nullptr)) return rc;
+        fg.g.resp = d_st.get();
+        fn = (t->fused_c && t->L == 65) ? (fused_fn_t)dog_fused_kernel<true, 1, 65> : (fused_fn_t)dog_fused_kernel<true, 1>;
+        if (int rc = raise_lds_limit((const void *)fn, lds)) return rc;
+        hipLaunchKernelGGL(fn, dim3(n), dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        HIP_TRY(hipMemcpy(st.data(), d_st.get(), st.size() * sizeof(float), hipMemcpyDeviceToHost));
         static const int order[7] = {0, 4, 1, 2, 5, 6, 3};
         static const char *names[7] = {"samples", "barrier", "staged", "row pass", "col+peak(w0)", "barrier", "finalize"};
         std::fprintf(stderr, "fused chain phases (median over frames 8.., 100 MHz ticks → us):");
@@ -1027,171 +957,116 @@ int launch_fused(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride,
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus < 1) cus = 256;
         t->fused_resident = per_cu * cus;
     }
-    hipLaunchKernelGGL(fn, dim3(std::min(n, t->fused_resident)), dim3(FUSED_NT), lds, t->stream, fg, (const f2 *)t->d_taps_row, (const f2 *)t->d_taps_col);
+    hipLaunchKernelGGL(fn, dim3(std::min(n, t->fused_resident)), dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
 }
 
-int launch_detect(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
-                  const int32_t *d_frame_index, const int32_t *d_guesses, int n, int32_t *d_out_ij,
-                  float *d_out_resp, int fh_override = 0, int fw_override = 0, int32_t *d_done_flag = nullptr,
-                  int32_t done_value = 0, bool *ticket_armed = nullptr, int dc_host = -1)
+// The kernels of g write their FP32 responses to the tracker's map, where exact mode's refinement reads its candidates
+// instead of recomputing them — unless g.n windows exceed PDOG_MAP_MB: g.resp then stays null.
+int reserve_response_map(pdog_tracker *t, LaunchGeo &g)
+{
+    const size_t count = (size_t)g.n * t->n1 * t->n2;
+    if (sizeof(float) * count > t->sw.map_cap) return PDOG_OK;
+    if (int rc = t->d_map.reserve(count, &t->stream)) return rc;
+    g.resp = t->d_map.get();
+    return PDOG_OK;
+}
+
+// Small batches: fewer than ≈1000 strip-waves cannot fill 256 CUs × 8 waves; the two-pass kernels (dozens of workgroups per
+// window, the intermediate in HBM) can.  `g` arrives as launch_detect filled it.
+int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticket_armed)
+{
+    const int n = req.n;
+    const int hr = t->sw.hpass16 ? HP_ROWS : 8; // 8 RT rows per workgroup (32 KB LDS → 4 workgroups per CU): +3 % on cfg5 vs 16; env = tuning switch
+    const int tp_slots = (t->n2 + hr - 1) / hr; // partial slots = hr-column blocks
+    g.nstrips = tp_slots;
+    g.nslots = tp_slots;
+    g.nthin = 0;
+    g.ex = exact_ctl(t, hr == 8 ? kFamTwoPass8 : kFamTwoPass16); // the two-pass kernels' own bound (blocked accumulation)
+    // exact mode: the column pass also writes its responses (4 B per pixel), so that a window that needs the
+    // refinement — every window, at the σ this path serves — reads its candidates off the map instead of recomputing them
+    if (t->exact && !g.resp)
+        if (int rc = reserve_response_map(t, g)) return rc;
+    const bool want_resp = g.resp != nullptr;
+    TwoPassGeo tg;
+    tg.TWin = t->n2 + t->L - 1;
+    tg.NA = t->n1 + t->L - 1;
+    tg.h1blocks_per_win = (tg.NA + HP_ROWS - 1) / HP_ROWS;
+    tg.hblocks_per_win = tp_slots;
+    tg.pitchA = twopass_pitch_q(t->n2, t->L, 16 * t->tp_ph1);
+    tg.pitchV = hr == 8 ? twopass_pitch_q(t->n1, t->L, 32 * t->tp_php) : twopass_pitch(t->n1, t->L, hr);
+    const size_t per_win = (size_t)t->n2 * tg.NA; // f2 elements of HBM scratch for the transposed intermediate; larger batches go in chunks
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, t->sw.scratch_cap / (per_win * sizeof(f2))));
+    if (int rc = t->d_V.reserve(per_win * chunk, &t->stream)) return rc;
+    if (int rc = t->d_dc.reserve(2 * (size_t)n, &t->stream)) return rc; // [cap] DC levels, then [cap] the windows' own V (exact mode)
+    tg.g = g;
+    tg.RT = t->d_V.get();
+    tg.dc = t->d_dc.get();
+    tg.vmax = nullptr;
+    tg.counter = nullptr;
+    tg.out_ij = req.out_ij;
+    tg.done_flag = nullptr;
+    tg.done_value = 0;
+    tg.win0 = 0;
+    const size_t l1 = (size_t)HP_ROWS * tg.pitchA * sizeof(float);
+    const size_t l2 = (size_t)hr * tg.pitchV * sizeof(f2);
+    const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
+    Finish fin;
+    fin.slot_w = hr;
+    fin.map = g.resp;
+    fin.out_ij = req.out_ij;
+    // A handful of windows (single-clip chains and functor calls with windows too large for the fused kernel,
+    // the auto-detect pass): launches are what such a batch costs, so the DC level is derived inside the row pass
+    // and the last column-pass workgroup of a window combines its partials — two launches instead of four.
+    // (exact mode: the partials are combined by dog_finish_kernel, which also refines and publishes the ticket —
+    // three launches; without it the last column-pass workgroup of a window combines them itself — two)
+    constexpr int kLowLatMax = 16; // measured crossover (257×257 and 271×481 windows): 2 launches win up to 16 windows, 4 launches beyond
+    if (n <= kLowLatMax && n <= chunk && hr == 8 && !t->sw.twopass_4l) {
+        if (!t->exact) {
+            if (!t->d_counter.get()) {
+                if (int rc = t->d_counter.reserve(kLowLatMax, nullptr)) return rc;
+                HIP_TRY(hipMemsetAsync(t->d_counter.get(), 0, sizeof(int) * kLowLatMax, t->stream));
+            }
+            tg.counter = t->d_counter.get();
+            tg.done_flag = req.done_flag;
+            tg.done_value = req.done_value;
+        }
+        if (ticket_armed) *ticket_armed = req.done_flag != nullptr;
+        hipLaunchKernelGGL(h1_kernel(t, true), dim3(n * tg.h1blocks_per_win), dim3(256), l1, t->stream, tg, tr);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(hpass8_kernel(t, want_resp, !t->exact), dim3(n * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, tc);
+        HIP_TRY(hipGetLastError());
+        if (!t->exact) return PDOG_OK;
+        fin.done_flag = req.done_flag;
+        fin.done_value = req.done_value;
+        return launch_finish(t, g, fin);
+    }
+    // exact mode: the row pass collects each window's own V = max |pixel − dc| (the error bound is proportional to it) and the
+    // finishing kernel flags with it; the two-pass kernels' own bound (blocked accumulation) replaces the one-chain bound
+    if (t->exact && !t->exact_all && hr == 8 && t->L >= TWOPASS_FLUSH_L) tg.vmax = t->d_dc.get() + t->d_dc.capacity() / 2; // (the blocked-accumulation instances collect it)
+    hipLaunchKernelGGL(dog_dc_kernel, dim3(n), dim3(64), 0, t->stream, g, t->d_dc.get(), tg.vmax);
+    HIP_TRY(hipGetLastError());
+    const tp_fn h1 = h1_kernel(t, false);
+    const tp_fn hp = hr == 8 ? hpass8_kernel(t, want_resp, false) : want_resp ? (tp_fn)dog_hpass_kernel<13, 16, true> : (tp_fn)dog_hpass_kernel<13, 16, false>;
+    for (int w0 = 0; w0 < n; w0 += chunk) {
+        const int nw = std::min(chunk, n - w0);
+        tg.win0 = w0;
+        hipLaunchKernelGGL(h1, dim3(nw * tg.h1blocks_per_win), dim3(256), l1, t->stream, tg, tr);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(hp, dim3(nw * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, tc);
+        HIP_TRY(hipGetLastError());
+    }
+    fin.vmax = tg.vmax;
+    return launch_finish(t, g, fin);
+}
+
+// The tracker's batch kernel: one wave (roll) or workgroup (ring) per strip of every window, the thin remainder columns beside
+// them, then the finishing kernel.  `g` arrives as launch_detect filled it.
+int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
 {
     const Variant &v = *t->var;
-    if (ticket_armed) *ticket_armed = false; // set where the kernels that run will publish done_value (single-window paths)
-    // frames of another size than the tracker's (the packed window tiles of pdog_detect_batch_host)
-    const int FH = fh_override ? fh_override : t->fh, FW = fw_override ? fw_override : t->fw;
-    LaunchGeo g;
-    g.fold_r = nullptr;
-    g.frames = d_frames;
-    g.frame_stride = frame_stride;
-    g.row_stride = row_stride;
-    g.frame_index = d_frame_index;
-    g.guesses = d_guesses;
-    g.resp = d_out_resp;
-    g.part_val = t->d_part_val;
-    g.part_idx = t->d_part_idx;
-    g.part_sec = t->d_part_sec;
-    g.part_mask = t->d_part_mask;
-    g.ex = exact_ctl(t, (v.roll ? kFamRoll : kFamRing));
-    g.fh = FH; g.fw = FW; g.r1 = t->r1; g.r2 = t->r2; g.n1 = t->n1; g.n2 = t->n2;
-    g.L = t->L; g.fill = t->fill; g.nstrips = t->nstrips; g.n = n;
-    g.RR = v.ring(t->L);
-    g.pitchA = v.pa(t->L);
-    g.nblocks = n * t->nstrips;
-    g.nslots = t->nstrips + t->nthin;
-    g.thin_x0 = t->thin_x0;
-    g.nthin = t->nthin;
-    // windows that fit in LDS, in batches too small to fill the GPU any other way: one workgroup per window, one launch
-    const int path = path_for_batch(t, n);
-    if (path == kPathFused) {
-        if (ticket_armed) *ticket_armed = d_done_flag != nullptr;
-        return launch_fused(t, d_frames, frame_stride, row_stride, d_frame_index, d_guesses, n, 1, d_out_ij, d_out_resp, FH, FW,
-                            d_done_flag, done_value, false, n == 1 ? dc_host : -1);
-    }
-    // one or a few windows too large for the fused kernel: the tiled kernel, one launch (dog_tiled.hpp)
-    if (path == kPathTiled) {
-        bool launched = false;
-        if (int rc = launch_tiled(t, d_frames, frame_stride, row_stride, d_frame_index, d_guesses, n, 1, d_out_ij, d_out_resp, FH, FW,
-                                  d_done_flag, done_value, false, &launched, n == 1 ? dc_host : -1)) return rc;
-        if (launched) {
-            if (ticket_armed) *ticket_armed = d_done_flag != nullptr;
-            return PDOG_OK;
-        }
-    }
-    // small batches: fewer than ≈1000 strip-waves cannot fill 256 CUs × 8 waves; the two-pass kernels can
-    if (path == kPathTwoPass || path == kPathTiled) {
-        const int hr = t->sw.hpass16 ? HP_ROWS : 8; // 8 RT rows per workgroup (32 KB LDS → 4 workgroups per CU): +3 % on cfg5 vs 16; env = tuning switch
-        const int tp_slots = (t->n2 + hr - 1) / hr; // partial slots = hr-column blocks
-        g.nstrips = tp_slots;
-        g.nslots = tp_slots;
-        g.nthin = 0;
-        g.ex = exact_ctl(t, hr == 8 ? kFamTwoPass8 : kFamTwoPass16); // the two-pass kernels' own bound (blocked accumulation)
-        // exact mode: the column pass also writes its responses (4 B per pixel), so that a window that needs the
-        // refinement — every window, at the σ this path serves — reads its candidates off the map instead of recomputing them
-        const float *map = d_out_resp;
-        if (t->exact && !map) {
-            const size_t need = sizeof(float) * (size_t)n * t->n1 * t->n2;
-            if (need <= t->sw.map_cap) {
-                if (t->map_bytes < need) {
-                    HIP_TRY(hipStreamSynchronize(t->stream));
-                    if (t->d_map) (void)hipFree(t->d_map);
-                    t->d_map = nullptr; t->map_bytes = 0;
-                    HIP_TRY(hipMalloc(&t->d_map, need));
-                    t->map_bytes = need;
-                }
-                map = t->d_map;
-                g.resp = t->d_map;
-            }
-        }
-        const bool want_resp = g.resp != nullptr;
-        TwoPassGeo tg;
-        tg.g = g;
-        tg.TWin = t->n2 + t->L - 1;
-        tg.NA = t->n1 + t->L - 1;
-        tg.h1blocks_per_win = (tg.NA + HP_ROWS - 1) / HP_ROWS;
-        tg.hblocks_per_win = tp_slots;
-        tg.pitchA = twopass_pitch_q(t->n2, t->L, 16 * t->tp_ph1);
-        tg.pitchV = hr == 8 ? twopass_pitch_q(t->n1, t->L, 32 * t->tp_php) : twopass_pitch(t->n1, t->L, hr);
-        const size_t per_win = (size_t)t->n2 * tg.NA * sizeof(f2);
-        const size_t cap = t->sw.scratch_cap; // HBM scratch for the transposed intermediate; larger batches go in chunks
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, cap / per_win));
-        if (t->v_bytes < per_win * chunk || t->dc_cap < n) {
-            HIP_TRY(hipStreamSynchronize(t->stream));
-            if (t->v_bytes < per_win * chunk) {
-                if (t->d_V) (void)hipFree(t->d_V);
-                t->d_V = nullptr; t->v_bytes = 0;
-                HIP_TRY(hipMalloc(&t->d_V, per_win * chunk));
-                t->v_bytes = per_win * chunk;
-            }
-            if (t->dc_cap < n) {
-                if (t->d_dc) (void)hipFree(t->d_dc);
-                t->d_dc = nullptr; t->dc_cap = 0;
-                HIP_TRY(hipMalloc(&t->d_dc, sizeof(int) * 2 * (size_t)n)); // [n] DC levels, then [n] the windows' own V (exact mode)
-                t->dc_cap = n;
-            }
-        }
-        tg.RT = t->d_V;
-        tg.dc = t->d_dc;
-        tg.vmax = nullptr;
-        tg.counter = nullptr;
-        tg.out_ij = d_out_ij;
-        tg.done_flag = nullptr;
-        tg.done_value = 0;
-        const size_t l1 = (size_t)HP_ROWS * tg.pitchA * sizeof(float);
-        const size_t l2 = (size_t)hr * tg.pitchV * sizeof(f2);
-        // A handful of windows (single-clip chains and functor calls with windows too large for the fused kernel,
-        // the auto-detect pass): launches are what such a batch costs, so the DC level is derived inside the row pass
-        // and the last column-pass workgroup of a window combines its partials — two launches instead of four.
-        constexpr int kLowLatMax = 16; // measured crossover (257×257 and 271×481 windows): 2 launches win up to 16 windows, 4 launches beyond
-        // (exact mode: the partials are combined by dog_finish_kernel, which also refines and publishes the ticket —
-        // three launches; without it the last column-pass workgroup of a window combines them itself — two)
-        const bool lowlat = n <= kLowLatMax && n <= chunk && hr == 8 && !t->sw.twopass_4l;
-        if (lowlat && t->exact) {
-            tg.win0 = 0;
-            if (ticket_armed) *ticket_armed = d_done_flag != nullptr;
-            hipLaunchKernelGGL(h1_kernel_for(t->tp_ph1, true, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L), dim3(n * tg.h1blocks_per_win), dim3(256), l1, t->stream, tg, (const f2 *)t->d_taps_row);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(hpass8_kernel_for(t->tp_php, want_resp, false, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L), dim3(n * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, (const f2 *)t->d_taps_col);
-            HIP_TRY(hipGetLastError());
-            return launch_finish(t, g, hr, 1 << 30, d_out_ij, d_done_flag, done_value, false, t->exact ? map : nullptr);
-        }
-        if (lowlat) {
-            if (!t->d_counter) {
-                HIP_TRY(hipMalloc(&t->d_counter, sizeof(int) * kLowLatMax));
-                HIP_TRY(hipMemsetAsync(t->d_counter, 0, sizeof(int) * kLowLatMax, t->stream));
-            }
-            tg.counter = t->d_counter;
-            tg.win0 = 0;
-            tg.done_flag = d_done_flag;
-            tg.done_value = done_value;
-            if (ticket_armed) *ticket_armed = d_done_flag != nullptr;
-            hipLaunchKernelGGL(h1_kernel_for(t->tp_ph1, true, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L), dim3(n * tg.h1blocks_per_win), dim3(256), l1, t->stream, tg, (const f2 *)t->d_taps_row);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(hpass8_kernel_for(t->tp_php, want_resp, true, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L), dim3(n * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, (const f2 *)t->d_taps_col);
-            HIP_TRY(hipGetLastError());
-            return PDOG_OK;
-        }
-        // exact mode: the row pass collects each window's own V = max |pixel − dc| (the error bound is proportional to it) and the
-        // finishing kernel flags with it; the two-pass kernels' own bound (blocked accumulation) replaces the one-chain bound
-        if (t->exact && !t->exact_all && hr == 8 && t->L >= TWOPASS_FLUSH_L) tg.vmax = t->d_dc + t->dc_cap; // (the blocked-accumulation instances collect it)
-        hipLaunchKernelGGL(dog_dc_kernel, dim3(n), dim3(64), 0, t->stream, g, t->d_dc, tg.vmax);
-        HIP_TRY(hipGetLastError());
-        for (int w0 = 0; w0 < n; w0 += chunk) {
-            const int nw = std::min(chunk, n - w0);
-            tg.win0 = w0;
-            hipLaunchKernelGGL(h1_kernel_for(t->tp_ph1, false, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L), dim3(nw * tg.h1blocks_per_win), dim3(256), l1, t->stream, tg, (const f2 *)t->d_taps_row);
-            HIP_TRY(hipGetLastError());
-            if (hr == 8) {
-                hipLaunchKernelGGL(hpass8_kernel_for(t->tp_php, want_resp, false, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L), dim3(nw * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, (const f2 *)t->d_taps_col);
-            } else if (want_resp)
-                hipLaunchKernelGGL((dog_hpass_kernel<13, 16, true>), dim3(nw * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, (const f2 *)t->d_taps_col);
-            else
-                hipLaunchKernelGGL((dog_hpass_kernel<13, 16, false>), dim3(nw * tg.hblocks_per_win), dim3(256), l2, t->stream, tg, (const f2 *)t->d_taps_col);
-            HIP_TRY(hipGetLastError());
-        }
-        return launch_finish(t, g, hr, 1 << 30, d_out_ij, nullptr, 0, false, t->exact ? map : nullptr, tg.vmax);
-    }
+    const int n = req.n;
     const int grid = round_up(g.nblocks, 8);
     // Exact mode: a batch whose predecessors flagged more than 8 % of their windows writes its responses (the kernels'
     // RESP instances: +15 % on the strips) and the finishing kernel reads the candidates off that map instead of recomputing
@@ -1199,10 +1074,9 @@ int launch_detect(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride
     // flagged count TOGETHER with the number of windows it came from, through host-coherent memory: nothing here waits for
     // the GPU, and the rate is right however many batches are in flight (round 2 compared the count's increase with ONE
     // batch's size: with three batches in flight 0.9 % looked like 2.7 % and one step in four paid for a map it did not need).
-    const float *map = d_out_resp;
     if (t->exact && !t->exact_all) {
-        const unsigned cur = (unsigned)__atomic_load_n(&t->h_pinned[6], __ATOMIC_ACQUIRE); // (the low 32 bits of a cumulative count: differences wrap correctly)
-        const unsigned curw = (unsigned)__atomic_load_n(&t->h_pinned[7], __ATOMIC_ACQUIRE);
+        const unsigned cur = (unsigned)__atomic_load_n(&t->h_pinned.get()[6], __ATOMIC_ACQUIRE); // (the low 32 bits of a cumulative count: differences wrap correctly)
+        const unsigned curw = (unsigned)__atomic_load_n(&t->h_pinned.get()[7], __ATOMIC_ACQUIRE);
         const long long delta = (long long)(unsigned)(cur - t->flag_last), dwin = (long long)(unsigned)(curw - t->win_last);
         if (dwin > 0) {
             t->flag_last = cur;
@@ -1211,18 +1085,8 @@ int launch_detect(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride
             else if (delta * 50 < dwin) { if (++t->flag_calm >= 8) t->roll_map = false; }
             else t->flag_calm = 0;
         }
-        const size_t need = sizeof(float) * (size_t)n * t->n1 * t->n2;
-        if (!map && t->roll_map && !t->sw.no_roll_map && need <= t->sw.map_cap) {
-            if (t->map_bytes < need) {
-                HIP_TRY(hipStreamSynchronize(t->stream));
-                if (t->d_map) (void)hipFree(t->d_map);
-                t->d_map = nullptr; t->map_bytes = 0;
-                HIP_TRY(hipMalloc(&t->d_map, need));
-                t->map_bytes = need;
-            }
-            map = t->d_map;
-            g.resp = t->d_map;
-        }
+        if (!g.resp && t->roll_map && !t->sw.no_roll_map)
+            if (int rc = reserve_response_map(t, g)) return rc;
     }
     const bool want_resp = g.resp != nullptr;
     // A single remainder column (widths 64·k + 1: 257, 513, …) can be FOLDED into the last strip: its row pass rides in that
@@ -1237,23 +1101,16 @@ int launch_detect(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride
     // the strip's own wave cost a wave per SIMD (12.9 KB per wave) and +5 %.  So: folded from 8 strips per window on.
     const bool fold = v.roll && roll_folds(v.LT) && t->nthin == 1 && !want_resp && !t->sw.no_fold && (t->nstrips >= 8 || t->sw.fold_always) &&
                       (size_t)FINISH_WPB * fold_wave_lds <= kMaxLds - 1024;
+    const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
     if (fold) {
-        const size_t need = sizeof(f2) * (size_t)n * NA;
-        if (t->fold_bytes < need) {
-            HIP_TRY(hipStreamSynchronize(t->stream));
-            if (t->d_fold_r) (void)hipFree(t->d_fold_r);
-            t->d_fold_r = nullptr; t->fold_bytes = 0;
-            HIP_TRY(hipMalloc(&t->d_fold_r, need));
-            t->fold_bytes = need;
-        }
-        g.fold_r = t->d_fold_r;
+        if (int rc = t->d_fold_r.reserve((size_t)n * NA, &t->stream)) return rc;
+        g.fold_r = t->d_fold_r.get();
     } else if (t->nthin) {
         // fork: the thin kernel only reads the frames and writes its own partial slots
         HIP_TRY(hipEventRecord(t->ev_fork, t->stream));
         HIP_TRY(hipStreamWaitEvent(t->aux_stream, t->ev_fork, 0));
         const size_t thin_lds = thin_lds_bytes(t->n1, t->L);
-        hipLaunchKernelGGL(want_resp ? v.thin_resp : v.thin, dim3(round_up(n * t->nthin, 8)), dim3(256), thin_lds, t->aux_stream, g,
-                           (const f2 *)t->d_taps_row, (const f2 *)t->d_taps_col);
+        hipLaunchKernelGGL(want_resp ? v.thin_resp : v.thin, dim3(round_up(n * t->nthin, 8)), dim3(256), thin_lds, t->aux_stream, g, tr, tc);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(t->ev_join, t->aux_stream));
     }
@@ -1271,82 +1128,82 @@ int launch_detect(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride
         PDOG_EPI_CLASSES(PDOG_EPI_PICK)
 #undef PDOG_EPI_PICK
     }
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(v.NT), lds_bytes, t->stream, g,
-                       (const f2 *)t->d_taps_row, (const f2 *)(v.roll ? t->d_taps_roll : t->d_taps_col));
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(v.NT), lds_bytes, t->stream, g, tr, v.roll ? (const f2 *)t->d_taps_roll.get() : tc);
     HIP_TRY(hipGetLastError());
     if (t->nthin && !fold) HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0)); // join before the strip combine
     // roll: 64-column strips over the first `covered` columns, the last one shifted left to stay inside; ring: tw() columns each
     const int covered = t->nthin ? t->thin_x0 : t->n2;
-    return launch_finish(t, g, v.tw(), v.roll ? std::max(0, covered - v.tw()) : (1 << 30), d_out_ij, nullptr, 0, v.roll, t->exact ? map : nullptr);
+    Finish fin;
+    fin.slot_w = v.tw();
+    if (v.roll) fin.slot_last = std::max(0, covered - v.tw());
+    fin.use_mask = v.roll;
+    fin.map = g.resp;
+    fin.out_ij = req.out_ij;
+    return launch_finish(t, g, fin);
+}
+
+// req.n independent windows on the kernel family path_for_batch names.  *ticket_armed: the kernels that run will publish
+// req.done_value at req.done_flag (the single-window paths).
+int launch_detect(pdog_tracker *t, const Request &req, bool *ticket_armed = nullptr)
+{
+    const Variant &v = *t->var;
+    if (ticket_armed) *ticket_armed = false;
+    const int path = path_for_batch(t, req.n);
+    // windows that fit in LDS, in batches too small to fill the GPU any other way: the fused kernel, one workgroup per window,
+    // one launch; one or a few windows too large for it: the tiled kernel, one launch (dog_tiled.hpp)
+    if (path == kPathFused || path == kPathTiled) {
+        Request one = req;
+        if (req.n != 1) one.dc_host = -1; // the host samples the DC level of a single window only
+        bool launched = true;
+        if (path == kPathFused) {
+            if (int rc = launch_fused(t, one)) return rc;
+        } else if (int rc = launch_tiled(t, one, &launched)) return rc;
+        if (launched) {
+            if (ticket_armed) *ticket_armed = req.done_flag != nullptr;
+            return PDOG_OK;
+        }
+    }
+    LaunchGeo g = base_geo(t, req);
+    use_partials(t, g);
+    g.ex = exact_ctl(t, (v.roll ? kFamRoll : kFamRing));
+    g.nstrips = t->nstrips;
+    g.RR = v.ring(t->L);
+    g.pitchA = v.pa(t->L);
+    g.nblocks = req.n * t->nstrips;
+    g.nslots = t->nstrips + t->nthin;
+    g.thin_x0 = t->thin_x0;
+    g.nthin = t->nthin;
+    if (path == kPathTwoPass || path == kPathTiled) return launch_twopass(t, req, g, ticket_armed); // (a tiled launch that was not taken falls through to here)
+    return launch_strips(t, req, g);
 }
 
 } // namespace
 
-extern "C" __attribute__((visibility("hidden"))) void pdog_set_error_text(const char *msg) { g_err = msg ? msg : ""; }
+namespace {
+
+// a device buffer of exactly the vector's size, filled from it (tracker construction: nothing is queued yet)
+template <typename T>
+int upload(DeviceBuffer<T> &d, const std::vector<T> &h)
+{
+    if (int rc = d.reserve(h.size(), nullptr)) return rc;
+    HIP_TRY(hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+    return PDOG_OK;
+}
+
+} // namespace
 
 extern "C" {
 
 int pdog_abi_version(void) { return PDOG_ABI_VERSION; }
-const char *pdog_last_error(void) { return g_err.c_str(); }
-
-double pdog_sigma(double target_width) { return sigma_of(target_width); }
-int pdog_default_window(double target_width) { return 4 * (int)std::ceil(sigma_of(target_width)) + 1; } // :64-68
-int pdog_kernel_len(double target_width) { return kernel_len_of_sigma(sigma_of(target_width)); }
-
-int pdog_gaussian_taps(double target_width, int which, double *out, int cap)
-{
-    if (!out || (which != 0 && which != 1) || !(target_width > 0)) return fail(PDOG_E_ARG, "pdog_gaussian_taps: bad argument");
-    const double s = sigma_of(target_width);
-    const int l = kernel_len_of_sigma(s);
-    if (cap < l) return fail(PDOG_E_ARG, "pdog_gaussian_taps: buffer too small");
-    gaussian_1d(which ? s * std::sqrt(2.0) : s, l, out);
-    return PDOG_OK;
-}
-
-int pdog_dense_kernel(double target_width, int darker_target, double *out, int cap)
-{
-    if (!out || !(target_width > 0)) return fail(PDOG_E_ARG, "pdog_dense_kernel: bad argument");
-    const double s = sigma_of(target_width);
-    const int l = kernel_len_of_sigma(s);
-    if ((long long)cap < (long long)l * l) return fail(PDOG_E_ARG, "pdog_dense_kernel: buffer too small");
-    std::vector<double> gp(l), gm(l);
-    gaussian_1d(s, l, gp.data());
-    gaussian_1d(s * std::sqrt(2.0), l, gm.data());
-    dense_dog_kernel(gp.data(), gm.data(), l, darker_target != 0, out);
-    return PDOG_OK;
-}
-
-int pdog_mode_u8(const uint8_t *img, int h, int w, int64_t row_stride, int *out_mode)
-{
-    if (!img || !out_mode || h <= 0 || w <= 0 || row_stride < w) return fail(PDOG_E_ARG, "pdog_mode_u8: bad argument");
-    // StatsBase.mode over the h×w view, column-major scan (row index fastest): per-value
-    // running counts; the winner is the value whose count FIRST exceeds the running maximum.
-    // Equivalent single pass per column block: counts are order dependent only through ties,
-    // so keep the literal scan order.
-    int64_t cnt[256];
-    std::memset(cnt, 0, sizeof cnt);
-    int64_t mc = 0;
-    int mv = img[0];
-    for (int j = 0; j < w; ++j) {
-        const uint8_t *p = img + j;
-        for (int i = 0; i < h; ++i) {
-            const int v = p[(int64_t)i * row_stride];
-            const int64_t c = ++cnt[v];
-            if (c > mc) { mc = c; mv = v; }
-        }
-    }
-    *out_mode = mv;
-    return PDOG_OK;
-}
-
 int pdog_mode_u8_device(int device, const uint8_t *d_img, int h, int w, int64_t row_stride, void *hip_stream, int *out_mode)
 {
     if (!d_img || !out_mode || h <= 0 || w <= 0 || row_stride < w || (long long)h * w >= 0xffffffffLL)
         return fail(PDOG_E_ARG, "pdog_mode_u8_device: bad argument");
     HIP_TRY(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)hip_stream;
-    unsigned *d_tab = nullptr;
-    HIP_TRY(hipMalloc(&d_tab, sizeof(unsigned) * 512));
+    DeviceBuffer<unsigned> table; // [256] counts, [256] first positions
+    if (int rc = table.reserve(512, nullptr)) return rc;
+    unsigned *d_tab = table.get();
     unsigned tab[512];
     hipError_t e = hipMemsetAsync(d_tab, 0, sizeof(unsigned) * 512, stream);
     if (e == hipSuccess) {
@@ -1356,7 +1213,6 @@ int pdog_mode_u8_device(int device, const uint8_t *d_img, int h, int w, int64_t 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(tab, d_tab, sizeof tab, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_tab);
     if (e != hipSuccess) return fail(PDOG_E_HIP, std::string("pdog_mode_u8_device: ") + hipGetErrorString(e));
     int best = 0;
     for (int v = 1; v < 256; ++v)
@@ -1382,7 +1238,8 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
         return fail(PDOG_E_NODEV, std::string("pdog_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
     HIP_TRY(hipSetDevice(device));
 
-    pdog_tracker *t = new pdog_tracker();
+    std::unique_ptr<pdog_tracker> owner(new pdog_tracker()); // a failure below destroys what was built so far
+    pdog_tracker *t = owner.get();
     t->device = device;
     t->sw = read_switches();
     t->fh = frame_h; t->fw = frame_w;
@@ -1393,11 +1250,10 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
     t->r1 = win_h / 2; t->r2 = win_w / 2;          // :44
     t->n1 = 2 * t->r1 + 1; t->n2 = 2 * t->r2 + 1;  // :56
     t->fill = fill;                                // :47
-    if ((long long)t->n1 * t->n2 > 0x3fffffffLL) { delete t; return fail(PDOG_E_ARG, "pdog_create: window too large"); }
+    if ((long long)t->n1 * t->n2 > 0x3fffffffLL) return fail(PDOG_E_ARG, "pdog_create: window too large");
 
     setup_refine_geometry(t);
-    int rc = choose_variant(t, -1);
-    if (rc) { delete t; return rc; }
+    if (int rc = choose_variant(t, -1)) return rc;
 
     // taps: Float64 on the host, one rounding to f32
     std::vector<double> gp(t->L), gm(t->L);
@@ -1410,25 +1266,14 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
         tr[k] = f2{(float)gp[k], (float)gm[k]};
         tc[k] = f2{(float)(s * gp[k]), (float)(-s * gm[k])};
     }
-#define CREATE_TRY(expr)                                                                          \
-    do {                                                                                          \
-        hipError_t e__ = (expr);                                                                  \
-        if (e__ != hipSuccess) {                                                                  \
-            std::string m = std::string(#expr) + ": " + hipGetErrorString(e__);                   \
-            pdog_destroy(t);                                                                      \
-            return fail(PDOG_E_HIP, m);                                                           \
-        }                                                                                         \
-    } while (0)
-    CREATE_TRY(hipStreamCreateWithFlags(&t->own_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&t->own_stream, hipStreamNonBlocking));
     t->stream = t->own_stream;
-    CREATE_TRY(hipStreamCreateWithFlags(&t->aux_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&t->ev_switch, hipEventDisableTiming));
-    CREATE_TRY(hipMalloc(&t->d_taps_row, sizeof(f2) * tr.size()));
-    CREATE_TRY(hipMalloc(&t->d_taps_col, sizeof(f2) * tc.size()));
-    CREATE_TRY(hipMemcpy(t->d_taps_row, tr.data(), sizeof(f2) * tr.size(), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(t->d_taps_col, tc.data(), sizeof(f2) * tc.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamCreateWithFlags(&t->aux_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&t->ev_switch, hipEventDisableTiming));
+    if (int rc = upload(t->d_taps_row, tr)) return rc;
+    if (int rc = upload(t->d_taps_col, tc)) return rc;
     {
         // roll_col_body's table: (Tc[t], Tc[t-1]) pairs per parity, T outside 0..l-1 is 0
         const int nqb = roll_col_blocks(t->L);
@@ -1444,98 +1289,52 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
                         const int tt = p + 2 * (ROLL_QB * qb + m);
                         tab[((qb * 2 + p) * 2 + c) * ROLL_QB + m] = f2{tapc(c, tt), tapc(c, tt - 1)};
                     }
-        CREATE_TRY(hipMalloc(&t->d_taps_roll, sizeof(f2) * tab.size()));
-        CREATE_TRY(hipMemcpy(t->d_taps_roll, tab.data(), sizeof(f2) * tab.size(), hipMemcpyHostToDevice));
+        if (int rc = upload(t->d_taps_roll, tab)) return rc;
     }
-    CREATE_TRY(hipMalloc(&t->d_small, sizeof(int32_t) * 4));
-    CREATE_TRY(hipHostMalloc(&t->h_pinned, sizeof(int32_t) * 8, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(t->h_pinned, 0, sizeof(int32_t) * 8);
-    CREATE_TRY(hipHostGetDevicePointer((void **)&t->d_mail_map, t->h_pinned, 0));
+    if (int rc = t->d_small.reserve(4, nullptr)) return rc;
+    if (int rc = t->h_pinned.reserve(8, nullptr, true)) return rc;
     {
         // exact mode (dog_exact.hpp): the reference's dense kernel in Float64, built exactly as :41-43 builds it
         // (K = dir·(g₊⊗g₊ − g₋⊗g₋), column-major), and the decision threshold T = 2δ, δ = u·(6l + 4) for |pixel − dc| ≤ 255
         std::vector<double> K((size_t)t->L * t->L);
         dense_dog_kernel(gp.data(), gm.data(), t->L, t->darker != 0, K.data());
-        CREATE_TRY(hipMalloc(&t->d_K64, sizeof(double) * K.size()));
-        CREATE_TRY(hipMemcpy(t->d_K64, K.data(), sizeof(double) * K.size(), hipMemcpyHostToDevice));
+        if (int rc = upload(t->d_K64, K)) return rc;
         t->h_gp = gp;
         t->h_gm = gm;
         {
             const ExactFactors ef = exact_factors(gp, gm);
             t->F_sym_int = ef.sym_int; t->F_sym_sep = ef.sym_sep; t->F_ring = ef.ring; t->F_rescan = ef.rescan;
         }
-        CREATE_TRY(hipMalloc(&t->d_ref_stat, sizeof(unsigned long long) * 16)); // [4..7] unused, [8..15]: phase cycles of the refinement (diagnostic build)
-        CREATE_TRY(hipMemset(t->d_ref_stat, 0, sizeof(unsigned long long) * 16));
+        if (int rc = t->d_ref_stat.reserve(16, nullptr, true)) return rc; // [4..7] unused, [8..15]: phase cycles of the refinement (diagnostic build)
         {
             std::vector<double> g2(2 * (size_t)t->L);
             std::copy(gp.begin(), gp.end(), g2.begin());
             std::copy(gm.begin(), gm.end(), g2.begin() + t->L);
-            CREATE_TRY(hipMalloc(&t->d_g64, sizeof(double) * g2.size()));
-            CREATE_TRY(hipMemcpy(t->d_g64, g2.data(), sizeof(double) * g2.size(), hipMemcpyHostToDevice));
+            if (int rc = upload(t->d_g64, g2)) return rc;
         }
         // separable Float64 vs the reference's dense Float64 (l² sequential roundings): both within δ64 of the exact value
         t->exact_T64 = 2.0 * std::ldexp(1.0, -53) * (2.1 * t->L * t->L + 8.0 * t->L + 64.0);
         {
             RefineParams rp;
-            rp.K64 = t->d_K64;
-            rp.g64 = t->d_g64;
+            rp.K64 = t->d_K64.get();
+            rp.g64 = t->d_g64.get();
             rp.dir = t->darker ? -1.0 : 1.0;
             rp.T64 = t->exact_T64;
-            CREATE_TRY(hipMalloc(&t->d_rp, sizeof rp));
-            CREATE_TRY(hipMemcpy(t->d_rp, &rp, sizeof rp, hipMemcpyHostToDevice));
+            if (int rc = upload(t->d_rp, std::vector<RefineParams>(1, rp))) return rc;
         }
         t->exact = refine_lds_bytes(t->n1, t->L, 1, 8) <= kMaxLds - 8192;
         if (!t->exact) // (success all the same: pdog_last_error carries the note, pdog_get_exact reports the state)
-            g_err = "pdog_create: window too tall for the refinement's LDS block (n1 + l beyond ~9000 rows): exact mode is OFF for this tracker";
-        if (raise_lds_limit((const void *)dog_finish_kernel, refine_lds_bytes(t->n1, t->L, t->ref_cbw, t->ref_rows))) { pdog_destroy(t); return PDOG_E_HIP; }
+            (void)fail(PDOG_OK, "pdog_create: window too tall for the refinement's LDS block (n1 + l beyond ~9000 rows): exact mode is OFF for this tracker");
+        if (raise_lds_limit((const void *)dog_finish_kernel, refine_lds_bytes(t->n1, t->L, t->ref_cbw, t->ref_rows))) return PDOG_E_HIP;
     }
-#undef CREATE_TRY
-    rc = ensure_capacity(t, 1);
-    if (rc) { pdog_destroy(t); return rc; }
-    *out = t;
+    if (int rc = ensure_capacity(t, 1)) return rc;
+    *out = owner.release();
     return PDOG_OK;
 }
 
 int pdog_destroy(pdog_tracker *t)
 {
-    if (!t) return PDOG_OK;
-    (void)hipSetDevice(t->device);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    if (t->d_taps_row) (void)hipFree(t->d_taps_row);
-    if (t->d_taps_col) (void)hipFree(t->d_taps_col);
-    if (t->d_taps_roll) (void)hipFree(t->d_taps_roll);
-    for (void *p : {(void *)t->d_part_val, (void *)t->d_part_idx, (void *)t->d_part_sec, (void *)t->d_part_mask, (void *)t->d_K64, (void *)t->d_g64, (void *)t->d_rp,
-                    (void *)t->d_ref_stat})
-        if (p) (void)hipFree(p);
-    if (t->d_fold_r) (void)hipFree(t->d_fold_r);
-    if (t->d_frame) (void)hipFree(t->d_frame);
-    if (t->d_small) (void)hipFree(t->d_small);
-    if (t->h_pinned) (void)hipHostFree(t->h_pinned);
-    if (t->d_resp) (void)hipFree(t->d_resp);
-    if (t->h_tile) (void)hipHostFree(t->h_tile);
-    if (t->d_V) (void)hipFree(t->d_V);
-    if (t->d_map) (void)hipFree(t->d_map);
-    if (t->d_dc) (void)hipFree(t->d_dc);
-    if (t->d_counter) (void)hipFree(t->d_counter);
-    if (t->d_chain_tmp) (void)hipFree(t->d_chain_tmp);
-    if (t->d_tiled_slots) (void)hipFree(t->d_tiled_slots);
-    if (t->d_tiled_ctl) (void)hipFree(t->d_tiled_ctl);
-    if (t->h2d_stream) { (void)hipStreamSynchronize(t->h2d_stream); (void)hipStreamDestroy(t->h2d_stream); }
-    for (int k = 0; k < pdog_tracker::kIngestSlots; ++k) {
-        if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
-        if (t->d_tiles[k]) (void)hipFree(t->d_tiles[k]);
-        if (t->ev_h2d[k]) (void)hipEventDestroy(t->ev_h2d[k]);
-        if (t->ev_used[k]) (void)hipEventDestroy(t->ev_used[k]);
-    }
-    if (t->d_ingest_guess) (void)hipFree(t->d_ingest_guess);
-    if (t->d_ingest_out) (void)hipFree(t->d_ingest_out);
-    if (t->h_ingest_out) (void)hipHostFree(t->h_ingest_out);
-    if (t->aux_stream) { (void)hipStreamSynchronize(t->aux_stream); (void)hipStreamDestroy(t->aux_stream); }
-    if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
-    if (t->ev_join) (void)hipEventDestroy(t->ev_join);
-    if (t->ev_switch) (void)hipEventDestroy(t->ev_switch);
-    if (t->own_stream) (void)hipStreamDestroy(t->own_stream);
-    delete t;
+    delete t; // ~pdog_tracker drains and destroys the streams; the buffers free themselves
     return PDOG_OK;
 }
 
@@ -1617,10 +1416,10 @@ static int drain_and_check(pdog_tracker *t, const char *who)
 {
     HIP_TRY(hipSetDevice(t->device)); // (group mode: the current device is whichever rank was touched last)
     HIP_TRY(hipStreamSynchronize(t->stream));
-    if (const int32_t raised = __atomic_load_n(&t->h_pinned[5], __ATOMIC_ACQUIRE)) { // raised by a kernel
-        __atomic_store_n(&t->h_pinned[5], 0, __ATOMIC_RELEASE);
+    if (const int32_t raised = __atomic_load_n(&t->h_pinned.get()[5], __ATOMIC_ACQUIRE)) { // raised by a kernel
+        __atomic_store_n(&t->h_pinned.get()[5], 0, __ATOMIC_RELEASE);
         if (raised == 2) { // a wait between resident workgroups gave up (wait_counter): the positions of that work are not valid
-            if (t->d_tiled_ctl) (void)hipMemset(t->d_tiled_ctl, 0, sizeof(int) * (4 * (size_t)t->tiled_ctl_cap + 1)); // counters, flags and the abort word
+            if (t->d_tiled_ctl.get()) (void)hipMemset(t->d_tiled_ctl.get(), 0, sizeof(int) * t->d_tiled_ctl.capacity()); // counters, flags and the abort word
             return fail(PDOG_E_HIP, std::string(who) + ": a kernel gave up waiting for its other workgroups (device-side watchdog); the results of the work just finished are not valid");
         }
         // a device-resident guess was out of range
@@ -1682,7 +1481,7 @@ int pdog_get_exact_detail(pdog_tracker *t, uint64_t out[4])
     if (!t || !out) return fail(PDOG_E_ARG, "pdog_get_exact_detail: null pointer");
     if (int rc = drain_and_check(t, "pdog_get_exact_detail")) return rc;
     unsigned long long v[16];
-    HIP_TRY(hipMemcpy(v, t->d_ref_stat, sizeof v, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(v, t->d_ref_stat.get(), sizeof v, hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out[i] = (uint64_t)v[i];
 #ifdef PDOG_ABLATIONS
     std::fprintf(stderr, "pdog refine phases (shader cycles, thread 0): setup %llu, tile %llu, row32 %llu, col32 %llu, row64 %llu, cand64 %llu, verdict %llu\n",
@@ -1702,7 +1501,7 @@ int pdog_get_exact(pdog_tracker *t, int *out_on, double *out_threshold, uint64_t
     if (out_refined) {
         if (int rc = drain_and_check(t, "pdog_get_exact")) return rc;
         unsigned long long v = 0;
-        HIP_TRY(hipMemcpy(&v, t->d_ref_stat, sizeof v, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&v, t->d_ref_stat.get(), sizeof v, hipMemcpyDeviceToHost));
         *out_refined = (uint64_t)v;
     }
     return PDOG_OK;
@@ -1719,12 +1518,12 @@ int pdog_detect_batch(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_st
     if (!d_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_detect_batch: more windows than frames and no frame index");
     if ((long long)n * t->nstrips > 0x7ffffff0LL) return fail(PDOG_E_ARG, "pdog_detect_batch: batch too large");
     HIP_TRY(hipSetDevice(t->device));
-    if (n > t->cap_windows) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        int rc = ensure_capacity(t, n);
-        if (rc) return rc;
-    }
-    return launch_detect(t, d_frames, frame_stride, row_stride, d_frame_index, d_guesses, n, d_out_ij, d_out_resp);
+    if (int rc = ensure_capacity(t, n)) return rc;
+    Request req;
+    req.frames = d_frames; req.frame_stride = frame_stride; req.row_stride = row_stride;
+    req.frame_index = d_frame_index; req.guesses = d_guesses; req.n = n;
+    req.out_ij = d_out_ij; req.out_resp = d_out_resp;
+    return launch_detect(t, req);
 }
 
 // ---- response and sub-pixel position at tracked points (dog_measure.hpp) ----
@@ -1757,7 +1556,7 @@ int pdog_measure(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride,
     g.fw = t->fw;
     g.fill = t->fill;
     g.L = t->L;
-    g.K64 = t->d_K64;
+    g.K64 = t->d_K64.get();
     g.out_resp5 = d_out_resp5;
     g.out_sub = d_out_sub;
     // positions per wave: as many tiles as leave four workgroups per CU their LDS.  Below MEASURE_MIN_PPW tiles per wave
@@ -1790,7 +1589,8 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
     if (guess[0] < -hw || guess[0] > t->fh + hw + 1 || guess[1] < -hw || guess[1] > t->fw + hw + 1)
         return fail(PDOG_E_RANGE, "pdog_detect_host: guess outside the padded frame (reference: BoundsError)");
     HIP_TRY(hipSetDevice(t->device));
-    if (h_resp && !t->d_resp) HIP_TRY(hipMalloc(&t->d_resp, sizeof(float) * (size_t)t->n1 * t->n2));
+    if (h_resp)
+        if (int rc = t->d_resp.reserve((size_t)t->n1 * t->n2, nullptr)) return rc;
     if (!t->sw.host_copy) {
         // Latency path: the tile is packed into pinned, device-mapped memory (fill materialised, as in
         // pdog_detect_batch_host) and the kernels read it in place over PCIe — no copy commands.  On the device the
@@ -1801,21 +1601,16 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         // queued next.  With a response copy, a pinned batch kernel that publishes no ticket, or a ticket that does
         // not show up in time (a failed launch), the stream is synchronised as usual.
         const int th = t->n1 + 2 * hw, tw = t->n2 + 2 * hw, pitch = round_up(tw, 16);
-        if (!t->h_tile) {
-            HIP_TRY(hipHostMalloc((void **)&t->h_tile, (size_t)th * pitch, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void **)&t->d_tile_map, t->h_tile, 0));
-        }
-        uint8_t *d_tile = t->d_tile_map;
-        int32_t *d_mail = t->d_mail_map;
+        if (int rc = t->h_tile.reserve((size_t)th * pitch, nullptr)) return rc;
+        int32_t *mail = t->h_pinned.get(), *d_mail = t->h_pinned.device();
         const bool trace = t->sw.host_trace; // diagnostic: where a call's wall time goes
         const auto t0 = std::chrono::steady_clock::now();
-        pack_tile(t, h_frame, row_stride, guess[0], guess[1], t->h_tile, pitch);
-        t->h_pinned[0] = t->r1 + hw + 1;   // the guess is the tile's centre
-        t->h_pinned[1] = t->r2 + hw + 1;
+        // cached stores: the functor's kernel reads this tile in place right away (non-temporal stores measured equal here)
+        pack_tile_geo(h_frame, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2, guess[0], guess[1], t->h_tile.get(), pitch, false);
+        mail[0] = t->r1 + hw + 1;   // the guess is the tile's centre
+        mail[1] = t->r2 + hw + 1;
         const auto t1 = std::chrono::steady_clock::now();
-        if (t->cap_windows < 1) {
-            if (int rc = ensure_capacity(t, 1)) return rc;
-        }
+        if (int rc = ensure_capacity(t, 1)) return rc;
         const int32_t ticket = t->ticket = t->ticket % 0x7fffffff + 1;   // 1 … 2^31 − 1, never the mailbox's initial 0
         bool armed = false;
         // the DC level from the tile just packed: the kernels' own 32×32 sample grid (dc_sample_sum / dc_from_sum), so the
@@ -1824,20 +1619,25 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         {
             int total = 0;
             for (int k = 0; k < 1024; ++k)
-                total += t->h_tile[(size_t)(int)(((long long)(k >> 5) * th) >> 5) * pitch + (size_t)(int)(((long long)(k & 31) * tw) >> 5)];
+                total += t->h_tile.get()[(size_t)(int)(((long long)(k >> 5) * th) >> 5) * pitch + (size_t)(int)(((long long)(k & 31) * tw) >> 5)];
             dc_host = (total + 512) >> 10;
             if (std::abs(dc_host - t->fill) <= 8) dc_host = t->fill;
         }
-        int rc = launch_detect(t, d_tile, (int64_t)th * pitch, pitch, nullptr, d_mail, 1, d_mail + 2, h_resp ? t->d_resp : nullptr, th, tw,
-                               d_mail + 4, ticket, &armed, t->sw.no_host_dc ? -1 : dc_host);
-        if (rc) return rc;
-        if (h_resp) HIP_TRY(hipMemcpyAsync(h_resp, t->d_resp, sizeof(float) * (size_t)t->n1 * t->n2, hipMemcpyDeviceToHost, t->stream));
+        Request req;
+        req.frames = t->h_tile.device(); req.frame_stride = (int64_t)th * pitch; req.row_stride = pitch;
+        req.guesses = d_mail; req.n = 1;
+        req.out_ij = d_mail + 2; req.out_resp = h_resp ? t->d_resp.get() : nullptr;
+        req.fh = th; req.fw = tw;
+        req.done_flag = d_mail + 4; req.done_value = ticket;
+        req.dc_host = t->sw.no_host_dc ? -1 : dc_host;
+        if (int rc = launch_detect(t, req, &armed)) return rc;
+        if (h_resp) HIP_TRY(hipMemcpyAsync(h_resp, t->d_resp.get(), sizeof(float) * (size_t)t->n1 * t->n2, hipMemcpyDeviceToHost, t->stream));
         const auto t2 = std::chrono::steady_clock::now();
         bool done = false;
         if (armed && !h_resp && !t->sw.host_sync) {
             const auto deadline = t2 + std::chrono::microseconds(500);
             for (int spin = 0;; ++spin) {
-                if (__atomic_load_n(&t->h_pinned[4], __ATOMIC_ACQUIRE) == ticket) { done = true; break; }
+                if (__atomic_load_n(&mail[4], __ATOMIC_ACQUIRE) == ticket) { done = true; break; }
                 if ((spin & 63) == 63 && std::chrono::steady_clock::now() > deadline) break;
                 __builtin_ia32_pause();
             }
@@ -1848,11 +1648,13 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
             auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
             std::fprintf(stderr, "pdog functor: pack %.1f us, launch %.1f us, sync %.1f us\n", us(t0, t1), us(t1, t2), us(t2, t3));
         }
-        out_ij[0] = std::min(std::max(guess[0] - t->r1 - hw + t->h_pinned[2] - 1, 1), t->fh);   // tile-local → frame, clamp (:60-61)
-        out_ij[1] = std::min(std::max(guess[1] - t->r2 - hw + t->h_pinned[3] - 1, 1), t->fw);
+        out_ij[0] = std::min(std::max(guess[0] - t->r1 - hw + mail[2] - 1, 1), t->fh);   // tile-local → frame, clamp (:60-61)
+        out_ij[1] = std::min(std::max(guess[1] - t->r2 - hw + mail[3] - 1, 1), t->fw);
         return PDOG_OK;
     }
-    if (!t->d_frame) HIP_TRY(hipMalloc(&t->d_frame, (size_t)t->fh * t->fw));
+    if (int rc = t->d_frame.reserve((size_t)t->fh * t->fw, nullptr)) return rc;
+    if (int rc = ensure_capacity(t, 1)) return rc;
+    int32_t *mail = t->h_pinned.get(), *d_small = t->d_small.get();
     {
         // Only the window's padded tile is read by the kernels (anything else they touch feeds masked
         // lanes), so only that rectangle of the frame crosses PCIe: 109×109 B instead of 2 MB for the
@@ -1860,80 +1662,26 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         const int r_lo = std::max(0, guess[0] - t->r1 - 1 - hw), r_hi = std::min(t->fh, guess[0] + t->r1 + hw);
         const int c_lo = std::max(0, guess[1] - t->r2 - 1 - hw), c_hi = std::min(t->fw, guess[1] + t->r2 + hw);
         if (r_hi > r_lo && c_hi > c_lo)
-            HIP_TRY(hipMemcpy2DAsync(t->d_frame + (size_t)r_lo * t->fw + c_lo, t->fw, h_frame + (size_t)r_lo * row_stride + c_lo,
+            HIP_TRY(hipMemcpy2DAsync(t->d_frame.get() + (size_t)r_lo * t->fw + c_lo, t->fw, h_frame + (size_t)r_lo * row_stride + c_lo,
                                      row_stride, (size_t)(c_hi - c_lo), (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, t->stream));
     }
-    t->h_pinned[0] = guess[0];
-    t->h_pinned[1] = guess[1];
-    HIP_TRY(hipMemcpyAsync(t->d_small, t->h_pinned, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
-    int rc = launch_detect(t, t->d_frame, (int64_t)t->fh * t->fw, t->fw, nullptr, t->d_small, 1, t->d_small + 2,
-                           h_resp ? t->d_resp : nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(t->h_pinned + 2, t->d_small + 2, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, t->stream));
-    if (h_resp) HIP_TRY(hipMemcpyAsync(h_resp, t->d_resp, sizeof(float) * (size_t)t->n1 * t->n2, hipMemcpyDeviceToHost, t->stream));
+    mail[0] = guess[0];
+    mail[1] = guess[1];
+    HIP_TRY(hipMemcpyAsync(d_small, mail, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
+    Request req;
+    req.frames = t->d_frame.get(); req.frame_stride = (int64_t)t->fh * t->fw; req.row_stride = t->fw;
+    req.guesses = d_small; req.n = 1;
+    req.out_ij = d_small + 2; req.out_resp = h_resp ? t->d_resp.get() : nullptr;
+    if (int rc = launch_detect(t, req)) return rc;
+    HIP_TRY(hipMemcpyAsync(mail + 2, d_small + 2, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, t->stream));
+    if (h_resp) HIP_TRY(hipMemcpyAsync(h_resp, t->d_resp.get(), sizeof(float) * (size_t)t->n1 * t->n2, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
-    out_ij[0] = t->h_pinned[2];
-    out_ij[1] = t->h_pinned[3];
+    out_ij[0] = mail[2];
+    out_ij[1] = mail[3];
     return PDOG_OK;
 }
 
 } // extern "C"
-
-namespace {
-
-// One window's padded tile, (n1+l-1) rows of `pitch` bytes: the frame rectangle the functor reads, with the
-// PaddedView fill (:48) materialised wherever the rectangle leaves the frame.  Tile row a, column b is the
-// padded frame at 1-based (g1 - r1 - l÷2 + a, g2 - r2 - l÷2 + b).
-void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int fill, int L, int r1, int r2, int g1, int g2,
-                   uint8_t *dst, int64_t pitch, bool stream = false)
-{
-    const int hw = L >> 1, th = 2 * r1 + 1 + 2 * hw, tw = 2 * r2 + 1 + 2 * hw;
-    const int i0 = g1 - r1 - hw - 1, j0 = g2 - r2 - hw - 1;        // 0-based frame coordinates of tile (0, 0)
-    const int jl = std::min(tw, std::max(0, -j0));                 // columns left of the frame
-    const int jr = std::max(jl, std::min(tw, fw - j0));            // first column right of the frame
-    // stream: the tile goes to pinned staging that only the DMA engine reads next — assemble each row in a small
-    // buffer and write it with non-temporal stores, so the copy engine finds the data in DRAM instead of having to
-    // snoop dirty lines out of this core's cache
-    const bool nt = stream && pitch % 16 == 0 && pitch <= 4096 && ((uintptr_t)dst & 15) == 0;
-    alignas(16) uint8_t rowbuf[4096];
-    for (int a = 0; a < th; ++a) {
-        uint8_t *out = dst + (size_t)a * pitch;
-        uint8_t *row = nt ? rowbuf : out;
-        const int gi = i0 + a;
-        if (gi < 0 || gi >= fh) {
-            std::memset(row, fill, (size_t)pitch);
-        } else {
-            if (jl) std::memset(row, fill, (size_t)jl);
-            if (jr > jl) std::memcpy(row + jl, frame + (size_t)gi * row_stride + (j0 + jl), (size_t)(jr - jl));
-            if (pitch > jr) std::memset(row + jr, fill, (size_t)(pitch - jr));
-        }
-        if (nt)
-            for (int64_t k = 0; k < pitch; k += 16)
-                _mm_stream_si128((__m128i *)(out + k), _mm_load_si128((const __m128i *)(rowbuf + k)));
-    }
-    if (nt) _mm_sfence(); // the non-temporal stores are globally visible before the caller publishes the tile
-}
-
-void pack_tile(const pdog_tracker *t, const uint8_t *frame, int64_t row_stride, int g1, int g2, uint8_t *dst, int pitch)
-{
-    // cached stores: the functor's kernel reads this tile in place right away (non-temporal stores measured equal here)
-    pack_tile_geo(frame, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2, g1, g2, dst, pitch, false);
-}
-
-} // namespace
-
-// The tile packer as a host-only entry (no GPU): what the host paths hand to the kernels, checkable on a CPU box.
-extern "C" int pdog_window_tile(const uint8_t *h_frame, int frame_h, int frame_w, int64_t row_stride, int fill, double target_width,
-                                int win_h, int win_w, const int32_t guess[2], uint8_t *h_out, int64_t out_pitch)
-{
-    if (!h_frame || !guess || !h_out) return fail(PDOG_E_ARG, "pdog_window_tile: null pointer");
-    if (frame_h <= 0 || frame_w <= 0 || row_stride < frame_w || fill < 0 || fill > 255 || win_h <= 0 || win_w <= 0 || !(target_width > 0))
-        return fail(PDOG_E_ARG, "pdog_window_tile: bad argument");
-    const int L = kernel_len_of_sigma(sigma_of(target_width)), r1 = win_h / 2, r2 = win_w / 2;
-    if (out_pitch < 2 * r2 + L) return fail(PDOG_E_ARG, "pdog_window_tile: out_pitch smaller than the tile width");
-    pack_tile_geo(h_frame, frame_h, frame_w, row_stride, fill, L, r1, r2, guess[0], guess[1], h_out, out_pitch);
-    return PDOG_OK;
-}
 
 namespace {
 
@@ -1985,44 +1733,22 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
             HIP_TRY(hipEventCreateWithFlags(&t->ev_used[k], hipEventDisableTiming));
         }
     }
-    if (t->ingest_slot_bytes < tile_bytes * chunk) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        HIP_TRY(hipStreamSynchronize(t->h2d_stream));
-        for (int k = 0; k < NS; ++k) {
-            if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
-            if (t->d_tiles[k]) (void)hipFree(t->d_tiles[k]);
-            t->h_stage[k] = nullptr; t->d_tiles[k] = nullptr;
-        }
-        t->ingest_slot_bytes = 0;
-        for (int k = 0; k < NS; ++k) {
-            HIP_TRY(hipHostMalloc((void **)&t->h_stage[k], tile_bytes * chunk, hipHostMallocDefault));
-            HIP_TRY(hipMalloc(&t->d_tiles[k], tile_bytes * chunk));
-        }
-        t->ingest_slot_bytes = tile_bytes * chunk;
+    const size_t slot_bytes = tile_bytes * chunk;
+    for (int k = 0; k < NS; ++k) {
+        if (std::min(t->h_stage[k].capacity(), t->d_tiles[k].capacity()) < slot_bytes)
+            HIP_TRY(hipStreamSynchronize(t->h2d_stream)); // copies queued into the old slot (reserve drains the tracker's stream)
+        if (int rc = t->h_stage[k].reserve(slot_bytes, &t->stream)) return rc;
+        if (int rc = t->d_tiles[k].reserve(slot_bytes, &t->stream)) return rc;
     }
-    if (t->ingest_guess_cap < chunk) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (t->d_ingest_guess) (void)hipFree(t->d_ingest_guess);
-        t->d_ingest_guess = nullptr; t->ingest_guess_cap = 0;
-        HIP_TRY(hipMalloc(&t->d_ingest_guess, sizeof(int32_t) * 2 * (size_t)chunk));
+    if (t->d_ingest_guess.capacity() < 2 * (size_t)chunk) { // every tile's guess is its centre
+        if (int rc = t->d_ingest_guess.reserve(2 * (size_t)chunk, &t->stream)) return rc;
         std::vector<int32_t> centre(2 * (size_t)chunk);
         for (int b = 0; b < chunk; ++b) { centre[2 * b] = t->r1 + hw + 1; centre[2 * b + 1] = t->r2 + hw + 1; }
-        HIP_TRY(hipMemcpy(t->d_ingest_guess, centre.data(), sizeof(int32_t) * centre.size(), hipMemcpyHostToDevice));
-        t->ingest_guess_cap = chunk;
+        HIP_TRY(hipMemcpy(t->d_ingest_guess.get(), centre.data(), sizeof(int32_t) * centre.size(), hipMemcpyHostToDevice));
     }
-    if (t->ingest_cap < n) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (t->d_ingest_out) (void)hipFree(t->d_ingest_out);
-        if (t->h_ingest_out) (void)hipHostFree(t->h_ingest_out);
-        t->d_ingest_out = nullptr; t->h_ingest_out = nullptr; t->ingest_cap = 0;
-        HIP_TRY(hipMalloc(&t->d_ingest_out, sizeof(int32_t) * 2 * (size_t)n));
-        HIP_TRY(hipHostMalloc((void **)&t->h_ingest_out, sizeof(int32_t) * 2 * (size_t)n, hipHostMallocDefault));
-        t->ingest_cap = n;
-    }
-    if (chunk > t->cap_windows) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (int rc = ensure_capacity(t, chunk)) return rc;
-    }
+    if (int rc = t->d_ingest_out.reserve(2 * (size_t)n, &t->stream)) return rc;
+    if (int rc = t->h_ingest_out.reserve(2 * (size_t)n, &t->stream)) return rc;
+    if (int rc = ensure_capacity(t, chunk)) return rc;
 
     const int nchunks = (n + chunk - 1) / chunk;
     std::atomic<int> next{0}, submitted{0}, failed{0};
@@ -2047,7 +1773,7 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
             const int f = h_frame_index ? h_frame_index[b] : b;
             const bool nt_stores = !t->sw.ingest_no_nt;
             pack_tile_geo(h_frames + (int64_t)f * frame_stride, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2,
-                          h_guesses[2 * b], h_guesses[2 * b + 1], t->h_stage[c % NS] + (size_t)(b - c * chunk) * tile_bytes, pitch, nt_stores);
+                          h_guesses[2 * b], h_guesses[2 * b + 1], t->h_stage[c % NS].get() + (size_t)(b - c * chunk) * tile_bytes, pitch, nt_stores);
             packed[c].fetch_add(1, std::memory_order_release);
         }
     };
@@ -2066,13 +1792,17 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
         if (failed.load()) { rc = fail(PDOG_E_HIP, "pdog_detect_batch_host: event wait failed in a packing thread"); break; }
         hipError_t e = hipSuccess;
         if (c >= NS) e = hipStreamWaitEvent(t->h2d_stream, t->ev_used[slot], 0); // kernels of chunk c - NS are done with the device slot
-        if (e == hipSuccess) e = hipMemcpyAsync(t->d_tiles[slot], t->h_stage[slot], tile_bytes * nw, hipMemcpyHostToDevice, t->h2d_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t->d_tiles[slot].get(), t->h_stage[slot].get(), tile_bytes * nw, hipMemcpyHostToDevice, t->h2d_stream);
         if (e == hipSuccess) e = hipEventRecord(t->ev_h2d[slot], t->h2d_stream);
         submitted.store(c + 1, std::memory_order_release);
         if (e == hipSuccess) e = hipStreamWaitEvent(t->stream, t->ev_h2d[slot], 0);
         if (e != hipSuccess) { rc = fail(PDOG_E_HIP, std::string("pdog_detect_batch_host: ") + hipGetErrorString(e)); break; }
-        rc = launch_detect(t, t->d_tiles[slot], (int64_t)tile_bytes, pitch, nullptr, t->d_ingest_guess, nw,
-                           t->d_ingest_out + 2 * (size_t)w0, nullptr, th, tw);
+        Request req;
+        req.frames = t->d_tiles[slot].get(); req.frame_stride = (int64_t)tile_bytes; req.row_stride = pitch;
+        req.guesses = t->d_ingest_guess.get(); req.n = nw;
+        req.out_ij = t->d_ingest_out.get() + 2 * (size_t)w0;
+        req.fh = th; req.fw = tw;
+        rc = launch_detect(t, req);
         if (rc == PDOG_OK && hipEventRecord(t->ev_used[slot], t->stream) != hipSuccess)
             rc = fail(PDOG_E_HIP, "pdog_detect_batch_host: hipEventRecord failed");
     }
@@ -2080,7 +1810,7 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
     for (auto &th_ : pool) th_.join();
     if (rc != PDOG_OK) { (void)hipStreamSynchronize(t->h2d_stream); (void)hipStreamSynchronize(t->stream); return rc; }
     const auto t_submitted = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(t->h_ingest_out, t->d_ingest_out, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_ingest_out.get(), t->d_ingest_out.get(), sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     if (trace) {
         const auto t_end = std::chrono::steady_clock::now();
@@ -2088,10 +1818,11 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
                      n, nchunks, chunk, nthreads, std::chrono::duration<double, std::milli>(t_submitted - t_begin).count(), wait_pack_ms,
                      std::chrono::duration<double, std::milli>(t_end - t_submitted).count());
     }
+    const int32_t *local = t->h_ingest_out.get();
     for (int b = 0; b < n; ++b) {
         // tile-local 1-based (p, q)  ->  padded-frame index  ->  clamp (:60-61)
-        const int i = h_guesses[2 * b] - t->r1 - hw + t->h_ingest_out[2 * b] - 1;
-        const int j = h_guesses[2 * b + 1] - t->r2 - hw + t->h_ingest_out[2 * b + 1] - 1;
+        const int i = h_guesses[2 * b] - t->r1 - hw + local[2 * b] - 1;
+        const int j = h_guesses[2 * b + 1] - t->r2 - hw + local[2 * b + 1] - 1;
         h_out_ij[2 * b] = std::min(std::max(i, 1), t->fh);
         h_out_ij[2 * b + 1] = std::min(std::max(j, 1), t->fw);
     }
@@ -2100,16 +1831,18 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
 
 namespace {
 
-// stream-ordered fallback: frame k's guess is frame k-1's (clamped) answer, read straight from the
-// output array — stream order is the dependency, no host round trip per frame
-int chain_by_launches(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
-                      int n_frames, const int32_t *d_start, int32_t *d_out_ij)
+// stream-ordered fallback for one clip of req.chain_len frames: frame k's guess is frame k-1's (clamped) answer, read
+// straight from the output array — stream order is the dependency, no host round trip per frame
+int chain_by_launches(pdog_tracker *t, const Request &clip)
 {
-    for (int k = 0; k < n_frames; ++k) {
-        const int32_t *guess = k ? d_out_ij + 2 * (k - 1) : d_start;
-        int rc = launch_detect(t, d_frames + (int64_t)k * frame_stride, frame_stride, row_stride, nullptr, guess, 1,
-                               d_out_ij + 2 * k, nullptr);
-        if (rc) return rc;
+    Request req = clip;
+    req.n = 1;
+    req.chain_len = 1;
+    for (int k = 0; k < clip.chain_len; ++k) {
+        if (int rc = launch_detect(t, req)) return rc;
+        req.frames += clip.frame_stride;
+        req.guesses = req.out_ij;
+        req.out_ij += 2;
     }
     return PDOG_OK;
 }
@@ -2133,31 +1866,33 @@ extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int6
     const bool fused_wins = t->fused_ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || (long long)n_clips * chain_strips < 1400);
     const bool persistent = v.roll && v.chain && chain_strips <= 8 && !fused_wins &&
                             (t->forced_variant || !t->small_twopass || (long long)n_clips * chain_strips >= 1000);
+    Request req; // n_clips clips of n_frames frames
+    req.frames = d_frames; req.frame_stride = frame_stride; req.row_stride = row_stride;
+    req.guesses = d_start_guesses; req.n = n_clips; req.chain_len = n_frames;
+    req.out_ij = d_out_ij;
     if (t->sw.tiled_force && n_clips == 1 && !t->forced_variant) {
         bool launched = false;
-        if (int rc = launch_tiled(t, d_frames, frame_stride, row_stride, nullptr, d_start_guesses, 1, n_frames, d_out_ij, nullptr, t->fh, t->fw,
-                                  nullptr, 0, false, &launched)) return rc;
+        if (int rc = launch_tiled(t, req, &launched)) return rc;
         if (launched) return PDOG_OK;
     }
     if (v.fused || (!persistent && !t->forced_variant && t->fused_ok)) // one launch: a workgroup per clip loops over its frames
-        return launch_fused(t, d_frames, frame_stride, row_stride, nullptr, d_start_guesses, n_clips, n_frames, d_out_ij, nullptr, t->fh, t->fw);
+        return launch_fused(t, req);
     if (persistent) {
+        Request frames_only; // (the chain kernel takes its guesses from cg.start)
+        frames_only.frames = d_frames; frames_only.frame_stride = frame_stride; frames_only.row_stride = row_stride;
+        frames_only.n = n_clips;
         ChainGeo cg;
+        cg.g = base_geo(t, frames_only);
         LaunchGeo &g = cg.g;
-        std::memset(&g, 0, sizeof g);
-        g.frames = d_frames;
-        g.frame_stride = frame_stride;
-        g.row_stride = row_stride;
-        g.fh = t->fh; g.fw = t->fw; g.r1 = t->r1; g.r2 = t->r2; g.n1 = t->n1; g.n2 = t->n2;
-        g.L = t->L; g.fill = t->fill; g.nstrips = chain_strips; g.n = n_clips;
+        g.nstrips = chain_strips;
         g.nblocks = n_clips * chain_strips;
         g.nslots = chain_strips;
         cg.start = d_start_guesses;
         cg.out_ij = d_out_ij;
         cg.n_frames = n_frames;
         g.ex = exact_ctl(t, kFamRoll);
-        cg.rp = t->exact ? t->d_rp : nullptr;
-        cg.taps_col_plain = t->d_taps_col;
+        cg.rp = t->exact ? t->d_rp.get() : nullptr;
+        cg.taps_col_plain = t->d_taps_col.get();
         // the strips' LDS doubles as the refinement's scratch: the widest block (with its pixel tile if possible) that
         // fits what the strips need anyway, so that exact mode does not cost the chain kernel occupancy
         const int NAc = t->n1 + t->L - 1;
@@ -2175,39 +1910,27 @@ extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int6
         const size_t lds = base;
         if (int rc = raise_lds_limit((const void *)v.chain, lds)) return rc;
         hipLaunchKernelGGL(v.chain, dim3(n_clips), dim3(64 * chain_strips), lds, t->stream, cg,
-                           (const f2 *)t->d_taps_row, (const f2 *)t->d_taps_roll);
+                           (const f2 *)t->d_taps_row.get(), (const f2 *)t->d_taps_roll.get());
         HIP_TRY(hipGetLastError());
         return PDOG_OK;
     }
-    if (t->cap_windows < n_clips) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        int rc = ensure_capacity(t, n_clips);
-        if (rc) return rc;
-    }
+    if (int rc = ensure_capacity(t, n_clips)) return rc;
     if (!t->forced_variant) { // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that allows)
         bool launched = false;
-        if (int rc = launch_tiled(t, d_frames, frame_stride, row_stride, nullptr, d_start_guesses, n_clips, n_frames, d_out_ij, nullptr, t->fh, t->fw,
-                                  nullptr, 0, false, &launched)) return rc;
+        if (int rc = launch_tiled(t, req, &launched)) return rc;
         if (launched) return PDOG_OK;
     }
-    if (n_clips == 1) {
-        // stream order is the dependency: frame k's guess is read straight from frame k-1's answer
-        return chain_by_launches(t, d_frames, frame_stride, row_stride, n_frames, d_start_guesses, d_out_ij);
-    }
-    if (t->chain_tmp_cap < n_clips) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (t->d_chain_tmp) (void)hipFree(t->d_chain_tmp);
-        t->d_chain_tmp = nullptr; t->chain_tmp_cap = 0;
-        HIP_TRY(hipMalloc(&t->d_chain_tmp, sizeof(int32_t) * 4 * (size_t)n_clips));
-        t->chain_tmp_cap = n_clips;
-    }
-    int32_t *cur = t->d_chain_tmp, *step = t->d_chain_tmp + 2 * (size_t)n_clips;
+    if (n_clips == 1) return chain_by_launches(t, req);
+    if (int rc = t->d_chain_tmp.reserve(4 * (size_t)n_clips, &t->stream)) return rc;
+    int32_t *cur = t->d_chain_tmp.get(), *step = cur + 2 * (size_t)n_clips;
     HIP_TRY(hipMemcpyAsync(cur, d_start_guesses, sizeof(int32_t) * 2 * (size_t)n_clips, hipMemcpyDeviceToDevice, t->stream));
+    Request batch; // step k: window c looks at clip c's frame k = frame (c*n_frames + k): a batch whose frame stride is one clip
+    batch.frame_stride = frame_stride * n_frames; batch.row_stride = row_stride;
+    batch.guesses = cur; batch.n = n_clips;
+    batch.out_ij = step;
     for (int k = 0; k < n_frames; ++k) {
-        // step k: window c looks at clip c's frame k = frame (c*n_frames + k): a batch whose frame stride is one clip
-        int rc = launch_detect(t, d_frames + (int64_t)k * frame_stride, frame_stride * n_frames, row_stride, nullptr, cur, n_clips,
-                               step, nullptr);
-        if (rc) return rc;
+        batch.frames = d_frames + (int64_t)k * frame_stride;
+        if (int rc = launch_detect(t, batch)) return rc;
         hipLaunchKernelGGL(dog_chain_step_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, t->stream, step, cur, d_out_ij,
                            n_clips, n_frames, k);
         HIP_TRY(hipGetLastError());
@@ -2221,8 +1944,8 @@ extern "C" int pdog_detect_chain(pdog_tracker *t, const uint8_t *d_frames, int64
     if (!t || !d_frames || !start_guess || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chain: null pointer");
     if (n_frames <= 0 || row_stride < t->fw) return fail(PDOG_E_ARG, "pdog_detect_chain: bad size/stride");
     HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(hipMemcpyAsync(t->d_small, start_guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
-    return pdog_detect_chains(t, d_frames, frame_stride, row_stride, n_frames, 1, t->d_small, d_out_ij);
+    HIP_TRY(hipMemcpyAsync(t->d_small.get(), start_guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
+    return pdog_detect_chains(t, d_frames, frame_stride, row_stride, n_frames, 1, t->d_small.get(), d_out_ij);
 }
 
 
@@ -2254,25 +1977,28 @@ extern "C" int pdog_detect_chain_progress(pdog_tracker *t, const uint8_t *d_fram
     if (hipHostGetDevicePointer((void **)&d_out, h_out_ij, 0) != hipSuccess || hipHostGetDevicePointer((void **)&d_prog, h_progress, 0) != hipSuccess)
         return fail(PDOG_E_ARG, "pdog_detect_chain_progress: h_out_ij / h_progress must come from pdog_alloc_host");
     __atomic_store_n(h_progress, 0, __ATOMIC_RELEASE);
-    HIP_TRY(hipMemcpyAsync(t->d_small, start_guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
-    if (t->var->fused || (!t->forced_variant && t->fused_ok)) // one launch: the kernel publishes k + 1 after every frame
-        return launch_fused(t, d_frames, frame_stride, row_stride, nullptr, t->d_small, 1, n_frames, d_out, nullptr, t->fh, t->fw,
-                            d_prog, 0, true);
-    if (t->cap_windows < 1) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (int rc = ensure_capacity(t, 1)) return rc;
-    }
+    HIP_TRY(hipMemcpyAsync(t->d_small.get(), start_guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
+    Request req; // one clip whose kernel publishes k + 1 after every frame
+    req.frames = d_frames; req.frame_stride = frame_stride; req.row_stride = row_stride;
+    req.guesses = t->d_small.get(); req.n = 1; req.chain_len = n_frames;
+    req.out_ij = d_out;
+    req.done_flag = d_prog; req.progress = true;
+    if (t->var->fused || (!t->forced_variant && t->fused_ok)) return launch_fused(t, req); // one launch
+    if (int rc = ensure_capacity(t, 1)) return rc;
     if (!t->forced_variant) { // the tiled kernel: the combining workgroup publishes k + 1 after every frame
         bool launched = false;
-        if (int rc = launch_tiled(t, d_frames, frame_stride, row_stride, nullptr, t->d_small, 1, n_frames, d_out, nullptr, t->fh, t->fw, d_prog, 0, true,
-                                  &launched)) return rc;
+        if (int rc = launch_tiled(t, req, &launched)) return rc;
         if (launched) return PDOG_OK;
     }
+    req.chain_len = 1;
+    req.progress = false;
     for (int k = 0; k < n_frames; ++k) { // stream-ordered launches per frame; frame k's guess is read from the (host-mapped) answer k − 1
         bool armed = false;
-        int rc = launch_detect(t, d_frames + (int64_t)k * frame_stride, frame_stride, row_stride, nullptr, k ? d_out + 2 * (k - 1) : t->d_small, 1,
-                               d_out + 2 * k, nullptr, 0, 0, d_prog, k + 1, &armed);
-        if (rc) return rc;
+        req.done_value = k + 1;
+        if (int rc = launch_detect(t, req, &armed)) return rc;
+        req.frames += frame_stride;
+        req.guesses = req.out_ij;
+        req.out_ij += 2;
         if (!armed) {
             hipLaunchKernelGGL(dog_publish_kernel, dim3(1), dim3(64), 0, t->stream, d_prog, k + 1);
             HIP_TRY(hipGetLastError());

@@ -1,0 +1,112 @@
+// pdog_host.hpp — what the host side of the C ABI shares between its translation units (pawsome_dog.hip,
+// pawsome_group.hip, pawsome_diag.hip, pdog_math.cpp): the thread's error text, the reference's Float64 host arithmetic
+// (pdog_math.cpp, plain C++) and, for the units that hipcc compiles, the HIP-error macro and the owning buffer type.
+//
+// WHERE KERNELS LIVE.  The kernels of the tracker (dog_*.hpp) are templates or `static __global__` functions in headers, and
+// raise_lds_limit is keyed on a kernel's address: a second translation unit that included one of those headers would get
+// private copies whose LDS limit was never raised.  So every include of a dog_*.hpp header of the tracker, every launch of
+// its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
+// this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip and pawsome_group.hip launch their own
+// kernels, dog_diag.hpp's and group_compact_kernel, which no other unit names.)
+#pragma once
+#include "../../include/pawsome_dog.h"
+#include <string>
+#include <utility>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace pdog {
+
+// ---- the thread's pdog_last_error() text ----
+int fail(int code, const std::string &msg); // sets the text, returns code
+
+// ---- Float64 host arithmetic, as the reference does it (pdog_math.cpp) ----
+double sigma_of(double tw);                                  // src/PawsomeTracker.jl:30
+int kernel_len_of_sigma(double s);                           // Kernel.DoG
+void gaussian_1d(double s, int l, double *g);                // KernelFactors.gaussian: exp(-x²/2σ²) / sum
+void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, double *K); // :41-43, column-major
+struct ExactFactors { double sym_int, sym_sep, ring, rescan; };
+ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm); // exact mode's FP32 error-bound factors
+void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int fill, int L, int r1, int r2, int g1, int g2,
+                   uint8_t *dst, int64_t pitch, bool stream = false);
+
+} // namespace pdog
+#pragma GCC visibility pop
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#include <cstring>
+
+#define HIP_TRY(expr)                                                                            \
+    do {                                                                                         \
+        hipError_t e__ = (expr);                                                                 \
+        if (e__ != hipSuccess)                                                                   \
+            return pdog::fail(PDOG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));   \
+    } while (0)
+
+#pragma GCC visibility push(hidden)
+namespace pdog {
+
+// A typed, move-only buffer that owns device memory (kPinned = false) or pinned host memory (kPinned = true: with its
+// hipHostMalloc flags and, where those map it, its device alias).  capacity() counts elements.  The destructor frees: the
+// owner drains its streams before its buffers go.
+template <typename T, bool kPinned>
+class Buffer {
+public:
+    explicit Buffer(unsigned host_flags = hipHostMallocDefault) : flags_(host_flags) {}
+    Buffer(Buffer &&o) noexcept : flags_(o.flags_) { swap(o); }
+    Buffer &operator=(Buffer &&o) noexcept { if (this != &o) { release(); swap(o); } return *this; }
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    ~Buffer() { release(); }
+
+    T *get() const { return p_; }
+    T *device() const { return kPinned ? dev_ : p_; } // the address kernels use (pinned: only where the flags map it)
+    size_t capacity() const { return cap_; }
+
+    // Room for `count` elements.  Nothing happens when the capacity suffices.  Otherwise: `*drain` (if given) is
+    // synchronised — kernels queued there may still use the old memory —, the old memory is freed, new memory allocated
+    // and, with zero_fill, cleared.  On failure the buffer is empty.  try_reserve returns HIP's own error.
+    hipError_t try_reserve(size_t count, const hipStream_t *drain, bool zero_fill = false)
+    {
+        if (count <= cap_) return hipSuccess;
+        hipError_t e = drain ? hipStreamSynchronize(*drain) : hipSuccess;
+        if (e != hipSuccess) return e;
+        release();
+        const size_t bytes = sizeof(T) * count;
+        if (kPinned) {
+            e = hipHostMalloc((void **)&p_, bytes, flags_);
+            if (e == hipSuccess && (flags_ & hipHostMallocMapped)) e = hipHostGetDevicePointer((void **)&dev_, p_, 0);
+            if (e == hipSuccess && zero_fill) std::memset(p_, 0, bytes);
+        } else {
+            e = hipMalloc((void **)&p_, bytes);
+            if (e == hipSuccess && zero_fill) e = hipMemset(p_, 0, bytes);
+        }
+        if (e != hipSuccess) release();
+        else cap_ = count;
+        return e;
+    }
+    int reserve(size_t count, const hipStream_t *drain, bool zero_fill = false)
+    {
+        const hipError_t e = try_reserve(count, drain, zero_fill);
+        return e == hipSuccess ? PDOG_OK : fail(PDOG_E_HIP, std::string("buffer of ") + std::to_string(sizeof(T) * count) + " bytes: " + hipGetErrorString(e));
+    }
+    void release()
+    {
+        if (p_) (void)(kPinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = dev_ = nullptr;
+        cap_ = 0;
+    }
+
+private:
+    void swap(Buffer &o) { std::swap(p_, o.p_); std::swap(dev_, o.dev_); std::swap(cap_, o.cap_); std::swap(flags_, o.flags_); }
+    T *p_ = nullptr, *dev_ = nullptr;
+    size_t cap_ = 0;
+    unsigned flags_;
+};
+template <typename T> using DeviceBuffer = Buffer<T, false>;
+template <typename T> using PinnedBuffer = Buffer<T, true>;
+
+} // namespace pdog
+#pragma GCC visibility pop
+#endif // __HIPCC__

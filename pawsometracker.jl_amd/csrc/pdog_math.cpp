@@ -1,0 +1,188 @@
+// pdog_math.cpp — the part of the C ABI (include/pawsome_dog.h) that needs no GPU: the thread's error text, the
+// reference's Float64 kernel arithmetic (src/PawsomeTracker.jl:30, :41-43), mode(_img) (:47) and the window
+// tile packer.  Plain C++: no HIP, no kernel header (pdog_host.hpp says why), so tools/asan_host.sh sanitises it alone.
+#include "pdog_host.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <emmintrin.h>
+
+namespace pdog {
+
+namespace {
+thread_local std::string g_err;
+}
+
+int fail(int code, const std::string &msg)
+{
+    g_err = msg;
+    return code;
+}
+
+double sigma_of(double tw) { return tw / (2.0 * std::sqrt(2.0 * std::log(2.0))); } // :30
+int kernel_len_of_sigma(double s) { return 4 * (int)std::ceil(s * std::sqrt(2.0)) + 1; } // Kernel.DoG
+void gaussian_1d(double s, int l, double *g)
+{ // KernelFactors.gaussian: exp(-x²/2σ²) / sum
+#pragma clang fp contract(off)
+    const int w = l >> 1;
+    for (int x = -w; x <= w; ++x) g[x + w] = std::exp(-((double)x * (double)x) / (2.0 * s * s));
+    double sum = 0.0;
+    for (int i = 0; i < l; ++i) sum += g[i];
+    for (int i = 0; i < l; ++i) g[i] /= sum;
+}
+
+// The reference's dense kernel, K = dir·(g₊⊗g₊ − g₋⊗g₋) (src/PawsomeTracker.jl:41-43), column-major, every product and
+// the difference rounded separately as Julia evaluates them: a compiler may contract a·b − c·d into an FMA, which
+// changes last bits — and last bits are exactly what decides the ties exact mode exists for.
+void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, double *K)
+{
+#pragma clang fp contract(off)
+    const double dir = darker ? -1.0 : 1.0;
+    for (int j = 0; j < l; ++j)
+        for (int i = 0; i < l; ++i) {
+            const double a = gp[i] * gp[j];
+            const double b = gm[i] * gm[j];
+            K[i + (size_t)l * j] = dir * (a - b);
+        }
+}
+
+// ---- exact mode's FP32 error bounds, per kernel family (dog_exact.hpp: the guarantee) ----
+// An FMA chain ŝ_i = fl(ŝ_{i−1} + a_i·b̂_i) satisfies |ŝ_n − s_n| ≤ u·(1 + u)·Σ_i |ŝ_i| (each step rounds its own result once), and
+// |ŝ_i| ≤ V·W_i·(1 + nu) where W_i = Σ_{j ≤ i} |b_j|·max|a_j|/V is the cumulative tap weight IN THE ORDER THE KERNEL ADDS THEM.  The
+// Gaussians sum to 1, so Σ_i W_i is far below the chain length n that the order-blind bound n·u·V charges: the kernels add the
+// smallest taps (the kernel's edges) first.  The factors below are Σ_i W_i evaluated numerically over the tracker's own Float64
+// taps for each family's operation order (+1 per rounded tap table, +2 for a final channel addition); δ = u·(V/255)·F·1.02:
+//   row pass, symmetric pairs from the edge inwards, centre last (roll, thin, fused, tiled, two-pass):  W_i = Σ_{j ≤ i} 2g[j]
+//   row pass, plain chain over the l taps (ring kernels; the refinement's FP32 rescan):               W_i = Σ_{j ≤ i} g[j]
+//   column pass, one f32 per output taking (+, −) terms alternately (roll, thin, folded column, rescan): both cumulative weights per step
+//   column pass, the two Gaussians in separate chains, added at the end (ring, fused, tiled, two-pass)
+//   two-pass: every chain is one trip of the register ring long, the chains' sums are added up (dog_twopass.hpp) — per chain its own
+//   cumulative weights from zero, plus the running total's weight per addition (twopass_factor, pawsome_dog.hip)
+// l = 65: 157 (roll) / 94 (fused, tiled) / 138 (ring) against the order-blind 6l + 4 = 394;  l = 293 two-pass: 72 against 1762.
+ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm)
+{
+    const int l = (int)gp.size(), H = l / 2;
+    auto row_sym = [&](const std::vector<double> &g) { double W = 0, F = 0; for (int k = 0; k <= H; ++k) { W += (k < H ? 2.0 : 1.0) * g[k]; F += W; } return F + 1.0; };
+    auto row_plain = [&](const std::vector<double> &g) { double W = 0, F = 0; for (int k = 0; k < l; ++k) { W += g[k]; F += W; } return F + 1.0; };
+    double Gp = 0, Gm = 0, c_sep = 4.0, c_int = 2.0;
+    for (int t = 0; t < l; ++t) {
+        Gp += gp[t];
+        c_int += Gp + Gm; // after the + term of tap t
+        Gm += gm[t];
+        c_int += Gp + Gm; // after the − term
+        c_sep += Gp + Gm;
+    }
+    ExactFactors f;
+    f.sym_int = row_sym(gp) + row_sym(gm) + c_int;
+    f.sym_sep = row_sym(gp) + row_sym(gm) + c_sep;
+    f.ring = row_plain(gp) + row_plain(gm) + c_sep;
+    f.rescan = row_plain(gp) + row_plain(gm) + c_int;
+    return f;
+}
+
+// One window's padded tile, (n1+l-1) rows of `pitch` bytes: the frame rectangle the functor reads, with the
+// PaddedView fill (:48) materialised wherever the rectangle leaves the frame.  Tile row a, column b is the
+// padded frame at 1-based (g1 - r1 - l÷2 + a, g2 - r2 - l÷2 + b).
+void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int fill, int L, int r1, int r2, int g1, int g2,
+                   uint8_t *dst, int64_t pitch, bool stream)
+{
+    const int hw = L >> 1, th = 2 * r1 + 1 + 2 * hw, tw = 2 * r2 + 1 + 2 * hw;
+    const int i0 = g1 - r1 - hw - 1, j0 = g2 - r2 - hw - 1;        // 0-based frame coordinates of tile (0, 0)
+    const int jl = std::min(tw, std::max(0, -j0));                 // columns left of the frame
+    const int jr = std::max(jl, std::min(tw, fw - j0));            // first column right of the frame
+    // stream: the tile goes to pinned staging that only the DMA engine reads next — assemble each row in a small
+    // buffer and write it with non-temporal stores, so the copy engine finds the data in DRAM instead of having to
+    // snoop dirty lines out of this core's cache
+    const bool nt = stream && pitch % 16 == 0 && pitch <= 4096 && ((uintptr_t)dst & 15) == 0;
+    alignas(16) uint8_t rowbuf[4096];
+    for (int a = 0; a < th; ++a) {
+        uint8_t *out = dst + (size_t)a * pitch;
+        uint8_t *row = nt ? rowbuf : out;
+        const int gi = i0 + a;
+        if (gi < 0 || gi >= fh) {
+            std::memset(row, fill, (size_t)pitch);
+        } else {
+            if (jl) std::memset(row, fill, (size_t)jl);
+            if (jr > jl) std::memcpy(row + jl, frame + (size_t)gi * row_stride + (j0 + jl), (size_t)(jr - jl));
+            if (pitch > jr) std::memset(row + jr, fill, (size_t)(pitch - jr));
+        }
+        if (nt)
+            for (int64_t k = 0; k < pitch; k += 16)
+                _mm_stream_si128((__m128i *)(out + k), _mm_load_si128((const __m128i *)(rowbuf + k)));
+    }
+    if (nt) _mm_sfence(); // the non-temporal stores are globally visible before the caller publishes the tile
+}
+
+} // namespace pdog
+
+using namespace pdog;
+
+extern "C" {
+
+const char *pdog_last_error(void) { return g_err.c_str(); }
+
+double pdog_sigma(double target_width) { return sigma_of(target_width); }
+int pdog_default_window(double target_width) { return 4 * (int)std::ceil(sigma_of(target_width)) + 1; } // :64-68
+int pdog_kernel_len(double target_width) { return kernel_len_of_sigma(sigma_of(target_width)); }
+
+int pdog_gaussian_taps(double target_width, int which, double *out, int cap)
+{
+    if (!out || (which != 0 && which != 1) || !(target_width > 0)) return fail(PDOG_E_ARG, "pdog_gaussian_taps: bad argument");
+    const double s = sigma_of(target_width);
+    const int l = kernel_len_of_sigma(s);
+    if (cap < l) return fail(PDOG_E_ARG, "pdog_gaussian_taps: buffer too small");
+    gaussian_1d(which ? s * std::sqrt(2.0) : s, l, out);
+    return PDOG_OK;
+}
+
+int pdog_dense_kernel(double target_width, int darker_target, double *out, int cap)
+{
+    if (!out || !(target_width > 0)) return fail(PDOG_E_ARG, "pdog_dense_kernel: bad argument");
+    const double s = sigma_of(target_width);
+    const int l = kernel_len_of_sigma(s);
+    if ((long long)cap < (long long)l * l) return fail(PDOG_E_ARG, "pdog_dense_kernel: buffer too small");
+    std::vector<double> gp(l), gm(l);
+    gaussian_1d(s, l, gp.data());
+    gaussian_1d(s * std::sqrt(2.0), l, gm.data());
+    dense_dog_kernel(gp.data(), gm.data(), l, darker_target != 0, out);
+    return PDOG_OK;
+}
+
+int pdog_mode_u8(const uint8_t *img, int h, int w, int64_t row_stride, int *out_mode)
+{
+    if (!img || !out_mode || h <= 0 || w <= 0 || row_stride < w) return fail(PDOG_E_ARG, "pdog_mode_u8: bad argument");
+    // StatsBase.mode over the h×w view, column-major scan (row index fastest): per-value
+    // running counts; the winner is the value whose count FIRST exceeds the running maximum.
+    // Equivalent single pass per column block: counts are order dependent only through ties,
+    // so keep the literal scan order.
+    int64_t cnt[256];
+    std::memset(cnt, 0, sizeof cnt);
+    int64_t mc = 0;
+    int mv = img[0];
+    for (int j = 0; j < w; ++j) {
+        const uint8_t *p = img + j;
+        for (int i = 0; i < h; ++i) {
+            const int v = p[(int64_t)i * row_stride];
+            const int64_t c = ++cnt[v];
+            if (c > mc) { mc = c; mv = v; }
+        }
+    }
+    *out_mode = mv;
+    return PDOG_OK;
+}
+
+// The tile packer as a host-only entry (no GPU): what the host paths hand to the kernels, checkable on a CPU box.
+int pdog_window_tile(const uint8_t *h_frame, int frame_h, int frame_w, int64_t row_stride, int fill, double target_width,
+                     int win_h, int win_w, const int32_t guess[2], uint8_t *h_out, int64_t out_pitch)
+{
+    if (!h_frame || !guess || !h_out) return fail(PDOG_E_ARG, "pdog_window_tile: null pointer");
+    if (frame_h <= 0 || frame_w <= 0 || row_stride < frame_w || fill < 0 || fill > 255 || win_h <= 0 || win_w <= 0 || !(target_width > 0))
+        return fail(PDOG_E_ARG, "pdog_window_tile: bad argument");
+    const int L = kernel_len_of_sigma(sigma_of(target_width)), r1 = win_h / 2, r2 = win_w / 2;
+    if (out_pitch < 2 * r2 + L) return fail(PDOG_E_ARG, "pdog_window_tile: out_pitch smaller than the tile width");
+    pack_tile_geo(h_frame, frame_h, frame_w, row_stride, fill, L, r1, r2, guess[0], guess[1], h_out, out_pitch);
+    return PDOG_OK;
+}
+
+} // extern "C"
