@@ -240,6 +240,57 @@ int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_s
                        int64_t row_stride, int n_frames, int n_clips,
                        const int32_t *d_start_guesses, int32_t *d_out_ij);
 
+/* ---- many clips, each tracked as the reference tracks it: own fill, own start ----
+ * The reference builds one `Tracker` per video (src/PawsomeTracker.jl:39-52), so every clip's PaddedView is filled with the
+ * mode of ITS first frame (:47-48), and with the default start_location = missing the first position comes from a
+ * sz .÷ 4 window on the first frame (:99-107), is stored as given (:161) and the loop continues from the second frame
+ * (:161-167).  The chains entry point above has one fill for all clips and always recomputes frame 0.  A pdog_clips handle
+ * adds both, through the tracker's public entry points only (no kernel of the tracker differs): the clips are grouped by
+ * fill and WALKED PER FRAME AND PER FILL GROUP — for frame k, one detect-batch launch per group under that group's
+ * fill — so it costs launches where the persistent chain costs one.  Single-caller like the tracker it borrows. */
+typedef struct pdog_clips pdog_clips; /* opaque; borrows a tracker, which must outlive it */
+int pdog_clips_create(pdog_tracker *t, pdog_clips **out);
+/* Drains the tracker's stream first (queued work may still use the handle's workspace), then frees the handle. */
+int pdog_clips_destroy(pdog_clips *c);
+/* mode(_img) (:47) of n frames of the tracker's size that live on the device: entry b looks at frame d_frame_index[b]
+ * (device; NULL -> frame b), frame k at d_frames + k*frame_stride.  Tie rule as for the single-frame device entry point
+ * above.  d_out_mode: int32[n] in DEVICE memory; an entry whose index lies outside [0, n_frames) gets -1.  Asynchronous on
+ * the tracker's stream, no host read-back, no allocation once the workspace has grown.  Many frames run one workgroup per
+ * frame, few large ones several workgroups per frame and a second, stream-ordered launch that resolves them.  PDOG_E_ARG
+ * for a null pointer, n < 0, n_frames <= 0, row_stride < frame_w, a negative frame_stride, n > n_frames with no index,
+ * a frame of 2^32 - 1 pixels or more, or more entries than one launch takes (2^24 and beyond); n == 0 does nothing. */
+int pdog_clips_modes(pdog_clips *c, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
+                     int n_frames, const int32_t *d_frame_index, int n, int32_t *d_out_mode);
+/* The grouping plan of the track entry point below as host arithmetic (no handle, no GPU).  h_fill: a fill per clip, or
+ * NULL = one group under the tracker's fill, reported as -1; h_len: frames per clip in 0 … n_frames, or NULL = n_frames
+ * each.  A clip takes part when len > first.  out_order (room for n_clips): the participants sorted by (fill ascending,
+ * len descending, clip ascending); group g is out_order[out_group_start[g] … out_group_start[g+1]) under out_group_fill[g]
+ * (room for min(n_clips, 256) fills and one more start), so the clips of a group still active at frame k are a prefix of
+ * it.  PDOG_E_ARG (outputs untouched) for a null output, a non-positive size, first other than 0 or 1, a fill outside
+ * 0 … 255 or a length outside 0 … n_frames. */
+int pdog_clips_plan(int n_clips, int n_frames, int first, const int32_t *h_fill, const int32_t *h_len,
+                    int32_t *out_order, int32_t *out_group_fill, int32_t *out_group_start, int *out_n_groups);
+/* Layout as for the chains entry point above (clip c's frame k is frame c*n_frames + k; d_start n_clips x 2 and d_out_ij
+ * n_clips x n_frames x 2 on the device); h_fill and h_len are HOST arrays as for the plan, consumed before the call
+ * returns.  Per clip c with f = h_fill[c], len = h_len[c]:
+ *   first = 0: out[c][0] = functor_f(frame 0, start[c]); out[c][k] = functor_f(frame k, out[c][k-1]) for k < len   (:163-167)
+ *   first = 1: out[c][0] = start[c] as given when len >= 1 (:104, :161); then the same loop for 1 <= k < len
+ * Rows k >= len of out[c] are not written.  Everything runs on the tracker's stream without a host wait (the call may wait
+ * for the PREVIOUS call's plan upload, and drains the stream when workspace grows); the tracker's fill on return is what it
+ * was before.  One fill, full lengths and first = 0 is the chains entry point under that fill and nothing else.
+ * PDOG_E_ARG, with nothing launched, for a null pointer, a bad size or stride, n_clips * n_frames beyond int32, first other
+ * than 0 or 1, a fill outside 0 … 255 or a length outside 0 … n_frames; PDOG_E_RANGE arrives through pdog_sync, as for every
+ * device-resident guess. */
+int pdog_clips_track(pdog_clips *c, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
+                     int n_frames, int n_clips, const int32_t *h_fill, const int32_t *h_len, int first,
+                     const int32_t *d_start, int32_t *d_out_ij);
+/* For tests and measurements.  Counters since the handle was created: out[0] mode calls that ran one workgroup per frame,
+ * out[1] mode calls that ran several, out[2] per-frame batches the track entry point launched, out[3] track calls that
+ * took the chains fast path.  Tuning key: "mode_form" (0 automatic, 1 always one workgroup per frame, 2 always several);
+ * unknown key: PDOG_E_ARG. */
+int pdog_clips_get_counters(const pdog_clips *c, uint64_t out[4]);
+int pdog_clips_set_tuning(pdog_clips *c, const char *key, int value);
+
 /* A chain whose positions can be consumed WHILE it runs — what the reference's diagnostic overlay
  * (src/diagnose.jl:30-38, called per frame inside the loop :163-169) needs from a device-side chain.
  * h_out_ij (n_frames x 2 int32) and h_progress (one int32) must come from pdog_alloc_host (pinned,

@@ -24,6 +24,8 @@ SYMBOLS = (
     "pdog_set_exact", "pdog_get_exact", "pdog_get_exact_detail", "pdog_dense_kernel", "pdog_set_tuning",
     "pdog_diag_create", "pdog_diag_destroy", "pdog_diag_point", "pdog_diag_render",
     "pdog_subpixel", "pdog_measure",
+    "pdog_clips_create", "pdog_clips_destroy", "pdog_clips_modes", "pdog_clips_plan", "pdog_clips_track",
+    "pdog_clips_get_counters", "pdog_clips_set_tuning",
 )
 
 
@@ -143,6 +145,14 @@ def lib():
     if hasattr(L, "pdog_measure"):
         L.pdog_subpixel.restype = i; L.pdog_subpixel.argtypes = [p, p, p]
         L.pdog_measure.restype = i; L.pdog_measure.argtypes = [p, p, i64, i64, i, p, p, i, p, p]
+    if hasattr(L, "pdog_clips_create"):  # (absent from older builds loaded through PAWSOME_DOG_LIB for an A/B)
+        L.pdog_clips_create.restype = i; L.pdog_clips_create.argtypes = [p, C.POINTER(p)]
+        L.pdog_clips_destroy.restype = i; L.pdog_clips_destroy.argtypes = [p]
+        L.pdog_clips_modes.restype = i; L.pdog_clips_modes.argtypes = [p, p, i64, i64, i, p, i, p]
+        L.pdog_clips_plan.restype = i; L.pdog_clips_plan.argtypes = [i, i, i, p, p, p, p, p, C.POINTER(i)]
+        L.pdog_clips_track.restype = i; L.pdog_clips_track.argtypes = [p, p, i64, i64, i, i, p, p, i, p, p]
+        L.pdog_clips_get_counters.restype = i; L.pdog_clips_get_counters.argtypes = [p, C.POINTER(C.c_uint64)]
+        L.pdog_clips_set_tuning.restype = i; L.pdog_clips_set_tuning.argtypes = [p, C.c_char_p, i]
     _lib = L
     return L
 

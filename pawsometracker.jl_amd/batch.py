@@ -190,7 +190,86 @@ class BatchTracker:
             C.c_void_p(sub.data_ptr())))
         return (sub, resp) if want_resp else sub
 
+    def set_fill(self, fill):
+        """The PaddedView fill (src/PawsomeTracker.jl:48) of the launches queued from now on (pdog_set_fill)."""
+        _lib.check(_lib.lib().pdog_set_fill(self._h, int(fill)))
+
+    def _clips_handle(self):
+        """The pdog_clips handle behind clip_modes / track_clips: created on first use, closed with the tracker."""
+        if getattr(self, "_clips", None) is None:
+            h = C.c_void_p()
+            _lib.check(_lib.lib().pdog_clips_create(self._h, C.byref(h)))
+            self._clips = h
+        return self._clips
+
+    def clips_counters(self):
+        """(mode calls with one workgroup per frame, mode calls with several, per-frame batches of track_clips, track_clips
+        calls that took the detect_chains fast path) since the handle was created — pdog_clips_get_counters."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().pdog_clips_get_counters(self._clips_handle(), out))
+        return tuple(int(v) for v in out)
+
+    def set_clips_tuning(self, key, value=1):
+        """pdog_clips_set_tuning: tests and A/B only."""
+        _lib.check(_lib.lib().pdog_clips_set_tuning(self._clips_handle(), key.encode(), int(value)))
+
+    def clip_modes(self, frames, frame_index=None, out=None):
+        """mode(_img) (src/PawsomeTracker.jl:47) of many device-resident frames in one call (pdog_clips_modes): frames
+        uint8 cuda [nf, h, w] (row stride may exceed w); entry b looks at frame frame_index[b] (int32 cuda [n]; None:
+        every frame in order).  Returns an int32 cuda tensor [n]; nothing is read back."""
+        import torch
+        self.use_torch_stream()
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
+        assert frames.stride(2) == 1 and frames.shape[1] == self.frame_h and frames.shape[2] == self.frame_w
+        fi, n = None, frames.shape[0]
+        if frame_index is not None:
+            assert frame_index.is_cuda and frame_index.dtype == torch.int32 and frame_index.is_contiguous() and frame_index.dim() == 1
+            fi, n = C.c_void_p(frame_index.data_ptr()), frame_index.shape[0]
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=frames.device)
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.shape == (n,)
+        _lib.check(_lib.lib().pdog_clips_modes(self._clips_handle(), C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1),
+                                               frames.shape[0], fi, n, C.c_void_p(out.data_ptr())))
+        return out
+
+    def track_clips(self, frames, starts, fills=None, lengths=None, first=0, out=None):
+        """Many clips, each with its own fill, length and start (pdog_clips_track): frames uint8 cuda
+        [n_clips, n_frames, h, w] stacked as detect_chains requires, starts int32 cuda [n_clips, 2].  fills (None: the
+        tracker's fill for all) and lengths (None: n_frames each) hold one value per clip — sequences, numpy arrays or
+        tensors, brought to host int32.  first = 0: out[c][0] = functor(frame 0, starts[c]); first = 1: out[c][0] =
+        starts[c] as given and the loop starts at frame 1 (src/PawsomeTracker.jl:161-167).  Returns int32 cuda
+        [n_clips, n_frames, 2]; rows at and beyond a clip's length are not written (a fresh `out` is zeroed)."""
+        import numpy as np
+        import torch
+        self.use_torch_stream()
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.stride(3) == 1
+        assert frames.shape[2] == self.frame_h and frames.shape[3] == self.frame_w
+        assert frames.stride(0) == frames.shape[1] * frames.stride(1), "clips must be stacked contiguously"
+        nc, nf = frames.shape[0], frames.shape[1]
+        assert starts.is_cuda and starts.dtype == torch.int32 and starts.is_contiguous() and starts.shape == (nc, 2)
+
+        def host_i32(v):
+            if v is None:
+                return None, None
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu().numpy()
+            a = np.ascontiguousarray(np.asarray(v), dtype=np.int32)
+            assert a.shape == (nc,), "one value per clip"
+            return a, C.c_void_p(a.ctypes.data)
+
+        fa, fp = host_i32(fills)
+        la, lp = host_i32(lengths)
+        if out is None:
+            out = torch.zeros((nc, nf, 2), dtype=torch.int32, device=frames.device)
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.shape == (nc, nf, 2)
+        _lib.check(_lib.lib().pdog_clips_track(self._clips_handle(), C.c_void_p(frames.data_ptr()), frames.stride(1), frames.stride(2),
+                                               nf, nc, fp, lp, int(first), C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
     def close(self):
+        if getattr(self, "_clips", None) is not None:
+            _lib.lib().pdog_clips_destroy(self._clips)   # before the tracker it borrows
+            self._clips = None
         if getattr(self, "_h", None):
             _lib.lib().pdog_destroy(self._h)
             self._h = None

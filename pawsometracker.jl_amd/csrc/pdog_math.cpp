@@ -185,4 +185,37 @@ int pdog_window_tile(const uint8_t *h_frame, int frame_h, int frame_w, int64_t r
     return PDOG_OK;
 }
 
+// The grouping plan of pdog_clips_track (pawsome_clips.hip), host arithmetic only.  A clip takes part when it has a frame to
+// compute (len > first); the participants are sorted by (fill ascending, len descending, clip ascending), so that a group
+// is one run of equal fills and the clips of a group that are still active at frame k are a prefix of it.
+int pdog_clips_plan(int n_clips, int n_frames, int first, const int32_t *h_fill, const int32_t *h_len, int32_t *out_order,
+                    int32_t *out_group_fill, int32_t *out_group_start, int *out_n_groups)
+{
+    if (!out_order || !out_group_fill || !out_group_start || !out_n_groups) return fail(PDOG_E_ARG, "pdog_clips_plan: null output");
+    if (n_clips <= 0 || n_frames <= 0 || (first != 0 && first != 1)) return fail(PDOG_E_ARG, "pdog_clips_plan: bad size or first");
+    for (int c = 0; c < n_clips; ++c) { // everything is checked before anything is written
+        if (h_fill && (h_fill[c] < 0 || h_fill[c] > 255)) return fail(PDOG_E_ARG, "pdog_clips_plan: fill of clip " + std::to_string(c) + " outside 0 ... 255");
+        if (h_len && (h_len[c] < 0 || h_len[c] > n_frames)) return fail(PDOG_E_ARG, "pdog_clips_plan: length of clip " + std::to_string(c) + " outside 0 ... n_frames");
+    }
+    auto len_of = [&](int c) { return h_len ? (int)h_len[c] : n_frames; };
+    auto fill_of = [&](int c) { return h_fill ? (int)h_fill[c] : -1; };
+    int n = 0;
+    for (int c = 0; c < n_clips; ++c)
+        if (len_of(c) > first) out_order[n++] = c;
+    std::sort(out_order, out_order + n, [&](int32_t a, int32_t b) {
+        if (fill_of(a) != fill_of(b)) return fill_of(a) < fill_of(b);
+        if (len_of(a) != len_of(b)) return len_of(a) > len_of(b);
+        return a < b;
+    });
+    int ng = 0;
+    for (int p = 0; p < n; ++p)
+        if (p == 0 || fill_of(out_order[p]) != fill_of(out_order[p - 1])) {
+            out_group_fill[ng] = fill_of(out_order[p]);
+            out_group_start[ng++] = p;
+        }
+    out_group_start[ng] = n;
+    *out_n_groups = ng;
+    return PDOG_OK;
+}
+
 } // extern "C"

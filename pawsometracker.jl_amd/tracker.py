@@ -271,3 +271,72 @@ def _track_one(frames, target_width, start_location, window_size, darker_target,
     finally:
         trckr.close()
     return indices
+
+
+def track_clips(frames, target_width=25, start_locations=None, window_size=None, darker_target=True, sar=1.0,
+                lengths=None, subpixel=False):
+    """The reference's `track` for every clip of a device-resident stack at once: frames is a uint8 cuda tensor
+    [n_clips, n_frames, h, w] (clips stacked contiguously), the device is the tensor's.  Each clip is tracked as its own
+    `Tracker` would track it (src/PawsomeTracker.jl:39-52): the fill is the mode of ITS first frame (:47-48), the first
+    position comes from ITS bootstrap — the sz .÷ 4 window for a start location of None (:99-107), the functor at the
+    given guess otherwise (:92-97) — and the loop continues from the second frame (:161-167).  `start_locations` is None
+    or one entry per clip, spelled as for get_guess; `lengths` is None or the number of frames of each clip
+    (0 ... n_frames).  Returns int32 cuda [n_clips, n_frames, 2], 1-based (row, col); rows beyond a clip's length hold 0.
+    With subpixel=True the result is (indices, sub), sub float64 cuda of the same shape: BatchTracker.measure at every
+    returned position under that clip's fill (this library's addition; the indices are unchanged)."""
+    import torch
+    from .batch import BatchTracker
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4):
+        raise TypeError("frames must be a uint8 cuda tensor [n_clips, n_frames, h, w]")
+    nc, nf, h, w = (int(v) for v in frames.shape)
+    locs = [None] * nc if start_locations is None else list(start_locations)
+    if len(locs) != nc:
+        raise ValueError(f"{nc} clips but {len(locs)} start locations")
+    lens = np.full(nc, nf, np.int32) if lengths is None else np.ascontiguousarray(
+        lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths), dtype=np.int32)
+    if lens.shape != (nc,) or (lens < 0).any() or (lens > nf).any():
+        raise ValueError("lengths: one value in 0 ... n_frames per clip")
+    if window_size is None:
+        window_size = guess_window_size(target_width)            # :136
+    window_size = fix_window_size(window_size)                   # :142
+    dev = frames.device
+    flat = frames.flatten(0, 1)
+    with torch.cuda.device(dev):
+        bt = BatchTracker(h, w, target_width, window_size, darker_target, 0, device=dev.index)
+        try:
+            # 1. the fills, :47: one launch, one read-back of n_clips ints
+            first_frame = torch.arange(nc, dtype=torch.int32, device=dev) * nf
+            fills = bt.clip_modes(flat, first_frame).cpu().numpy()
+            # 2. the first positions, :92-107: one functor application on each clip's first frame
+            auto = np.array([loc is None for loc in locs], bool)
+            guesses = torch.tensor([get_guess(loc, frames[0, 0], sar) for loc in locs], dtype=torch.int32, device=dev).reshape(nc, 2)
+            has = lens >= 1
+            out = torch.zeros((nc, nf, 2), dtype=torch.int32, device=dev)    # row 0 of a clip first holds its bootstrap
+            if (auto & has).any():
+                bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, 0, device=dev.index)   # :102-103
+                try:
+                    bt4.track_clips(frames, guesses, fills, (auto & has).astype(np.int32), out=out)            # :104
+                    bt4.sync()           # a guess outside the padded frame raises here, like the reference's BoundsError
+                finally:
+                    bt4.close()
+            if (~auto & has).any():
+                bt.track_clips(frames, guesses, fills, (~auto & has).astype(np.int32), out=out)                # :95
+                bt.sync()
+            starts = out[:, 0].contiguous()
+            # 3. the loop from the second frame on, :161-167
+            bt.track_clips(frames, starts, fills, lens, first=1, out=out)
+            if not subpixel:
+                bt.sync()                # what the kernels raised (PdogError) surfaces before the positions are handed out
+                return out
+            sub = torch.zeros((nc, nf, 2), dtype=torch.float64, device=dev)
+            k = np.arange(nf)
+            for f in np.unique(fills[has]):
+                clips = np.nonzero(has & (fills == f))[0]
+                idx = np.concatenate([c * nf + k[: lens[c]] for c in clips])
+                fi = torch.from_numpy(idx.astype(np.int32)).to(dev)
+                bt.set_fill(int(f))
+                sub.view(-1, 2)[fi.long()] = bt.measure(flat, out.view(-1, 2)[fi.long()].contiguous(), fi)
+            bt.sync()
+            return out, sub
+        finally:
+            bt.close()
