@@ -1,0 +1,61 @@
+"""Checked arguments of the entry points that take torch tensors.  What these let through reaches a kernel as a raw
+pointer with the sizes and strides it indexes by, so a violation is raised (`assert` does not survive `python -O`):
+TypeError for a wrong device, dtype or rank, ValueError for a wrong shape, stride or contiguity.  The device is
+looked at last, so that everything else about an argument can be judged — and tested — on host tensors."""
+import numpy as np
+
+_LAYOUT = {2: "[h, w]", 3: "[n, h, w]", 4: "[n_clips, n_frames, h, w]"}
+
+
+def _on_device(t, name, device):
+    if not t.is_cuda or (device is not None and t.device.index != device):
+        raise TypeError(f"{name} must live on the GPU" + ("" if device is None else f" (device {device})") + f", not on {t.device}")
+    return t
+
+
+def device_frames(t, name, dims, hw=None, device=None):
+    """Frames as the kernels read them: a uint8 cuda tensor of `dims` dimensions (see _LAYOUT) whose last stride is 1 (the
+    row stride may exceed w), clips stacked contiguously, and of the tracker's frame size `hw` where one is given."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != dims:
+        raise TypeError(f"{name} must be a uint8 cuda tensor {_LAYOUT[dims]}")
+    if t.stride(-1) != 1:
+        raise ValueError(f"{name}: the last stride must be 1, not {t.stride(-1)}")
+    if dims == 4 and t.stride(0) != t.shape[1] * t.stride(1):
+        raise ValueError(f"{name}: clips must be stacked contiguously")
+    if hw is not None and (t.shape[-2], t.shape[-1]) != hw:
+        raise ValueError(f"{name}: frames of {t.shape[-2]} x {t.shape[-1]}, but the tracker was made for {hw[0]} x {hw[1]}")
+    return _on_device(t, name, device)
+
+
+def device_array(t, name, dtype, shape, device=None):
+    """A contiguous cuda tensor of `dtype` and `shape` (None: any size along that axis)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != len(shape):
+        raise TypeError(f"{name} must be a {dtype} cuda tensor of {len(shape)} dimension(s)")
+    for k, n in enumerate(shape):
+        if n is not None and t.shape[k] != n:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple('n' if v is None else v for v in shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return _on_device(t, name, device)
+
+
+def frame_index_ptr(frame_index, n):
+    """None (entry b looks at frame b), or the address of an int32 cuda tensor [n] (n None: any length)."""
+    if frame_index is None:
+        return None
+    import torch
+    return device_array(frame_index, "frame_index", torch.int32, (n,)).data_ptr()
+
+
+def host_i32(v, name, n):
+    """n values — None, a sequence, a numpy array or a tensor — as a contiguous host int32 array [n] (None stays None)."""
+    if v is None:
+        return None
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(v), dtype=np.int32)
+    if a.shape != (n,):
+        raise ValueError(f"{name}: {n} values expected, one per entry, not shape {a.shape}")
+    return a

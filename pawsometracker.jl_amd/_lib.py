@@ -12,23 +12,6 @@ LIB_PATH = os.environ.get("PAWSOME_DOG_LIB") or os.path.join(_HERE, "libpawsome_
 
 PDOG_OK, PDOG_E_ARG, PDOG_E_HIP, PDOG_E_NODEV, PDOG_E_RANGE, PDOG_E_ALLOC = range(6)
 
-# every symbol include/pawsome_dog.h declares (tests check the library exports them all)
-SYMBOLS = (
-    "pdog_abi_version", "pdog_last_error", "pdog_sigma", "pdog_default_window", "pdog_kernel_len",
-    "pdog_gaussian_taps", "pdog_mode_u8", "pdog_mode_u8_device", "pdog_create", "pdog_destroy", "pdog_get_info",
-    "pdog_set_fill", "pdog_set_stream", "pdog_reserve", "pdog_set_variant", "pdog_kernel_for_batch", "pdog_sync",
-    "pdog_detect_batch", "pdog_detect_host", "pdog_window_tile", "pdog_detect_batch_host", "pdog_detect_chain", "pdog_detect_chains",
-    "pdog_alloc_host", "pdog_free_host", "pdog_detect_chain_progress", "pdog_get_stream",
-    "pdog_group_create", "pdog_group_destroy", "pdog_group_size", "pdog_group_tracker", "pdog_group_shard",
-    "pdog_group_detect_batch", "pdog_group_sync", "pdog_shard_range", "pdog_shard_owner", "pdog_group_test_compact",
-    "pdog_set_exact", "pdog_get_exact", "pdog_get_exact_detail", "pdog_dense_kernel", "pdog_set_tuning",
-    "pdog_diag_create", "pdog_diag_destroy", "pdog_diag_point", "pdog_diag_render",
-    "pdog_subpixel", "pdog_measure",
-    "pdog_clips_create", "pdog_clips_destroy", "pdog_clips_modes", "pdog_clips_plan", "pdog_clips_track",
-    "pdog_clips_get_counters", "pdog_clips_set_tuning",
-)
-
-
 class PdogInfo(C.Structure):
     _fields_ = [
         ("frame_h", C.c_int32), ("frame_w", C.c_int32),
@@ -39,6 +22,71 @@ class PdogInfo(C.Structure):
         ("sigma", C.c_double), ("target_width", C.c_double),
         ("algorithmic_bytes_per_window", C.c_int64), ("algorithmic_fma_per_window", C.c_int64),
     ]
+
+
+_i, _d, _p, _i64, _s = C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_char_p
+_pi, _pp, _pu64 = C.POINTER(_i), C.POINTER(_p), C.POINTER(C.c_uint64)
+
+# every function include/pawsome_dog.h declares, in header order: name -> (restype, argtypes).  tests/test_abi_cpu.py
+# holds this table against the header's prototypes and the library's exports.
+PROTOTYPES = {
+    "pdog_abi_version": (_i, []),
+    "pdog_last_error": (_s, []),
+    "pdog_sigma": (_d, [_d]),
+    "pdog_default_window": (_i, [_d]),
+    "pdog_kernel_len": (_i, [_d]),
+    "pdog_gaussian_taps": (_i, [_d, _i, _p, _i]),
+    "pdog_dense_kernel": (_i, [_d, _i, _p, _i]),
+    "pdog_mode_u8": (_i, [_p, _i, _i, _i64, _pi]),
+    "pdog_mode_u8_device": (_i, [_i, _p, _i, _i, _i64, _p, _pi]),
+    "pdog_create": (_i, [_i, _i, _i, _d, _i, _i, _i, _i, _pp]),
+    "pdog_destroy": (_i, [_p]),
+    "pdog_get_info": (_i, [_p, C.POINTER(PdogInfo)]),
+    "pdog_set_fill": (_i, [_p, _i]),
+    "pdog_set_stream": (_i, [_p, _p]),
+    "pdog_get_stream": (_i, [_p, _pp]),
+    "pdog_reserve": (_i, [_p, _i]),
+    "pdog_kernel_for_batch": (_i, [_p, _i, _pi]),
+    "pdog_set_variant": (_i, [_p, _i]),
+    "pdog_sync": (_i, [_p]),
+    "pdog_set_exact": (_i, [_p, _i]),
+    "pdog_set_tuning": (_i, [_p, _s, _i]),
+    "pdog_get_exact": (_i, [_p, _pi, C.POINTER(_d), _pu64]),
+    "pdog_get_exact_detail": (_i, [_p, _pu64]),
+    "pdog_detect_batch": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _p, _p]),
+    "pdog_subpixel": (_i, [_p, _p, _p]),
+    "pdog_measure": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _p, _p]),
+    "pdog_detect_host": (_i, [_p, _p, _i64, _p, _p, _p]),
+    "pdog_window_tile": (_i, [_p, _i, _i, _i64, _i, _d, _i, _i, _p, _p, _i64]),
+    "pdog_detect_batch_host": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _p]),
+    "pdog_detect_chain": (_i, [_p, _p, _i64, _i64, _i, _p, _p]),
+    "pdog_detect_chains": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _p]),
+    "pdog_clips_create": (_i, [_p, _pp]),
+    "pdog_clips_destroy": (_i, [_p]),
+    "pdog_clips_modes": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _p]),
+    "pdog_clips_plan": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _pi]),
+    "pdog_clips_track": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _p, _i, _p, _p]),
+    "pdog_clips_get_counters": (_i, [_p, _pu64]),
+    "pdog_clips_set_tuning": (_i, [_p, _s, _i]),
+    "pdog_alloc_host": (_i, [C.c_size_t, _pp]),
+    "pdog_free_host": (_i, [_p]),
+    "pdog_detect_chain_progress": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _p]),
+    "pdog_group_create": (_i, [_i, _p, _i, _i, _d, _i, _i, _i, _i, _pp]),
+    "pdog_group_destroy": (_i, [_p]),
+    "pdog_group_size": (_i, [_p]),
+    "pdog_group_tracker": (_i, [_p, _i, _pp]),
+    "pdog_group_shard": (_i, [_p, _i, _i, _pi, _pi]),
+    "pdog_shard_range": (_i, [_i, _i, _i, _pi, _pi]),
+    "pdog_shard_owner": (_i, [_i, _i, _i, _pi, _pi]),
+    "pdog_group_detect_batch": (_i, [_p, _p, _i64, _i64, _p, _p, _p, _i, _p]),
+    "pdog_group_sync": (_i, [_p]),
+    "pdog_group_test_compact": (_i, [_p, _i, _i, _p]),
+    "pdog_diag_create": (_i, [_i, _i, _pp]),
+    "pdog_diag_destroy": (_i, [_p]),
+    "pdog_diag_point": (_i, [_i, _i, _p, _p]),
+    "pdog_diag_render": (_i, [_p, _p, _p, _i64, _i64, _i, _i, _i, _p, _p]),
+}
+SYMBOLS = tuple(PROTOTYPES)
 
 
 class PdogError(RuntimeError):
@@ -82,77 +130,10 @@ def lib():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    i, d, p, i64 = C.c_int, C.c_double, C.c_void_p, C.c_int64
-    L.pdog_abi_version.restype = i
-    L.pdog_last_error.restype = C.c_char_p
-    L.pdog_sigma.restype = d; L.pdog_sigma.argtypes = [d]
-    L.pdog_default_window.restype = i; L.pdog_default_window.argtypes = [d]
-    L.pdog_kernel_len.restype = i; L.pdog_kernel_len.argtypes = [d]
-    L.pdog_gaussian_taps.restype = i; L.pdog_gaussian_taps.argtypes = [d, i, p, i]
-    L.pdog_mode_u8.restype = i; L.pdog_mode_u8.argtypes = [p, i, i, i64, C.POINTER(i)]
-    if hasattr(L, "pdog_mode_u8_device"):
-        L.pdog_mode_u8_device.restype = i; L.pdog_mode_u8_device.argtypes = [i, p, i, i, i64, p, C.POINTER(i)]
-    L.pdog_create.restype = i; L.pdog_create.argtypes = [i, i, i, d, i, i, i, i, C.POINTER(p)]
-    L.pdog_destroy.restype = i; L.pdog_destroy.argtypes = [p]
-    L.pdog_get_info.restype = i; L.pdog_get_info.argtypes = [p, C.POINTER(PdogInfo)]
-    L.pdog_set_fill.restype = i; L.pdog_set_fill.argtypes = [p, i]
-    L.pdog_set_stream.restype = i; L.pdog_set_stream.argtypes = [p, p]
-    L.pdog_reserve.restype = i; L.pdog_reserve.argtypes = [p, i]
-    L.pdog_set_variant.restype = i; L.pdog_set_variant.argtypes = [p, i]
-    L.pdog_sync.restype = i; L.pdog_sync.argtypes = [p]
-    L.pdog_detect_batch.restype = i
-    L.pdog_detect_batch.argtypes = [p, p, i64, i64, i, p, p, i, p, p]
-    L.pdog_detect_host.restype = i; L.pdog_detect_host.argtypes = [p, p, i64, p, p, p]
-    L.pdog_detect_chain.restype = i; L.pdog_detect_chain.argtypes = [p, p, i64, i64, i, p, p]
-    if hasattr(L, "pdog_kernel_for_batch"):
-        L.pdog_kernel_for_batch.restype = i; L.pdog_kernel_for_batch.argtypes = [p, i, C.POINTER(i)]
-    if hasattr(L, "pdog_window_tile"):
-        L.pdog_window_tile.restype = i; L.pdog_window_tile.argtypes = [p, i, i, i64, i, d, i, i, p, p, i64]
-    if hasattr(L, "pdog_detect_batch_host"):
-        L.pdog_detect_batch_host.restype = i; L.pdog_detect_batch_host.argtypes = [p, p, i64, i64, i, p, p, i, p]
-    if hasattr(L, "pdog_detect_chain_progress"):
-        L.pdog_alloc_host.restype = i; L.pdog_alloc_host.argtypes = [C.c_size_t, C.POINTER(p)]
-        L.pdog_free_host.restype = i; L.pdog_free_host.argtypes = [p]
-        L.pdog_detect_chain_progress.restype = i; L.pdog_detect_chain_progress.argtypes = [p, p, i64, i64, i, p, p, p]
-    if hasattr(L, "pdog_detect_chains"):  # absent only in older A/B builds selected through PAWSOME_DOG_LIB
-        L.pdog_detect_chains.restype = i; L.pdog_detect_chains.argtypes = [p, p, i64, i64, i, i, p, p]
-    if hasattr(L, "pdog_group_create"):
-        L.pdog_get_stream.restype = i; L.pdog_get_stream.argtypes = [p, C.POINTER(p)]
-        L.pdog_group_create.restype = i; L.pdog_group_create.argtypes = [i, p, i, i, d, i, i, i, i, C.POINTER(p)]
-        L.pdog_group_destroy.restype = i; L.pdog_group_destroy.argtypes = [p]
-        L.pdog_group_size.restype = i; L.pdog_group_size.argtypes = [p]
-        L.pdog_group_tracker.restype = i; L.pdog_group_tracker.argtypes = [p, i, C.POINTER(p)]
-        L.pdog_group_shard.restype = i; L.pdog_group_shard.argtypes = [p, i, i, C.POINTER(i), C.POINTER(i)]
-        L.pdog_group_detect_batch.restype = i; L.pdog_group_detect_batch.argtypes = [p, p, i64, i64, p, p, p, i, p]
-        L.pdog_group_sync.restype = i; L.pdog_group_sync.argtypes = [p]
-        L.pdog_shard_range.restype = i; L.pdog_shard_range.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
-        L.pdog_shard_owner.restype = i; L.pdog_shard_owner.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
-        if hasattr(L, "pdog_group_test_compact"):   # (absent from older builds loaded through PAWSOME_DOG_LIB for an A/B)
-            L.pdog_group_test_compact.restype = i; L.pdog_group_test_compact.argtypes = [p, i, i, p]
-    if hasattr(L, "pdog_dense_kernel"):
-        L.pdog_dense_kernel.restype = i; L.pdog_dense_kernel.argtypes = [d, i, p, i]
-    if hasattr(L, "pdog_set_tuning"):
-        L.pdog_set_tuning.restype = i; L.pdog_set_tuning.argtypes = [p, C.c_char_p, i]
-    if hasattr(L, "pdog_set_exact"):
-        L.pdog_set_exact.restype = i; L.pdog_set_exact.argtypes = [p, i]
-        L.pdog_get_exact.restype = i; L.pdog_get_exact.argtypes = [p, C.POINTER(i), C.POINTER(d), C.POINTER(C.c_uint64)]
-        L.pdog_get_exact_detail.restype = i; L.pdog_get_exact_detail.argtypes = [p, C.POINTER(C.c_uint64)]
-    if hasattr(L, "pdog_diag_create"):
-        L.pdog_diag_create.restype = i; L.pdog_diag_create.argtypes = [i, i, C.POINTER(p)]
-        L.pdog_diag_destroy.restype = i; L.pdog_diag_destroy.argtypes = [p]
-        L.pdog_diag_point.restype = i; L.pdog_diag_point.argtypes = [i, i, p, p]
-        L.pdog_diag_render.restype = i; L.pdog_diag_render.argtypes = [p, p, p, i64, i64, i, i, i, p, p]
-    if hasattr(L, "pdog_measure"):
-        L.pdog_subpixel.restype = i; L.pdog_subpixel.argtypes = [p, p, p]
-        L.pdog_measure.restype = i; L.pdog_measure.argtypes = [p, p, i64, i64, i, p, p, i, p, p]
-    if hasattr(L, "pdog_clips_create"):  # (absent from older builds loaded through PAWSOME_DOG_LIB for an A/B)
-        L.pdog_clips_create.restype = i; L.pdog_clips_create.argtypes = [p, C.POINTER(p)]
-        L.pdog_clips_destroy.restype = i; L.pdog_clips_destroy.argtypes = [p]
-        L.pdog_clips_modes.restype = i; L.pdog_clips_modes.argtypes = [p, p, i64, i64, i, p, i, p]
-        L.pdog_clips_plan.restype = i; L.pdog_clips_plan.argtypes = [i, i, i, p, p, p, p, p, C.POINTER(i)]
-        L.pdog_clips_track.restype = i; L.pdog_clips_track.argtypes = [p, p, i64, i64, i, i, p, p, i, p, p]
-        L.pdog_clips_get_counters.restype = i; L.pdog_clips_get_counters.argtypes = [p, C.POINTER(C.c_uint64)]
-        L.pdog_clips_set_tuning.restype = i; L.pdog_clips_set_tuning.argtypes = [p, C.c_char_p, i]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -160,3 +141,84 @@ def lib():
 def check(code):
     if code != PDOG_OK:
         raise PdogError(code, lib().pdog_last_error().decode("utf-8", "replace"))
+
+
+def new_handle(create, *args):
+    """create(*args, &out) checked: the out-pointer the ABI's constructors and getters end with."""
+    h = C.c_void_p()
+    check(create(*args, C.byref(h)))
+    return h
+
+
+class Handle:
+    """One opaque handle of the ABI (`_h`) and the name of the entry point that frees it (None: borrowed, its owner
+    frees it).  After close() `_h` is None, which every entry point refuses with PDOG_E_ARG before it launches anything."""
+    _h = None
+
+    def __init__(self, h, destroy):
+        self._h, self._destroy = h, destroy
+
+    def close(self):
+        h, self._h = self._h, None
+        if h and self._destroy:
+            getattr(lib(), self._destroy)(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TrackerHandle(Handle):
+    """A pdog_tracker and the controls that only forward it."""
+
+    def info(self):
+        o = PdogInfo()
+        check(lib().pdog_get_info(self._h, C.byref(o)))
+        return o
+
+    def set_variant(self, variant):
+        check(lib().pdog_set_variant(self._h, int(variant)))
+
+    def set_exact(self, on):
+        """Exact mode (default on): near-ties of the FP32 ranking are re-decided in the reference's Float64 arithmetic."""
+        check(lib().pdog_set_exact(self._h, int(on)))   # 0 off, 1 on, 2 re-evaluate everything (self-check)
+
+    def set_tuning(self, key, value=1):
+        """Pin one of the library's alternative code paths (pdog_set_tuning): tests and A/B only."""
+        check(lib().pdog_set_tuning(self._h, key.encode(), int(value)))
+
+    def exact_stats(self):
+        """(on, threshold 2δ, windows re-evaluated so far) — pdog_get_exact."""
+        on, thr, n = C.c_int(), C.c_double(), C.c_uint64()
+        check(lib().pdog_get_exact(self._h, C.byref(on), C.byref(thr), C.byref(n)))
+        return bool(on.value), thr.value, int(n.value)
+
+    def exact_detail(self):
+        """(windows refined, column blocks rescanned, candidates, sequential chains) — pdog_get_exact_detail."""
+        out = (C.c_uint64 * 4)()
+        check(lib().pdog_get_exact_detail(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def kernel_for_batch(self, n):
+        """Variant id of the kernel family a batch of n windows runs on (300 fused, 400 tiled, 200 two-pass, else info().variant)."""
+        o = C.c_int()
+        check(lib().pdog_kernel_for_batch(self._h, int(n), C.byref(o)))
+        return o.value
+
+    def reserve(self, n):
+        check(lib().pdog_reserve(self._h, int(n)))
+
+    def set_fill(self, fill):
+        """The PaddedView fill (src/PawsomeTracker.jl:48) of the launches queued from now on (pdog_set_fill)."""
+        check(lib().pdog_set_fill(self._h, int(fill)))
+
+    def sync(self):
+        check(lib().pdog_sync(self._h))

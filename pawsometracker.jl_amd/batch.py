@@ -9,54 +9,19 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
+from ._args import device_array, device_frames, frame_index_ptr, host_i32
 
 
-class BatchTracker:
+class BatchTracker(_lib.TrackerHandle):
+    _clips = None
+
     def __init__(self, frame_h, frame_w, target_width, window_size, darker_target, fill, device=0):
-        h = C.c_void_p()
-        _lib.check(_lib.lib().pdog_create(int(device), int(frame_h), int(frame_w), float(target_width),
-                                          int(window_size[0]), int(window_size[1]), int(bool(darker_target)),
-                                          int(fill), C.byref(h)))
-        self._h = h
+        super().__init__(_lib.new_handle(_lib.lib().pdog_create, int(device), int(frame_h), int(frame_w), float(target_width),
+                                         int(window_size[0]), int(window_size[1]), int(bool(darker_target)), int(fill)),
+                         "pdog_destroy")
         self.device = int(device)
         self.frame_h, self.frame_w = int(frame_h), int(frame_w)
-
-    def info(self):
-        o = _lib.PdogInfo()
-        _lib.check(_lib.lib().pdog_get_info(self._h, C.byref(o)))
-        return o
-
-    def set_variant(self, variant):
-        _lib.check(_lib.lib().pdog_set_variant(self._h, int(variant)))
-
-    def set_exact(self, on):
-        """Exact mode (default on): near-ties of the FP32 ranking are re-decided in the reference's Float64 arithmetic."""
-        _lib.check(_lib.lib().pdog_set_exact(self._h, int(on)))   # 0 off, 1 on, 2 re-evaluate everything (self-check)
-
-    def set_tuning(self, key, value=1):
-        """Pin one of the library's alternative code paths (pdog_set_tuning): tests and A/B only."""
-        _lib.check(_lib.lib().pdog_set_tuning(self._h, key.encode(), int(value)))
-
-    def exact_stats(self):
-        """(on, threshold 2δ, windows re-evaluated so far) — pdog_get_exact."""
-        on, thr, n = C.c_int(), C.c_double(), C.c_uint64()
-        _lib.check(_lib.lib().pdog_get_exact(self._h, C.byref(on), C.byref(thr), C.byref(n)))
-        return bool(on.value), thr.value, int(n.value)
-
-    def exact_detail(self):
-        """(windows refined, column blocks rescanned, candidates, sequential chains) — pdog_get_exact_detail."""
-        out = (C.c_uint64 * 4)()
-        _lib.check(_lib.lib().pdog_get_exact_detail(self._h, out))
-        return tuple(int(v) for v in out)
-
-    def kernel_for_batch(self, n):
-        """Variant id of the kernel family a batch of n windows runs on (300 fused, 400 tiled, 200 two-pass, else info().variant)."""
-        o = C.c_int()
-        _lib.check(_lib.lib().pdog_kernel_for_batch(self._h, int(n), C.byref(o)))
-        return o.value
-
-    def reserve(self, n):
-        _lib.check(_lib.lib().pdog_reserve(self._h, int(n)))
+        self._hw = (self.frame_h, self.frame_w)
 
     def use_torch_stream(self):
         """Launch on torch's current stream.  Every detect* call does this: the kernels are asynchronous, and
@@ -65,29 +30,21 @@ class BatchTracker:
         import torch
         _lib.check(_lib.lib().pdog_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
-    def sync(self):
-        _lib.check(_lib.lib().pdog_sync(self._h))
-
     def detect(self, frames, guesses, frame_index=None, out=None, want_resp=False):
         """frames: uint8 cuda tensor [nf, h, w] (row stride may exceed w); guesses: int32 cuda [n, 2]
         1-based (row, col).  Returns int32 cuda [n, 2] (and float32 [n, win_w, win_h] — each
         window column-major, i.e. resp[b].T is the h x w response — when want_resp)."""
         import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
-        assert frames.stride(2) == 1 and frames.shape[1] == self.frame_h and frames.shape[2] == self.frame_w
-        assert guesses.is_cuda and guesses.dtype == torch.int32 and guesses.is_contiguous()
-        n = guesses.shape[0]
+        device_frames(frames, "frames", 3, self._hw)
+        n = device_array(guesses, "guesses", torch.int32, (None, 2)).shape[0]
+        fi = frame_index_ptr(frame_index, n)
         if out is None:
             out = torch.empty((n, 2), dtype=torch.int32, device=frames.device)
         resp = None
         if want_resp:
             info = self.info()
             resp = torch.empty((n, info.win_w, info.win_h), dtype=torch.float32, device=frames.device)
-        fi = None
-        if frame_index is not None:
-            assert frame_index.is_cuda and frame_index.dtype == torch.int32 and frame_index.is_contiguous()
-            fi = C.c_void_p(frame_index.data_ptr())
         _lib.check(_lib.lib().pdog_detect_batch(
             self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
             C.c_void_p(guesses.data_ptr()), n, C.c_void_p(out.data_ptr()),
@@ -100,26 +57,27 @@ class BatchTracker:
         in chunks that overlap the kernels.  guesses int32 [n, 2]; returns numpy int32 [n, 2].  Synchronous."""
         import numpy as np
         self.use_torch_stream()
-        assert frames.dtype == np.uint8 and frames.ndim == 3 and frames.strides[2] == 1
-        assert frames.shape[1] == self.frame_h and frames.shape[2] == self.frame_w
+        if not isinstance(frames, np.ndarray) or frames.dtype != np.uint8 or frames.ndim != 3:
+            raise TypeError("frames must be a numpy uint8 array [n, h, w]")
+        if frames.strides[2] != 1 or frames.shape[1:] != self._hw:
+            raise ValueError(f"frames: {frames.shape[1]} x {frames.shape[2]} with last stride {frames.strides[2]}, "
+                             f"the tracker needs {self.frame_h} x {self.frame_w} with last stride 1")
         g = np.ascontiguousarray(guesses, np.int32)
         n = g.shape[0]
+        if g.shape != (n, 2):
+            raise ValueError(f"guesses: shape {g.shape}, expected (n, 2)")
         out = np.empty((n, 2), np.int32)
-        fi = None
-        if frame_index is not None:
-            fi_arr = np.ascontiguousarray(frame_index, np.int32)
-            assert fi_arr.shape == (n,)
-            fi = C.c_void_p(fi_arr.ctypes.data)
+        fi_arr = host_i32(frame_index, "frame_index", n)
         _lib.check(_lib.lib().pdog_detect_batch_host(
-            self._h, C.c_void_p(frames.ctypes.data), frames.strides[0], frames.strides[1], frames.shape[0], fi,
-            C.c_void_p(g.ctypes.data), n, C.c_void_p(out.ctypes.data)))
+            self._h, C.c_void_p(frames.ctypes.data), frames.strides[0], frames.strides[1], frames.shape[0],
+            None if fi_arr is None else C.c_void_p(fi_arr.ctypes.data), C.c_void_p(g.ctypes.data), n, C.c_void_p(out.ctypes.data)))
         return out
 
     def detect_chain(self, frames, start_guess, out=None):
         """The serial chain of src/PawsomeTracker.jl:163-169 on device-resident frames."""
         import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3 and frames.stride(2) == 1
+        device_frames(frames, "frames", 3, self._hw)
         n = frames.shape[0]
         if out is None:
             out = torch.empty((n, 2), dtype=torch.int32, device=frames.device)
@@ -132,14 +90,13 @@ class BatchTracker:
         """detect_chain whose positions land in host memory as the frames finish (pdog_detect_chain_progress): returns a
         ChainProgress to poll — what a per-frame consumer such as the reference's diagnostic overlay
         (src/diagnose.jl:30-38) needs from a device-side chain."""
-        import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3 and frames.stride(2) == 1
+        device_frames(frames, "frames", 3, self._hw)
         cp = ChainProgress(self, frames.shape[0], frames)
         g = (C.c_int32 * 2)(int(start_guess[0]), int(start_guess[1]))
         try:
             _lib.check(_lib.lib().pdog_detect_chain_progress(self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1),
-                                                             frames.shape[0], g, cp._out_ptr, cp._prog_ptr))
+                                                             frames.shape[0], g, cp._out._h, cp._prog._h))
         except Exception:
             cp.close()      # nothing was queued: the pinned buffers go back at once
             raise
@@ -150,10 +107,9 @@ class BatchTracker:
         start_guesses int32 cuda [n_clips, 2]; returns int32 cuda [n_clips, n_frames, 2]."""
         import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.stride(3) == 1
-        assert frames.stride(0) == frames.shape[1] * frames.stride(1), "clips must be stacked contiguously"
-        assert start_guesses.is_cuda and start_guesses.dtype == torch.int32 and start_guesses.is_contiguous()
+        device_frames(frames, "frames", 4, self._hw)
         nc, nf = frames.shape[0], frames.shape[1]
+        device_array(start_guesses, "start_guesses", torch.int32, (nc, 2))
         if out is None:
             out = torch.empty((nc, nf, 2), dtype=torch.int32, device=frames.device)
         _lib.check(_lib.lib().pdog_detect_chains(self._h, C.c_void_p(frames.data_ptr()), frames.stride(1), frames.stride(2),
@@ -173,34 +129,22 @@ class BatchTracker:
         """
         import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
-        assert frames.stride(2) == 1 and frames.shape[1] == self.frame_h and frames.shape[2] == self.frame_w
-        assert ij.is_cuda and ij.dtype == torch.int32 and ij.is_contiguous() and ij.dim() == 2 and ij.shape[1] == 2
-        n = ij.shape[0]
+        device_frames(frames, "frames", 3, self._hw)
+        n = device_array(ij, "ij", torch.int32, (None, 2)).shape[0]
+        fi = frame_index_ptr(frame_index, n)
         sub = torch.empty((n, 2), dtype=torch.float64, device=frames.device)
         resp = torch.empty((n, 5), dtype=torch.float64, device=frames.device) if want_resp else None
-        fi = None
-        if frame_index is not None:
-            assert frame_index.is_cuda and frame_index.dtype == torch.int32 and frame_index.is_contiguous()
-            assert frame_index.shape == (n,)
-            fi = C.c_void_p(frame_index.data_ptr())
         _lib.check(_lib.lib().pdog_measure(
             self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
             C.c_void_p(ij.data_ptr()), n, C.c_void_p(resp.data_ptr()) if want_resp else None,
             C.c_void_p(sub.data_ptr())))
         return (sub, resp) if want_resp else sub
 
-    def set_fill(self, fill):
-        """The PaddedView fill (src/PawsomeTracker.jl:48) of the launches queued from now on (pdog_set_fill)."""
-        _lib.check(_lib.lib().pdog_set_fill(self._h, int(fill)))
-
     def _clips_handle(self):
         """The pdog_clips handle behind clip_modes / track_clips: created on first use, closed with the tracker."""
-        if getattr(self, "_clips", None) is None:
-            h = C.c_void_p()
-            _lib.check(_lib.lib().pdog_clips_create(self._h, C.byref(h)))
-            self._clips = h
-        return self._clips
+        if self._clips is None:
+            self._clips = _lib.Handle(_lib.new_handle(_lib.lib().pdog_clips_create, self._h), "pdog_clips_destroy")
+        return self._clips._h
 
     def clips_counters(self):
         """(mode calls with one workgroup per frame, mode calls with several, per-frame batches of track_clips, track_clips
@@ -219,15 +163,12 @@ class BatchTracker:
         every frame in order).  Returns an int32 cuda tensor [n]; nothing is read back."""
         import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
-        assert frames.stride(2) == 1 and frames.shape[1] == self.frame_h and frames.shape[2] == self.frame_w
-        fi, n = None, frames.shape[0]
-        if frame_index is not None:
-            assert frame_index.is_cuda and frame_index.dtype == torch.int32 and frame_index.is_contiguous() and frame_index.dim() == 1
-            fi, n = C.c_void_p(frame_index.data_ptr()), frame_index.shape[0]
+        device_frames(frames, "frames", 3, self._hw)
+        fi = frame_index_ptr(frame_index, None)
+        n = frames.shape[0] if fi is None else frame_index.shape[0]
         if out is None:
             out = torch.empty((n,), dtype=torch.int32, device=frames.device)
-        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.shape == (n,)
+        device_array(out, "out", torch.int32, (n,))
         _lib.check(_lib.lib().pdog_clips_modes(self._clips_handle(), C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1),
                                                frames.shape[0], fi, n, C.c_void_p(out.data_ptr())))
         return out
@@ -239,46 +180,26 @@ class BatchTracker:
         tensors, brought to host int32.  first = 0: out[c][0] = functor(frame 0, starts[c]); first = 1: out[c][0] =
         starts[c] as given and the loop starts at frame 1 (src/PawsomeTracker.jl:161-167).  Returns int32 cuda
         [n_clips, n_frames, 2]; rows at and beyond a clip's length are not written (a fresh `out` is zeroed)."""
-        import numpy as np
         import torch
         self.use_torch_stream()
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.stride(3) == 1
-        assert frames.shape[2] == self.frame_h and frames.shape[3] == self.frame_w
-        assert frames.stride(0) == frames.shape[1] * frames.stride(1), "clips must be stacked contiguously"
+        device_frames(frames, "frames", 4, self._hw)
         nc, nf = frames.shape[0], frames.shape[1]
-        assert starts.is_cuda and starts.dtype == torch.int32 and starts.is_contiguous() and starts.shape == (nc, 2)
-
-        def host_i32(v):
-            if v is None:
-                return None, None
-            if isinstance(v, torch.Tensor):
-                v = v.detach().cpu().numpy()
-            a = np.ascontiguousarray(np.asarray(v), dtype=np.int32)
-            assert a.shape == (nc,), "one value per clip"
-            return a, C.c_void_p(a.ctypes.data)
-
-        fa, fp = host_i32(fills)
-        la, lp = host_i32(lengths)
+        device_array(starts, "starts", torch.int32, (nc, 2))
+        fa, la = host_i32(fills, "fills", nc), host_i32(lengths, "lengths", nc)
         if out is None:
             out = torch.zeros((nc, nf, 2), dtype=torch.int32, device=frames.device)
-        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.shape == (nc, nf, 2)
+        device_array(out, "out", torch.int32, (nc, nf, 2))
         _lib.check(_lib.lib().pdog_clips_track(self._clips_handle(), C.c_void_p(frames.data_ptr()), frames.stride(1), frames.stride(2),
-                                               nf, nc, fp, lp, int(first), C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
+                                               nf, nc, None if fa is None else C.c_void_p(fa.ctypes.data),
+                                               None if la is None else C.c_void_p(la.ctypes.data), int(first),
+                                               C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
     def close(self):
-        if getattr(self, "_clips", None) is not None:
-            _lib.lib().pdog_clips_destroy(self._clips)   # before the tracker it borrows
+        if self._clips is not None:
+            self._clips.close()          # before the tracker it borrows
             self._clips = None
-        if getattr(self, "_h", None):
-            _lib.lib().pdog_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 class ChainProgress:
@@ -288,21 +209,15 @@ class ChainProgress:
     def __init__(self, bt, n_frames, keepalive=None):
         import numpy as np
         self._bt, self.n_frames, self._keepalive = bt, int(n_frames), keepalive
-        self._out_ptr = self._prog_ptr = None
-        out, prog = C.c_void_p(), C.c_void_p()
-        _lib.check(_lib.lib().pdog_alloc_host(8 * self.n_frames, C.byref(out)))
-        self._out_ptr = out
-        try:
-            _lib.check(_lib.lib().pdog_alloc_host(4, C.byref(prog)))
-        except Exception:
-            self.close()
-            raise
-        self._prog_ptr = prog
-        self.positions = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_int32)), shape=(self.n_frames, 2))
-        self._prog = np.ctypeslib.as_array(C.cast(prog, C.POINTER(C.c_int32)), shape=(1,))
+        alloc = _lib.lib().pdog_alloc_host
+        out = _lib.Handle(_lib.new_handle(alloc, 8 * self.n_frames), "pdog_free_host")
+        prog = _lib.Handle(_lib.new_handle(alloc, 4), "pdog_free_host")     # (should this raise, `out` frees itself)
+        self._out, self._prog = out, prog
+        self.positions = np.ctypeslib.as_array(C.cast(self._out._h, C.POINTER(C.c_int32)), shape=(self.n_frames, 2))
+        self._done = np.ctypeslib.as_array(C.cast(self._prog._h, C.POINTER(C.c_int32)), shape=(1,))
 
     def done(self):
-        return int(self._prog[0])
+        return int(self._done[0])
 
     def wait(self):
         self._bt.sync()
@@ -311,17 +226,15 @@ class ChainProgress:
     def close(self):
         """Give the pinned buffers back.  The chain that writes them must have finished: the tracker's stream is
         drained first — unless the tracker itself is already closed (pdog_destroy drains its stream)."""
-        if self._out_ptr is None and self._prog_ptr is None:
+        if self._out._h is None:
             return
         try:
-            if getattr(self._bt, "_h", None):
+            if self._bt._h:
                 self._bt.sync()          # may raise what the chain's kernels raised: the buffers go back regardless
         finally:
-            self.positions = self._prog = None
-            for ptr in (self._out_ptr, self._prog_ptr):
-                if ptr is not None:
-                    _lib.lib().pdog_free_host(ptr)
-            self._out_ptr = self._prog_ptr = None
+            self.positions = self._done = None
+            self._out.close()
+            self._prog.close()
 
     def __del__(self):
         try:
@@ -330,7 +243,7 @@ class ChainProgress:
             pass
 
 
-class GroupTracker:
+class GroupTracker(_lib.Handle):
     """Several GPUs of one node behind one handle (pdog_group_*): contiguous window shards per device, frames and
     guesses resident on the owning device, one RCCL gather of the int32 positions to the root device per batch
     (the sharded unit is the functor src/PawsomeTracker.jl:55-62, the gathered result :173).
@@ -339,11 +252,9 @@ class GroupTracker:
     def __init__(self, devices, frame_h, frame_w, target_width, window_size, darker_target, fill):
         self.devices = [int(d) for d in devices]
         arr = (C.c_int * len(self.devices))(*self.devices)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().pdog_group_create(len(self.devices), arr, int(frame_h), int(frame_w), float(target_width),
-                                                int(window_size[0]), int(window_size[1]), int(bool(darker_target)),
-                                                int(fill), C.byref(h)))
-        self._h = h
+        super().__init__(_lib.new_handle(_lib.lib().pdog_group_create, len(self.devices), arr, int(frame_h), int(frame_w),
+                                         float(target_width), int(window_size[0]), int(window_size[1]),
+                                         int(bool(darker_target)), int(fill)), "pdog_group_destroy")
         self.frame_h, self.frame_w = int(frame_h), int(frame_w)
 
     def size(self):
@@ -354,35 +265,24 @@ class GroupTracker:
         _lib.check(_lib.lib().pdog_group_shard(self._h, int(n_total), int(rank), C.byref(lo), C.byref(hi)))
         return lo.value, hi.value
 
-    def info(self, rank=0):
-        t = C.c_void_p()
-        _lib.check(_lib.lib().pdog_group_tracker(self._h, int(rank), C.byref(t)))
-        o = _lib.PdogInfo()
-        _lib.check(_lib.lib().pdog_get_info(t, C.byref(o)))
-        return o
-
     def _tracker(self, rank):
-        t = C.c_void_p()
-        _lib.check(_lib.lib().pdog_group_tracker(self._h, int(rank), C.byref(t)))
-        return t
+        """Rank's tracker, borrowed: the group owns it."""
+        return _lib.TrackerHandle(_lib.new_handle(_lib.lib().pdog_group_tracker, self._h, int(rank)), None)
+
+    def info(self, rank=0):
+        return self._tracker(rank).info()
 
     def stream(self, rank):
         """The hipStream_t (as an int) rank's tracker launches on."""
-        st = C.c_void_p()
-        _lib.check(_lib.lib().pdog_get_stream(self._tracker(rank), C.byref(st)))
-        return st.value or 0
+        return _lib.new_handle(_lib.lib().pdog_get_stream, self._tracker(rank)._h).value or 0
 
     def kernel_for_batch(self, n_per_rank, rank=0):
-        o = C.c_int()
-        _lib.check(_lib.lib().pdog_kernel_for_batch(self._tracker(rank), int(n_per_rank), C.byref(o)))
-        return o.value
+        return self._tracker(rank).kernel_for_batch(n_per_rank)
 
     def reserve(self, n_total):
         for r in range(len(self.devices)):
             lo, hi = self.shard(n_total, r)
-            t = C.c_void_p()
-            _lib.check(_lib.lib().pdog_group_tracker(self._h, r, C.byref(t)))
-            _lib.check(_lib.lib().pdog_reserve(t, max(1, hi - lo)))
+            self._tracker(r).reserve(max(1, hi - lo))
 
     def detect(self, frames, guesses, n_total, out, frame_index=None):
         """frames[r]: uint8 cuda tensor [nf_r, h, w] on device r (same strides on every rank); guesses[r]: int32 cuda
@@ -390,45 +290,34 @@ class GroupTracker:
         device.  Asynchronous (each rank's tracker stream); sync() waits.  The caller keeps the tensors alive until then."""
         import torch
         nd = len(self.devices)
-        assert len(frames) == nd and len(guesses) == nd
-        for r in range(nd):
-            f, gq = frames[r], guesses[r]
+        if len(frames) != nd or len(guesses) != nd or (frame_index is not None and len(frame_index) != nd):
+            raise ValueError(f"frames, guesses and frame_index hold one entry per device ({nd})")
+        fi = None if frame_index is None else [None] * nd
+        for r, dev in enumerate(self.devices):
             lo, hi = self.shard(n_total, r)
-            assert f.is_cuda and f.dtype == torch.uint8 and f.dim() == 3 and f.stride(2) == 1 and f.device.index == self.devices[r]
-            assert f.shape[1] == self.frame_h and f.shape[2] == self.frame_w
-            assert f.stride(0) == frames[0].stride(0) and f.stride(1) == frames[0].stride(1)
-            assert gq.is_cuda and gq.dtype == torch.int32 and gq.is_contiguous() and gq.shape == (hi - lo, 2) and gq.device.index == self.devices[r]
-        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.shape == (n_total, 2) and out.device.index == self.devices[0]
+            f = device_frames(frames[r], f"frames[{r}]", 3, (self.frame_h, self.frame_w), dev)
+            if f.stride(0) != frames[0].stride(0) or f.stride(1) != frames[0].stride(1):
+                raise ValueError(f"frames[{r}]: every rank's frames must have the strides of frames[0]")
+            device_array(guesses[r], f"guesses[{r}]", torch.int32, (hi - lo, 2), dev)
+            if fi is not None and frame_index[r] is not None:
+                fi[r] = device_array(frame_index[r], f"frame_index[{r}]", torch.int32, (hi - lo,), dev).data_ptr()
+        device_array(out, "out", torch.int32, (n_total, 2), self.devices[0])
         P = C.c_void_p * nd
         fr = P(*[f.data_ptr() for f in frames])
         gs = P(*[q.data_ptr() for q in guesses])
         nf = (C.c_int * nd)(*[f.shape[0] for f in frames])
-        fi = None
-        if frame_index is not None:
-            fi = P(*[(x.data_ptr() if x is not None else None) for x in frame_index])
-        _lib.check(_lib.lib().pdog_group_detect_batch(self._h, fr, frames[0].stride(0), frames[0].stride(1), nf, fi, gs,
-                                                      int(n_total), C.c_void_p(out.data_ptr())))
+        _lib.check(_lib.lib().pdog_group_detect_batch(self._h, fr, frames[0].stride(0), frames[0].stride(1), nf,
+                                                      None if fi is None else P(*fi), gs, int(n_total), C.c_void_p(out.data_ptr())))
         return out
 
     def sync(self):
         _lib.check(_lib.lib().pdog_group_sync(self._h))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().pdog_group_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def mode_device(frame):
     """mode(_img) (src/PawsomeTracker.jl:47, StatsBase tie rule) of a uint8 cuda tensor [h, w]."""
     import torch
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 2 and frame.stride(1) == 1
+    device_frames(frame, "frame", 2)
     out = C.c_int()
     dev = frame.device.index if frame.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.lib().pdog_mode_u8_device(dev, C.c_void_p(frame.data_ptr()), frame.shape[0], frame.shape[1], frame.stride(0),

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._args import host_i32
 
 
 def get_sigma(target_width):
@@ -67,7 +68,15 @@ class _PaddedFrame:
         self.fillvalue = fillvalue
 
 
-class Tracker:
+def _to_device(frame, ij, device):
+    """One host frame and one 1-based position as the batch entry points take them: uint8 cuda [1, h, w], int32 cuda [1, 2]."""
+    import torch
+    dev = torch.device("cuda", device)
+    f = torch.from_numpy(np.ascontiguousarray(frame, np.uint8)).to(dev).unsqueeze(0)
+    return f, torch.tensor([[int(ij[0]), int(ij[1])]], dtype=torch.int32, device=dev)
+
+
+class Tracker(_lib.TrackerHandle):
     """src/PawsomeTracker.jl:32-62 — constructor (:39-52) and functor (:55-62)."""
 
     def __init__(self, img, target_width, window_size, darker_target, device=0):
@@ -80,12 +89,9 @@ class Tracker:
         self.darker_target = bool(darker_target)
         fillvalue = mode(img)                                        # :47
         self.img = _PaddedFrame(np.array(img, dtype=np.uint8, order="C", copy=True), fillvalue)  # :48
-        h = C.c_void_p()
-        _lib.check(_lib.lib().pdog_create(int(device), self.sz[0], self.sz[1], self.target_width,
-                                          int(window_size[0]), int(window_size[1]),
-                                          int(self.darker_target), fillvalue, C.byref(h)))
-        self._h = h
-        self._resp = None
+        super().__init__(_lib.new_handle(_lib.lib().pdog_create, int(device), self.sz[0], self.sz[1], self.target_width,
+                                         int(window_size[0]), int(window_size[1]), int(self.darker_target), fillvalue),
+                         "pdog_destroy")
         self.device = int(device)
 
     # -- the functor, :55-62 --
@@ -107,56 +113,15 @@ class Tracker:
         want_resp, the five responses {c, up, down, left, right} there (pdog_measure).  The frame goes up through torch,
         the kernel runs on the tracker's own stream.  Synchronous, like the functor."""
         import torch
-        dev = torch.device("cuda", self.device)
-        f = torch.from_numpy(np.ascontiguousarray(self.img.data, np.uint8)).to(dev).unsqueeze(0)
-        p = torch.tensor([[int(ij[0]), int(ij[1])]], dtype=torch.int32, device=dev)
-        out = torch.empty((1, 7), dtype=torch.float64, device=dev)
-        torch.cuda.current_stream(dev).synchronize()          # the upload is on torch's stream
+        f, p = _to_device(self.img.data, ij, self.device)
+        out = torch.empty((1, 7), dtype=torch.float64, device=f.device)
+        torch.cuda.current_stream(f.device).synchronize()     # the upload is on torch's stream
         _lib.check(_lib.lib().pdog_measure(self._h, C.c_void_p(f.data_ptr()), f.stride(0), f.stride(1), 1, None,
                                            C.c_void_p(p.data_ptr()), 1, C.c_void_p(out.data_ptr()),
                                            C.c_void_p(out.data_ptr() + 5 * 8)))
-        _lib.check(_lib.lib().pdog_sync(self._h))
+        self.sync()
         v = [float(x) for x in out[0].cpu()]
         return ((v[5], v[6]), tuple(v[:5])) if want_resp else (v[5], v[6])
-
-    def info(self):
-        o = _lib.PdogInfo()
-        _lib.check(_lib.lib().pdog_get_info(self._h, C.byref(o)))
-        return o
-
-    def set_exact(self, on):
-        """Exact mode (default on): near-ties of the FP32 ranking are re-decided in the reference's Float64 arithmetic."""
-        _lib.check(_lib.lib().pdog_set_exact(self._h, int(on)))   # 0 off, 1 on, 2 re-evaluate everything (self-check)
-
-    def set_tuning(self, key, value=1):
-        """Pin one of the library's alternative code paths (pdog_set_tuning): tests and A/B only."""
-        _lib.check(_lib.lib().pdog_set_tuning(self._h, key.encode(), int(value)))
-
-    def exact_stats(self):
-        """(on, threshold 2δ, windows re-evaluated so far) — pdog_get_exact."""
-        on, thr, n = C.c_int(), C.c_double(), C.c_uint64()
-        _lib.check(_lib.lib().pdog_get_exact(self._h, C.byref(on), C.byref(thr), C.byref(n)))
-        return bool(on.value), thr.value, int(n.value)
-
-    def exact_detail(self):
-        """(windows refined, column blocks rescanned, candidates, sequential chains) — pdog_get_exact_detail."""
-        out = (C.c_uint64 * 4)()
-        _lib.check(_lib.lib().pdog_get_exact_detail(self._h, out))
-        return tuple(int(v) for v in out)
-
-    def set_variant(self, variant):
-        _lib.check(_lib.lib().pdog_set_variant(self._h, int(variant)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().pdog_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def get_guess(start_location, img, sar=1.0):
@@ -243,11 +208,7 @@ def track_segments(segments, start_locations=None, target_width=25, window_size=
 
 def _overlay(dia, frame, ij, device):
     """dia(trckr.img.data, indices[k]) for one host frame: it goes up, the 360 x 640 buffer comes back."""
-    import torch
-    dev = torch.device("cuda", device)
-    f = torch.from_numpy(np.ascontiguousarray(frame, np.uint8)).to(dev).unsqueeze(0)
-    p = torch.tensor([ij], dtype=torch.int32, device=dev)
-    return dia(f, p)[0].cpu().numpy()
+    return dia(*_to_device(frame, ij, device))[0].cpu().numpy()
 
 
 def _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub=None):
@@ -292,9 +253,8 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
     locs = [None] * nc if start_locations is None else list(start_locations)
     if len(locs) != nc:
         raise ValueError(f"{nc} clips but {len(locs)} start locations")
-    lens = np.full(nc, nf, np.int32) if lengths is None else np.ascontiguousarray(
-        lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths), dtype=np.int32)
-    if lens.shape != (nc,) or (lens < 0).any() or (lens > nf).any():
+    lens = np.full(nc, nf, np.int32) if lengths is None else host_i32(lengths, "lengths", nc)
+    if (lens < 0).any() or (lens > nf).any():
         raise ValueError("lengths: one value in 0 ... n_frames per clip")
     if window_size is None:
         window_size = guess_window_size(target_width)            # :136

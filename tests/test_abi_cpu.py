@@ -184,3 +184,120 @@ def test_dense_kernel_is_bit_equal_to_the_oracle(oracle):
             ref = oracle.dog_kernel(oracle.sigma(tw), bool(darker), l)
             assert np.array_equal(K.view(np.uint64), ref.view(np.uint64)), (tw, darker)
     assert L.pdog_dense_kernel(25.0, 1, np.empty(4).ctypes.data, 4) == _lib.PDOG_E_ARG
+
+
+def _header_prototypes():
+    """[(name, return kind, [argument kinds])] of every function include/pawsome_dog.h declares, in its order."""
+    hdr = open(os.path.join(ROOT, "include", "pawsome_dog.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"^\s*#.*$", " ", hdr, flags=re.M)
+    scalars = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "double": C.c_double, "size_t": C.c_size_t}
+
+    def kind(decl, named):
+        decl = " ".join(decl.split())
+        if "*" in decl or "[" in decl:
+            return C.c_char_p if re.match(r"const char \*", decl) else "pointer"
+        words = [w for w in decl.split() if w != "const"]
+        if named:
+            assert len(words) == 2, decl       # a type and the parameter's name
+        return scalars[words[0]]
+
+    protos = []
+    for stmt in hdr.split(";"):
+        m = re.match(r"\s*(.*?)\b(pdog_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+        if m:
+            args = m.group(3).strip()
+            protos.append((m.group(2), kind(m.group(1), False), [] if args == "void" else [kind(a, True) for a in args.split(",")]))
+    return protos
+
+
+def _same_kind(ctype, kind):
+    if kind == "pointer":
+        return ctype is C.c_void_p or issubclass(ctype, C._Pointer)
+    return ctype is kind
+
+
+def test_prototype_table_matches_the_header():
+    """Every prototype of the header against _lib.PROTOTYPES, argument by argument: a stride bound as c_int where the header
+    says int64_t would be truncated without a word and hand the kernels a wrong address."""
+    protos = _header_prototypes()
+    assert [name for name, _, _ in protos] == list(_lib.PROTOTYPES) and len(protos) == 55
+    for name, ret, args in protos:
+        restype, argtypes = _lib.PROTOTYPES[name]
+        assert _same_kind(restype, ret), (name, restype, ret)
+        assert len(argtypes) == len(args), (name, len(argtypes), len(args))
+        for k, (ctype, want) in enumerate(zip(argtypes, args)):
+            assert _same_kind(ctype, want), (name, k, ctype, want)
+        fn = getattr(pt.lib(), name)           # and lib() bound exactly the table
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_argument_helpers_reject_bad_input():
+    """The checks in front of every raw pointer (_args.py), on host tensors: TypeError for a wrong device, dtype or rank,
+    ValueError for a wrong shape, stride or contiguity; each message names the argument."""
+    import torch
+    from pawsometracker_jl_amd import _args
+    frames = torch.zeros((4, 120, 160), dtype=torch.uint8)
+    guesses = torch.ones((4, 2), dtype=torch.int32)
+    fi = torch.zeros(4, dtype=torch.int32)
+    hw = (120, 160)
+    cases = [
+        (TypeError, lambda: _args.device_frames(frames, "frames", 3, hw)),                                  # a CPU tensor
+        (TypeError, lambda: _args.device_array(guesses, "guesses", torch.int32, (None, 2))),
+        (TypeError, lambda: _args.frame_index_ptr(fi, 4)),
+        (TypeError, lambda: _args.device_frames(frames.numpy(), "frames", 3, hw)),                          # no tensor at all
+        (TypeError, lambda: _args.device_frames(frames.float(), "frames", 3, hw)),                          # wrong dtype
+        (TypeError, lambda: _args.device_array(guesses.long(), "guesses", torch.int32, (None, 2))),
+        (TypeError, lambda: _args.frame_index_ptr(fi.long(), 4)),
+        (TypeError, lambda: _args.device_frames(frames[0], "frames", 3, hw)),                               # wrong rank
+        (TypeError, lambda: _args.device_frames(frames, "frames", 4, hw)),
+        (TypeError, lambda: _args.device_array(guesses.flatten(), "guesses", torch.int32, (None, 2))),
+        (ValueError, lambda: _args.device_frames(frames[:, :, ::2], "frames", 3, (120, 80))),               # last stride 2
+        (ValueError, lambda: _args.device_array(torch.ones((4, 4), dtype=torch.int32)[:, :2], "guesses", torch.int32, (None, 2))),  # rows 4 apart
+        (ValueError, lambda: _args.device_array(torch.ones((2, 4), dtype=torch.int32).t(), "guesses", torch.int32, (4, 2))),
+        (ValueError, lambda: _args.device_frames(frames, "frames", 3, (120, 161))),                         # a frame of another size
+        (ValueError, lambda: _args.device_frames(frames[:, :100], "frames", 3, hw)),
+        (ValueError, lambda: _args.device_frames(frames.view(2, 2, 120, 160)[:, :1], "frames", 4, hw)),     # clips not stacked contiguously
+        (ValueError, lambda: _args.device_array(guesses, "guesses", torch.int32, (None, 3))),               # wrong shape
+        (ValueError, lambda: _args.frame_index_ptr(fi[:3], 4)),                                             # frame index of the wrong length
+        (ValueError, lambda: _args.host_i32([1, 2, 3], "fills", 4)),
+        (ValueError, lambda: _args.host_i32(np.zeros((4, 1)), "lengths", 4)),
+    ]
+    for k, (exc, call) in enumerate(cases):
+        with pytest.raises(exc) as e:
+            call()
+        assert type(e.value) is exc, (k, e.value)
+        assert re.search(r"frames|guesses|frame_index|fills|lengths", str(e.value)), (k, e.value)
+    assert _args.frame_index_ptr(None, 4) is None and _args.host_i32(None, "fills", 4) is None
+    a = _args.host_i32(torch.tensor([3, 1, 2, 0]), "lengths", 4)
+    assert a.dtype == np.int32 and a.flags.c_contiguous and a.tolist() == [3, 1, 2, 0]
+    # the strided views the kernels do accept pass every check but the device's
+    for ok in (frames[:, :, :], torch.zeros((4, 120, 200), dtype=torch.uint8)[:, :, 20:180], frames[::2]):
+        with pytest.raises(TypeError, match="must live on the GPU"):
+            _args.device_frames(ok, "frames", 3, hw)
+
+
+def test_argument_helpers_survive_python_O():
+    """`python -O` strips every assert: the checks are raised, so a CPU tensor or a wrong dtype is still refused there.  The child
+    imports the package and calls the helpers; it opens no GPU."""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import torch\n"
+            "from pawsometracker_jl_amd import _args\n"
+            "frames = torch.zeros((4, 120, 160), dtype=torch.uint8)\n"
+            "guesses = torch.ones((4, 2), dtype=torch.int32)\n"
+            "got = [str(__debug__)]\n"
+            "for call in (lambda: _args.device_frames(frames, 'frames', 3, (120, 160)),\n"
+            "             lambda: _args.device_array(guesses, 'guesses', torch.int32, (None, 2)),\n"
+            "             lambda: _args.device_frames(frames.float(), 'frames', 3, (120, 160)),\n"
+            "             lambda: _args.device_array(guesses.long(), 'guesses', torch.int32, (None, 2))):\n"
+            "    try:\n"
+            "        call()\n"
+            "        got.append('accepted')\n"
+            "    except Exception as e:\n"
+            "        got.append(type(e).__name__)\n"
+            "print(' '.join(got))\n" % ROOT)
+    p = subprocess.run([sys.executable, "-O", "-c", code], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.split() == ["False"] + ["TypeError"] * 4, p.stdout
