@@ -390,4 +390,11 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- chains over a frame table: start, stop, fps, several targets per video ----
+ * The time axis of src/PawsomeTracker.jl:150-152, the frames its ffmpeg line (:155) selects from a stack that is already
+ * in device memory, and the chain (:163-169) over such a table of frame indices are declared in pawsome_video.h, which
+ * is part of this ABI and of this header. */
+#include "pawsome_video.h"
+
 #endif /* PAWSOME_DOG_H */

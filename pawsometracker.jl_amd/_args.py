@@ -59,3 +59,18 @@ def host_i32(v, name, n):
     if a.shape != (n,):
         raise ValueError(f"{name}: {n} values expected, one per entry, not shape {a.shape}")
     return a
+
+
+def host_table(v, name):
+    """A frame table — a sequence of rows, a numpy array or a tensor of integers [n_clips, n_steps] — as a contiguous host int32
+    array.  Its entries are the library's to judge (it validates them before it launches anything)."""
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{name} must hold integers, not {a.dtype}")
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"{name}: shape {a.shape}, expected (n_clips, n_steps)")
+    if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+        raise ValueError(f"{name}: entries beyond int32")
+    return np.ascontiguousarray(a, dtype=np.int32)

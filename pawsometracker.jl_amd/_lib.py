@@ -88,6 +88,17 @@ PROTOTYPES = {
 }
 SYMBOLS = tuple(PROTOTYPES)
 
+# the same for include/pawsome_video.h, which pawsome_dog.h includes: chains over a frame table (tests/test_video_cpu.py
+# holds this table against that header)
+VIDEO_PROTOTYPES = {
+    "pdog_time_axis": (_i, [_d, _d, _d, _p, _i, _pi]),
+    "pdog_fps_table": (_i, [_d, _i, _d, _d, _d, _p, _i, _pi]),
+    "pdog_detect_chains_indexed": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _i, _i, _p, _p]),
+    "pdog_clips_track_indexed": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _i, _p, _i, _p, _p]),
+}
+VIDEO_SYMBOLS = tuple(VIDEO_PROTOTYPES)
+DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
+
 
 class PdogError(RuntimeError):
     def __init__(self, code, msg):
@@ -130,7 +141,7 @@ def lib():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

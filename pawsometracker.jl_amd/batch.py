@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, frame_index_ptr, host_i32
+from ._args import device_array, device_frames, frame_index_ptr, host_i32, host_table
 
 
 class BatchTracker(_lib.TrackerHandle):
@@ -116,6 +116,29 @@ class BatchTracker(_lib.TrackerHandle):
                                                  nf, nc, C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
+    def detect_chains_indexed(self, frames, frame_table, start_guesses, first=0, out=None):
+        """Chains over a frame table (pdog_detect_chains_indexed): frames uint8 cuda [n_frames, h, w] is ONE stack that every
+        clip shares; frame_table — rows of integers [n_clips, n_steps], host side — names the frame of each step, and a clip
+        ends where its row turns negative; start_guesses int32 cuda [n_clips, 2].  first = 0: out[c][0] = functor(frame
+        table[c][0], start[c]); first = 1: out[c][0] = start[c] as given and the loop starts at step 1
+        (src/PawsomeTracker.jl:161-167).  Several rows may name the same frames (several targets in one video, several
+        start/stop windows of it).  The library checks the table before it launches anything (PdogError, PDOG_E_ARG, for an
+        entry >= n_frames or a non-negative entry behind a negative one).  Returns int32 cuda [n_clips, n_steps, 2]; rows at
+        and beyond a clip's end are not written (a fresh `out` is zeroed)."""
+        import torch
+        self.use_torch_stream()
+        device_frames(frames, "frames", 3, self._hw)
+        table = host_table(frame_table, "frame_table")
+        nc, ns = table.shape
+        device_array(start_guesses, "start_guesses", torch.int32, (nc, 2))
+        if out is None:
+            out = torch.zeros((nc, ns, 2), dtype=torch.int32, device=frames.device)
+        device_array(out, "out", torch.int32, (nc, ns, 2))
+        _lib.check(_lib.lib().pdog_detect_chains_indexed(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
+            C.c_void_p(table.ctypes.data), ns, nc, int(first), C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
     def measure(self, frames, ij, frame_index=None, want_resp=False):
         """Sub-pixel positions (and peak responses) at tracked points (pdog_measure).  frames: uint8 cuda tensor
         [nf, h, w] (row stride may exceed w); ij: int32 cuda [n, 2], 1-based (row, col) — what detect / detect_chain
@@ -193,6 +216,28 @@ class BatchTracker(_lib.TrackerHandle):
                                                nf, nc, None if fa is None else C.c_void_p(fa.ctypes.data),
                                                None if la is None else C.c_void_p(la.ctypes.data), int(first),
                                                C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
+    def track_clips_indexed(self, frames, frame_table, starts, fills=None, first=0, out=None):
+        """track_clips over a frame table (pdog_clips_track_indexed): frames uint8 cuda [n_frames, h, w] is one stack that the
+        clips share, frame_table [n_clips, n_steps] names each step's frame as for detect_chains_indexed (a clip ends where
+        its row turns negative: the lengths are the table's), fills holds one value per clip (None: the tracker's fill for
+        all).  Returns int32 cuda [n_clips, n_steps, 2]; rows at and beyond a clip's end are not written (a fresh `out` is
+        zeroed)."""
+        import torch
+        self.use_torch_stream()
+        device_frames(frames, "frames", 3, self._hw)
+        table = host_table(frame_table, "frame_table")
+        nc, ns = table.shape
+        device_array(starts, "starts", torch.int32, (nc, 2))
+        fa = host_i32(fills, "fills", nc)
+        if out is None:
+            out = torch.zeros((nc, ns, 2), dtype=torch.int32, device=frames.device)
+        device_array(out, "out", torch.int32, (nc, ns, 2))
+        _lib.check(_lib.lib().pdog_clips_track_indexed(
+            self._clips_handle(), C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
+            C.c_void_p(table.ctypes.data), ns, nc, None if fa is None else C.c_void_p(fa.ctypes.data), int(first),
+            C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
     def close(self):

@@ -39,6 +39,7 @@ struct FusedGeo {
     int dc_host;           // ≥ 0: the window's DC level, computed by the host from the same sample grid (the functor packs the tile
                            // itself: no sample loads, no reduction barrier); −1: sampled here
 };
+struct FusedTableGeo : FusedGeo { ClipTable tab; }; // clips over a frame table (dog_roll.hpp): n clips of up to chain_len steps
 
 constexpr int FUSED_NT = 1024, FUSED_PMAX = 8, FUSED_U = 8;
 
@@ -202,9 +203,11 @@ __device__ __forceinline__ void fusedc_col_task(const f2 *a, tap_ptr taps, f2 (&
 // (16 floats per frame: shader cycles since the frame's start at 0 samples reduced (wave 0), 4 after the barrier,
 // 1 tile staged, 2 row pass, 5 column pass + wave peak (wave 0), 6 after the barrier, 3 end of frame; then the same
 // in 100 MHz ticks) instead of the response.
-template <bool RESP, int DIAG = 0, int LT = 0>
-__global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const FusedGeo fg, const f2 *__restrict__ taps_row,
-                                                             const f2 *__restrict__ taps_col)
+// TABLE: the instances that walk a frame table.  A template flag and a kernel argument of their own, not a run-time branch:
+// with the branch every instance spilled 8 … 27 more SGPRs, and the existing launches must compile as they did.
+template <bool RESP, int DIAG = 0, int LT = 0, bool TABLE = false>
+__global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditional_t<TABLE, FusedTableGeo, FusedGeo> fg,
+                                                             const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
     const LaunchGeo &g = fg.g;
     constexpr int NT = FUSED_NT, NW = NT / 64, U = FUSED_U;
@@ -246,8 +249,19 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const FusedGeo fg, 
     for (; b < g.n; b += gridDim.x) {
     zero_padding(); // (the previous window may have been refined: the refinement uses this LDS as its scratch)
     int g1 = g.guesses[2 * b], g2 = g.guesses[2 * b + 1];
-    for (int k = 0; k < fg.chain_len; ++k) {
-        const long long fidx = fg.chain_len > 1 ? (long long)b * fg.chain_len + k : (g.frame_index ? g.frame_index[b] : b);
+    const int32_t *table = nullptr;
+    int len = 0, k_first = 0;
+    if constexpr (TABLE) { // (chain_len > 1, the host sees to it)
+        table = fg.tab.index + (long long)b * fg.chain_len;
+        len = fg.tab.len[b];
+        k_first = fg.tab.first;
+        if (k_first && len >= 1 && tid == 0) { // the bootstrap's position, stored as given (:161)
+            fg.out_ij[2 * (long long)b * fg.chain_len] = g1;
+            fg.out_ij[2 * (long long)b * fg.chain_len + 1] = g2;
+        }
+    }
+    for (int k = k_first; k < (TABLE ? len : fg.chain_len); ++k) { // (len: TABLE instances only — the plain ones read fg.chain_len where they did)
+        const long long fidx = TABLE ? (long long)table[k] : fg.chain_len > 1 ? (long long)b * fg.chain_len + k : (g.frame_index ? g.frame_index[b] : b);
         const uint8_t *__restrict__ frame = g.frames + fidx * g.frame_stride;
         const int ti0 = g1 - g.r1 - 1 - hw, wj0 = g2 - g.r2 - 1 - hw;
         unsigned long long dc0 = 0, dr0 = 0;
@@ -479,7 +493,7 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const FusedGeo fg, 
         stamp(5);
         __syncthreads();
         stamp(6);
-        const bool publish = fg.done_flag && b == 0 && (fg.progress || k == fg.chain_len - 1);
+        const bool publish = fg.done_flag && b == 0 && (fg.progress || k == (TABLE ? len : fg.chain_len) - 1);
         int32_t *const o_ij = fg.out_ij + 2 * ((long long)b * fg.chain_len + k);
         if (wave == 0) { // the 16 wave peaks: lanes 0..15 of wave 0, same tie rule
             peak_init(pk);
@@ -495,7 +509,7 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const FusedGeo fg, 
                 o_ij[1] = j;
                 s_guess[0] = i;
                 s_guess[1] = j;
-                if (k == 0) range_check(g.ex, g1, g2, hw, g.fh, g.fw);
+                if (k == k_first) range_check(g.ex, g1, g2, hw, g.fh, g.fw);
                 // exact mode (dog_exact.hpp): a runner-up within 2δ of the maximum → the reference's own arithmetic decides
                 const bool rf = fg.rp && (pk.best - pk.second <= g.ex.T);
                 s_refine = rf;
@@ -581,7 +595,7 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const FusedGeo fg, 
                     __hip_atomic_store(fg.done_flag, fg.progress ? k + 1 : fg.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             __syncthreads();
-            if (k + 1 < fg.chain_len) { zero_padding(); }
+            if (k + 1 < (TABLE ? len : fg.chain_len)) { zero_padding(); }
         }
         stamp(3);
         g1 = s_guess[0];   // :167 — the next frame's guess

@@ -578,9 +578,21 @@ struct ChainGeo {
     int *__restrict__ out_ij;            // n_clips x n_frames x 2
     int n_frames;                        // per clip; clip c's frame k is frame c*n_frames + k
 };
-template <int LT>
-__global__ __launch_bounds__(512) void dog_chain_kernel(const ChainGeo cg, const f2 *__restrict__ taps_row,
-                                                        const f2 *__restrict__ taps_col)
+// A frame table for the kernels that walk a clip themselves (pdog_detect_chains_indexed): step k of clip c looks at frame
+// index[c*n_steps + k] of ONE stack, for k < len[c] — checked on the host before the launch, so every entry a kernel reads
+// names a frame of the stack.  Every workgroup (wave) of a clip reads the same len[c] and leaves the frame loop with the others.
+struct ClipTable {
+    const int32_t *index; // [n_clips][n_steps]
+    const int32_t *len;   // [n_clips] steps of each clip: the count of its row's leading non-negative entries
+    int first;            // 1: row 0 of a clip that has one receives its start guess as given, the loop begins at step 1 (:104, :161)
+};
+struct ChainTableGeo : ChainGeo { ClipTable tab; };
+// TABLE: the instances that walk a frame table.  A template flag and a kernel argument of their own, not a run-time branch
+// on a wider ChainGeo: the existing instances compile exactly as before (the branch cost them SGPR spills, the wider
+// argument 16 bytes of scratch).
+template <int LT, bool TABLE = false>
+__global__ __launch_bounds__(512) void dog_chain_kernel(const std::conditional_t<TABLE, ChainTableGeo, ChainGeo> cg,
+                                                        const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int cur[2];
@@ -593,15 +605,27 @@ __global__ __launch_bounds__(512) void dog_chain_kernel(const ChainGeo cg, const
     const LaunchGeo &g = cg.g;
     const int tid = threadIdx.x, wave = tid >> 6, nst = blockDim.x >> 6;
     const int c_ = blockIdx.x;
+    const int32_t *table = nullptr;
+    int len = 0, k_first = 0;
+    if constexpr (TABLE) {
+        table = cg.tab.index + (long long)c_ * cg.n_frames;
+        len = cg.tab.len[c_];
+        k_first = cg.tab.first;
+    }
     if (tid == 0) {
         cur[0] = cg.start[2 * c_];
         cur[1] = cg.start[2 * c_ + 1];
-        range_check(g.ex, cur[0], cur[1], LT / 2, g.fh, g.fw);
+        if (!TABLE || len > k_first) range_check(g.ex, cur[0], cur[1], LT / 2, g.fh, g.fw); // (a start that no step uses raises nothing)
+        if (k_first && len >= 1) { // the bootstrap's position, stored as given (:161)
+            cg.out_ij[2 * (long long)c_ * cg.n_frames] = cur[0];
+            cg.out_ij[2 * (long long)c_ * cg.n_frames + 1] = cur[1];
+        }
     }
     __syncthreads();
-    for (int k = 0; k < cg.n_frames; ++k) {
+    for (int k = k_first; k < (TABLE ? len : cg.n_frames); ++k) { // (len: TABLE instances only — the plain ones read cg.n_frames where they did)
         const int g1 = cur[0], g2 = cur[1];
-        const uint8_t *__restrict__ frame = g.frames + ((long long)c_ * cg.n_frames + k) * g.frame_stride;
+        const long long fidx = TABLE ? (long long)table[k] : (long long)c_ * cg.n_frames + k;
+        const uint8_t *__restrict__ frame = g.frames + fidx * g.frame_stride;
         Peak pk;
         unsigned long long mask;
         roll_strip_call<LT>(&g, taps_row, taps_col, smem + wave * roll_lds_bytes(LT), frame, g1, g2, wave, 0, &pk, &mask);
@@ -675,6 +699,36 @@ static __global__ void dog_chain_step_kernel(const int *__restrict__ step_ij, in
     const int i = step_ij[2 * c], j = step_ij[2 * c + 1];
     out_ij[2 * ((long long)c * n_frames + k)] = i;
     out_ij[2 * ((long long)c * n_frames + k) + 1] = j;
+    cur[2 * c] = i;
+    cur[2 * c + 1] = j;
+}
+
+// The same for chains over a frame table run as ordinary batches (pdog_detect_chains_indexed): clip c has len[c] steps.
+// Before the first step: a clip with a step to compute starts from its start guess, any other from (1, 1) — its window is
+// still part of every batch, its result is never stored, and a start that no step uses must raise nothing; with first = 1
+// row 0 of a clip that has one receives the start as given (src/PawsomeTracker.jl:104, :161).
+static __global__ void dog_chain_table_init_kernel(const int *__restrict__ start, const int *__restrict__ len, int *__restrict__ cur,
+                                                   int *__restrict__ out_ij, int n_clips, int n_steps, int first)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_clips) return;
+    const int i = start[2 * c], j = start[2 * c + 1], n = len[c];
+    cur[2 * c] = n > first ? i : 1;
+    cur[2 * c + 1] = n > first ? j : 1;
+    if (first && n >= 1) {
+        out_ij[2 * (long long)c * n_steps] = i;
+        out_ij[2 * (long long)c * n_steps + 1] = j;
+    }
+}
+// After step k: a clip that has ended takes no part in the stored result and keeps its last guess.
+static __global__ void dog_chain_table_step_kernel(const int *__restrict__ step_ij, const int *__restrict__ len, int *__restrict__ cur,
+                                                   int *__restrict__ out_ij, int n_clips, int n_steps, int k)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_clips || k >= len[c]) return;
+    const int i = step_ij[2 * c], j = step_ij[2 * c + 1];
+    out_ij[2 * ((long long)c * n_steps + k)] = i;
+    out_ij[2 * ((long long)c * n_steps + k) + 1] = j;
     cur[2 * c] = i;
     cur[2 * c + 1] = j;
 }

@@ -48,13 +48,15 @@ struct TiledGeo {
     unsigned tag_base;      // chains: frame k's partials carry the tag tag_base + k + 1; the host advances it by chain_len + 1 per launch
     int fault_inject;       // tests: sub-window 0 of clip 0 never delivers the partial of its second frame (pdog_set_tuning "fault_inject")
 };
+struct TiledTableGeo : TiledGeo { ClipTable tab; }; // clips over a frame table (dog_roll.hpp): n clips of up to chain_len steps
 
 constexpr int TILED_SLOT_CAP = 256; // sub-windows per window the combining wave handles (4 per lane)
 
 // LT > 0: the compile-time-l tasks and tile layout of dog_fused.hpp (fusedc_*), same values bit for bit.
-template <bool RESP, int LT = 0>
-__global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const TiledGeo tg, const f2 *__restrict__ taps_row,
-                                                             const f2 *__restrict__ taps_col)
+// TABLE: the instances that walk a frame table — a template flag and a kernel argument of their own, for the reason given in dog_fused.hpp.
+template <bool RESP, int LT = 0, bool TABLE = false>
+__global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const std::conditional_t<TABLE, TiledTableGeo, TiledGeo> tg,
+                                                             const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
     const LaunchGeo &g = tg.g;
     constexpr int NT = FUSED_NT, NW = NT / 64, U = FUSED_U;
@@ -126,8 +128,20 @@ __global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const TiledGeo tg, 
     };
 
     int g1 = g.guesses[2 * clip], g2 = g.guesses[2 * clip + 1];
-    for (int k = 0; k < tg.chain_len; ++k) {
-        const long long fidx = tg.chain_len > 1 ? (long long)clip * tg.chain_len + k : (g.frame_index ? g.frame_index[clip] : clip);
+    // a clip over a frame table: its own number of steps, counted by k like the frame tags and the slot parity
+    const int32_t *table = nullptr;
+    int len = 0, k_first = 0; // (len: TABLE instances only — the plain ones read tg.chain_len where they did)
+    if constexpr (TABLE) {
+        table = tg.tab.index + (long long)clip * tg.chain_len;
+        len = tg.tab.len[clip];
+        k_first = tg.tab.first;
+        if (k_first && len >= 1 && s == 0 && tid == 0) { // the bootstrap's position, stored as given (:161)
+            tg.out_ij[2 * (long long)clip * tg.chain_len] = g1;
+            tg.out_ij[2 * (long long)clip * tg.chain_len + 1] = g2;
+        }
+    }
+    for (int k = k_first; k < (TABLE ? len : tg.chain_len); ++k) {
+        const long long fidx = TABLE ? (long long)table[k] : tg.chain_len > 1 ? (long long)clip * tg.chain_len + k : (g.frame_index ? g.frame_index[clip] : clip);
         const uint8_t *__restrict__ frame = g.frames + fidx * g.frame_stride;
         const int wi0 = g1 - g.r1 - 1 - hw, wj0 = g2 - g.r2 - 1 - hw; // the full window's tile origin
         const int ti0 = wi0 + sy, tj0 = wj0 + sx;                     // this sub-window's
@@ -284,9 +298,9 @@ __global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const TiledGeo tg, 
         // frame ahead of the slowest reader).  Independent windows: the LAST arrival combines them.  Clips: EVERY
         // workgroup polls the partials and combines for itself — the same values in the same order give the same answer
         // everywhere; only sub-window 0's workgroup writes the answer out, and only a refinement (rare) goes through the frame flag. ----
-        const bool chain = k + 1 < tg.chain_len; // (the clip's last frame has no successor to wait for: the last arrival alone combines it)
+        const bool chain = k + 1 < (TABLE ? len : tg.chain_len); // (the clip's last frame has no successor to wait for: the last arrival alone combines it)
         const int par = (k & 1) * nsub;
-        const bool publish = tg.done_flag && clip == 0 && (tg.progress || k == tg.chain_len - 1);
+        const bool publish = tg.done_flag && clip == 0 && (tg.progress || k == (TABLE ? len : tg.chain_len) - 1);
         int32_t *const o_ij = tg.out_ij + 2 * ((long long)clip * tg.chain_len + k);
         if (wave == 0) {
             peak_init(pk);
@@ -368,8 +382,8 @@ __global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const TiledGeo tg, 
                     s_idx[0] = i; // (the wave peaks have been consumed: the next guess travels through their slots)
                     s_idx[1] = j;
                     if (last) {
-                        if (k == 0) range_check(g.ex, g1, g2, hw, g.fh, g.fw);
-                        if (k == tg.chain_len - 1) { // nobody looks at the arrival count or the frame flag any more: zero for the next launch
+                        if (k == k_first) range_check(g.ex, g1, g2, hw, g.fh, g.fw);
+                        if (k == (TABLE ? len : tg.chain_len) - 1) { // nobody looks at the arrival count or the frame flag any more: zero for the next launch
                             if (tg.chain_len == 1) __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (clips never count arrivals)
                             __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         }
@@ -495,12 +509,12 @@ __global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const TiledGeo tg, 
                         __threadfence_system();
                         __hip_atomic_store(tg.done_flag, tg.progress ? k + 1 : tg.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
                     }
-                    __hip_atomic_store(flag, k + 1 < tg.chain_len ? (unsigned)(k + 1) : 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); // (0 again after the last frame)
+                    __hip_atomic_store(flag, k + 1 < (TABLE ? len : tg.chain_len) ? (unsigned)(k + 1) : 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); // (0 again after the last frame)
                 }
                 __syncthreads();
-                if (k + 1 < tg.chain_len) zero_padding();
+                if (k + 1 < (TABLE ? len : tg.chain_len)) zero_padding();
             }
-            if (k + 1 < tg.chain_len) { // the refined answer is the next guess (:167): it comes through the frame flag
+            if (k + 1 < (TABLE ? len : tg.chain_len)) { // the refined answer is the next guess (:167): it comes through the frame flag
                 if (tid == 0) {
                     if (!wait_counter(flag, (unsigned)(k + 1), g.ex, tg.abort)) s_abort = 1;
                     s_idx[0] = __hip_atomic_load(&cur[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -510,7 +524,7 @@ __global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const TiledGeo tg, 
                 if (s_abort) break;
             }
         }
-        if (k + 1 < tg.chain_len) { // :167
+        if (k + 1 < (TABLE ? len : tg.chain_len)) { // :167
             g1 = s_idx[0];
             g2 = s_idx[1];
             __syncthreads();

@@ -11,4 +11,7 @@ template __global__ void dog_fused_kernel<false, 0, PDOG_LAT_L>(const FusedGeo, 
 template __global__ void dog_fused_kernel<true, 0, PDOG_LAT_L>(const FusedGeo, const f2 *, const f2 *);
 template __global__ void dog_tiled_kernel<false, PDOG_LAT_L>(const TiledGeo, const f2 *, const f2 *);
 template __global__ void dog_tiled_kernel<true, PDOG_LAT_L>(const TiledGeo, const f2 *, const f2 *);
+// chains over a frame table (no response map: a chain has none)
+template __global__ void dog_fused_kernel<false, 0, PDOG_LAT_L, true>(const FusedTableGeo, const f2 *, const f2 *);
+template __global__ void dog_tiled_kernel<false, PDOG_LAT_L, true>(const TiledTableGeo, const f2 *, const f2 *);
 } // namespace pdog

@@ -36,7 +36,9 @@ namespace pdog {
     extern template __global__ void dog_fused_kernel<false, 0, LT>(const FusedGeo, const f2 *, const f2 *);    \
     extern template __global__ void dog_fused_kernel<true, 0, LT>(const FusedGeo, const f2 *, const f2 *);     \
     extern template __global__ void dog_tiled_kernel<false, LT>(const TiledGeo, const f2 *, const f2 *);       \
-    extern template __global__ void dog_tiled_kernel<true, LT>(const TiledGeo, const f2 *, const f2 *);
+    extern template __global__ void dog_tiled_kernel<true, LT>(const TiledGeo, const f2 *, const f2 *);        \
+    extern template __global__ void dog_fused_kernel<false, 0, LT, true>(const FusedTableGeo, const f2 *, const f2 *); \
+    extern template __global__ void dog_tiled_kernel<false, LT, true>(const TiledTableGeo, const f2 *, const f2 *);
 #include "lat_lengths.def"
 #undef PDOG_LAT_L
 } // namespace pdog
@@ -48,7 +50,8 @@ namespace pdog {
     extern template __global__ void dog_roll_kernel<LT, true, 0>(const LaunchGeo, const f2 *, const f2 *);       \
     extern template __global__ void dog_thin_kernel<LT, false>(const LaunchGeo, const f2 *, const f2 *);         \
     extern template __global__ void dog_thin_kernel<LT, true>(const LaunchGeo, const f2 *, const f2 *);          \
-    extern template __global__ void dog_chain_kernel<LT>(const ChainGeo, const f2 *, const f2 *);
+    extern template __global__ void dog_chain_kernel<LT>(const ChainGeo, const f2 *, const f2 *);                \
+    extern template __global__ void dog_chain_kernel<LT, true>(const ChainTableGeo, const f2 *, const f2 *);
 #include "roll_lengths.def"
 #undef PDOG_ROLL_L
 #define PDOG_EPI_CLASSES(X) X(10) X(2) X(16) X(14) X(6) X(4) X(0) X(1) X(3) X(5) X(7) X(8) X(9) X(11) X(12) X(13) X(15) X(17) // roll_inst.hip: every window-height class
@@ -165,6 +168,8 @@ struct Variant {
     int twopass = 0;           // dog_twopass.hpp: vertical pass → HBM → horizontal pass (Q = this value)
     typedef void (*chain_fn)(const ChainGeo, const f2 *, const f2 *);
     chain_fn chain = nullptr;  // persistent serial-chain kernel of the roll variants
+    typedef void (*chain_table_fn)(const ChainTableGeo, const f2 *, const f2 *);
+    chain_table_fn chain_table = nullptr; // … its instance that walks a frame table
     bool fused = false;        // dog_fused.hpp: one workgroup per window, whole tile in LDS
     int tw() const { return P * XG; }
     int ring(int L) const { return LT ? ring_rows(CH, LT, Q) : ring_rows(CH, L, Q); }
@@ -182,7 +187,7 @@ struct Variant {
 #define PDOG_ROLL_VARIANT(id, LT) \
     Variant { id, ROLL_P, ROLL_TW / ROLL_P, ROLL_CH, ROLL_CH, LT, 64, (kernel_fn)dog_roll_kernel<LT, false>, \
               (kernel_fn)dog_roll_kernel<LT, true>, true, (kernel_fn)dog_thin_kernel<LT, false>, \
-              (kernel_fn)dog_thin_kernel<LT, true>, 0, dog_chain_kernel<LT> }
+              (kernel_fn)dog_thin_kernel<LT, true>, 0, dog_chain_kernel<LT>, dog_chain_kernel<LT, true> }
 
 const Variant kVariants[] = {
     // runtime-L (any target_width)
@@ -202,7 +207,7 @@ const Variant kVariants[] = {
     // any l: two launches with the intermediate in HBM (long kernels, target_width ≳ 40)
     Variant { kPathTwoPass, 13, 16, 16, 16, 0, 256, nullptr, nullptr, false, nullptr, nullptr, 16 },
     // any l, windows whose padded tile fits in LDS: one workgroup per window, one launch (latency path)
-    Variant { kPathFused, 1, 1, 1, 1, 0, FUSED_NT, nullptr, nullptr, false, nullptr, nullptr, 0, nullptr, true },
+    Variant { kPathFused, 1, 1, 1, 1, 0, FUSED_NT, nullptr, nullptr, false, nullptr, nullptr, 0, nullptr, nullptr, true },
 #ifdef PDOG_ABLATIONS
     Variant { 101, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 1>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
     Variant { 102, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 2>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
@@ -250,6 +255,13 @@ struct pdog_tracker {
     bool fused_c = false;          // … through its compile-time-l instance (dog_fused.hpp: l = 65, the default tracker's), whose tile layout is wider
     int hp_rows = HP_ROWS;         // RT rows (window columns) per column-pass workgroup: 16 (P = 13) or 8 (P = 7)
     DeviceBuffer<int32_t> d_chain_tmp; // [2][n_clips][2]: current guesses / step results of multi-clip chains
+    // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it, packed in
+    // pinned staging and uploaded on the stream; grow-only, like pdog_clips::h_plan / ev_upload
+    PinnedBuffer<int32_t> h_table;
+    DeviceBuffer<int32_t> d_table;
+    hipEvent_t ev_table = nullptr;     // the last upload has left h_table
+    bool table_pending = false;
+    std::vector<int32_t> table_len;    // steps per clip of the table being served
     int tp_ph1 = 13, tp_php = 7;   // outputs per task of the two-pass row / column pass (pick_twopass_p)
     // tiled kernel (dog_tiled.hpp): one large window cut into sub-windows, a workgroup each, one launch per batch / clip
     bool tiled_ok = false;
@@ -327,7 +339,7 @@ struct pdog_tracker {
         for (int k = 0; k < kIngestSlots; ++k)
             for (hipEvent_t e : {ev_h2d[k], ev_used[k]})
                 if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_fork, ev_join, ev_switch})
+        for (hipEvent_t e : {ev_fork, ev_join, ev_switch, ev_table})
             if (e) (void)hipEventDestroy(e);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -337,6 +349,8 @@ namespace {
 
 typedef void (*fused_fn_t)(const FusedGeo, const f2 *, const f2 *);
 fused_fn_t fused_kernel_for(const pdog_tracker *t, bool resp);
+typedef void (*fused_table_fn_t)(const FusedTableGeo, const f2 *, const f2 *);
+fused_table_fn_t fused_table_kernel_for(const pdog_tracker *t); // the instance that walks a frame table (no response map: a chain has none)
 
 // LDS row pitches of the two-pass kernels: the sliding windows (and their one-block prefetch) of the last,
 // partly masked group of 13 outputs must stay inside the zero-padded row.  nout outputs, l taps.
@@ -470,6 +484,16 @@ int pick_outputs_per_task(int lines, int nout, std::initializer_list<int> ps, do
 
 // Tiled kernel (dog_tiled.hpp): windows too large for the fused kernel, cut into sub-windows of ≈48 rows/columns (a
 // 257×257 window: 6×6 of 43×43, each a tile of 107×107 like the default 45×45 window of the fused kernel).
+const void *tiled_table_kernel_for(const pdog_tracker *t) // the instance that walks a frame table (no response map: a chain has none)
+{
+    if (t->tiled_c) switch (t->L) {
+#define PDOG_LAT_L(LT) case LT: return (const void *)dog_tiled_kernel<false, LT, true>;
+#include "lat_lengths.def"
+#undef PDOG_LAT_L
+        default: break;
+    }
+    return (const void *)dog_tiled_kernel<false, 0, true>;
+}
 const void *tiled_kernel_for(const pdog_tracker *t, bool resp)
 {
     if (t->tiled_c) switch (t->L) {
@@ -538,6 +562,7 @@ int setup_tiled(pdog_tracker *t)
     t->tiled_pc = pick_outputs_per_task(sn2, sn1, {2, 3, 4, 6, 8}, 1.5);
     for (bool resp : {false, true})
         if (int rc = raise_lds_limit(tiled_kernel_for(t, resp), base)) return rc;
+    if (int rc = raise_lds_limit(tiled_table_kernel_for(t), base)) return rc;
     int per_cu = 0, cus = 0, coop = 0;
     t->tiled_resident = 0; // chains need every workgroup of a clip resident at once: a cooperative launch, if the device has them
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, t->device) == hipSuccess && coop &&
@@ -554,6 +579,7 @@ struct Request {
     const uint8_t *frames = nullptr;
     int64_t frame_stride = 0, row_stride = 0;
     const int32_t *frame_index = nullptr;  // may stay null: window b looks at frame b
+    ClipTable table{nullptr, nullptr, 0};  // chains over a frame table (index non-null): the kernels that walk a clip read it themselves
     const int32_t *guesses = nullptr;      // n x 2 (chains: the clips' start guesses)
     int n = 0;                             // windows, or clips of chain_len frames
     int chain_len = 1;
@@ -603,7 +629,7 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
     if (int rc = ensure_capacity(t, n)) return rc;
     // the kernel leaves its counters at zero; the last word is the abort word
     if (int rc = t->d_tiled_ctl.reserve(4 * (size_t)n + 1, &t->stream, true)) return rc;
-    TiledGeo tg;
+    TiledTableGeo tg; // (an ordinary launch takes its TiledGeo part)
     std::memset(&tg, 0, sizeof tg);
     LaunchGeo &g = tg.g;
     g = base_geo(t, req);
@@ -631,6 +657,7 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
     tg.sync = reinterpret_cast<unsigned *>(t->d_tiled_ctl.get() + 2 * (size_t)t->tiled_ctl_cap());
     tg.abort = reinterpret_cast<unsigned *>(t->d_tiled_ctl.get() + 4 * (size_t)t->tiled_ctl_cap());
     tg.fault_inject = t->sw.fault_inject ? 1 : 0;
+    tg.tab = req.table;
     tg.slots = nullptr;
     tg.tag_base = 0;
     if (chain_len > 1) {
@@ -639,7 +666,7 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
         tg.tag_base = t->tiled_tag;
         t->tiled_tag += (unsigned)chain_len + 1u;
     }
-    const void *fn = tiled_kernel_for(t, req.out_resp != nullptr);
+    const void *fn = req.table.index ? tiled_table_kernel_for(t) : tiled_kernel_for(t, req.out_resp != nullptr);
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
     if (chain_len > 1) {
         void *args[] = {(void *)&tg, (void *)&tr, (void *)&tc};
@@ -647,7 +674,7 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
         if (e != hipSuccess) { (void)hipGetLastError(); return PDOG_OK; } // refused: the caller's other paths
     } else {
         typedef void (*tiled_fn_t)(const TiledGeo, const f2 *, const f2 *);
-        hipLaunchKernelGGL((tiled_fn_t)fn, dim3(n * nsub), dim3(FUSED_NT), t->tiled_lds, t->stream, tg, tr, tc);
+        hipLaunchKernelGGL((tiled_fn_t)fn, dim3(n * nsub), dim3(FUSED_NT), t->tiled_lds, t->stream, static_cast<const TiledGeo &>(tg), tr, tc);
         HIP_TRY(hipGetLastError());
     }
     *launched = true;
@@ -704,6 +731,7 @@ int choose_variant(pdog_tracker *t, int forced)
         for (bool resp : {false, true}) {
             if (int rc = raise_lds_limit((const void *)fused_kernel_for(t, resp), fused_total_lds(t))) return rc;
         }
+        if (int rc = raise_lds_limit((const void *)fused_table_kernel_for(t), fused_total_lds(t))) return rc;
     }
     if (int rc = setup_tiled(t)) return rc;
     if (best->fused) { t->nstrips = 1; return PDOG_OK; }
@@ -766,6 +794,16 @@ int ensure_capacity(pdog_tracker *t, int n)
 }
 
 // fused-kernel instance (runtime kernel length)
+fused_table_fn_t fused_table_kernel_for(const pdog_tracker *t)
+{
+    if (t->fused_c) switch (t->L) {
+#define PDOG_LAT_L(LT) case LT: return (fused_table_fn_t)dog_fused_kernel<false, 0, LT, true>;
+#include "lat_lengths.def"
+#undef PDOG_LAT_L
+        default: break;
+    }
+    return (fused_table_fn_t)dog_fused_kernel<false, 0, 0, true>;
+}
 fused_fn_t fused_kernel_for(const pdog_tracker *t, bool resp)
 {
     if (t->fused_c) switch (t->L) {
@@ -889,7 +927,8 @@ int launch_finish(pdog_tracker *t, const LaunchGeo &g, const Finish &f)
 int launch_fused(pdog_tracker *t, const Request &req)
 {
     const int n = req.n, chain_len = req.chain_len;
-    FusedGeo fg;
+    FusedTableGeo fg; // (a launch without a table takes its FusedGeo part)
+    fg.tab = req.table;
     fg.g = base_geo(t, req);
     LaunchGeo &g = fg.g;
     g.nstrips = 1; g.nslots = 1; g.nblocks = n;
@@ -957,7 +996,9 @@ int launch_fused(pdog_tracker *t, const Request &req)
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus < 1) cus = 256;
         t->fused_resident = per_cu * cus;
     }
-    hipLaunchKernelGGL(fn, dim3(std::min(n, t->fused_resident)), dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
+    const dim3 grid(std::min(n, t->fused_resident));
+    if (req.table.index) hipLaunchKernelGGL(fused_table_kernel_for(t), grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
+    else hipLaunchKernelGGL(fn, grid, dim3(FUSED_NT), lds, t->stream, static_cast<const FusedGeo &>(fg), tr, tc);
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
 }
@@ -1831,14 +1872,56 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
 
 namespace {
 
+// A validated frame table (pdog_detect_chains_indexed): step k of clip c looks at frame h[c*n_steps + k], clip c has len[c] steps.
+struct ChainTable {
+    const int32_t *h;   // host, n_clips x n_steps
+    const int32_t *len; // host, n_clips
+    int first;          // 1: row 0 receives the start as given, the loop begins at step 1
+    int max_len;
+};
+
+// The table on the device, on the tracker's stream.  by_step = false: rows as given, then the lengths — what the kernels
+// that walk a clip themselves read.  by_step = true: the table transposed (step k's frames of all clips are one batch's
+// frame index), a clip that has ended repeating its last frame (frame 0 if it has none), then the lengths.
+int upload_chain_table(pdog_tracker *t, const ChainTable &ct, int n_clips, int n_steps, bool by_step, const int32_t **d_tab, const int32_t **d_len)
+{
+    const size_t cells = (size_t)n_clips * (by_step ? ct.max_len : n_steps), words = cells + (size_t)n_clips;
+    if (!t->ev_table) HIP_TRY(hipEventCreateWithFlags(&t->ev_table, hipEventDisableTiming));
+    if (t->table_pending) HIP_TRY(hipEventSynchronize(t->ev_table)); // the previous call's upload still reads h_table
+    t->table_pending = false;
+    if (int rc = t->h_table.reserve(words, nullptr)) return rc;
+    if (int rc = t->d_table.reserve(words, &t->stream)) return rc;
+    int32_t *hp = t->h_table.get();
+    if (!by_step) std::memcpy(hp, ct.h, sizeof(int32_t) * cells);
+    else
+        for (int c = 0; c < n_clips; ++c) {
+            const int32_t *row = ct.h + (size_t)c * n_steps;
+            for (int k = 0; k < ct.max_len; ++k) hp[(size_t)k * n_clips + c] = k < ct.len[c] ? row[k] : (ct.len[c] ? row[ct.len[c] - 1] : 0);
+        }
+    std::memcpy(hp + cells, ct.len, sizeof(int32_t) * (size_t)n_clips);
+    HIP_TRY(hipMemcpyAsync(t->d_table.get(), hp, sizeof(int32_t) * words, hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipEventRecord(t->ev_table, t->stream));
+    t->table_pending = true;
+    *d_tab = t->d_table.get();
+    *d_len = t->d_table.get() + cells;
+    return PDOG_OK;
+}
+
 // stream-ordered fallback for one clip of req.chain_len frames: frame k's guess is frame k-1's (clamped) answer, read
-// straight from the output array — stream order is the dependency, no host round trip per frame
-int chain_by_launches(pdog_tracker *t, const Request &clip)
+// straight from the output array — stream order is the dependency, no host round trip per frame.  With a table the
+// host names each step's frame itself.
+int chain_by_launches(pdog_tracker *t, const Request &clip, const ChainTable *ct)
 {
     Request req = clip;
     req.n = 1;
     req.chain_len = 1;
-    for (int k = 0; k < clip.chain_len; ++k) {
+    const int len = ct ? ct->len[0] : clip.chain_len, first = ct ? ct->first : 0;
+    if (first && len >= 1) { // the bootstrap's position, stored as given (:161); step 1 starts from the caller's copy of it
+        HIP_TRY(hipMemcpyAsync(req.out_ij, clip.guesses, sizeof(int32_t) * 2, hipMemcpyDeviceToDevice, t->stream));
+        req.out_ij += 2;
+    }
+    for (int k = first; k < len; ++k) {
+        if (ct) req.frames = clip.frames + (int64_t)ct->h[k] * clip.frame_stride;
         if (int rc = launch_detect(t, req)) return rc;
         req.frames += clip.frame_stride;
         req.guesses = req.out_ij;
@@ -1847,15 +1930,10 @@ int chain_by_launches(pdog_tracker *t, const Request &clip)
     return PDOG_OK;
 }
 
-} // namespace
-
-extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
-                                  int n_frames, int n_clips, const int32_t *d_start_guesses, int32_t *d_out_ij)
+// n_clips clips of n_steps frames each: contiguous (ct null: clip c's frame k is frame c*n_steps + k) or over a table.
+int run_chains(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride, int n_steps, int n_clips,
+               const int32_t *d_start_guesses, int32_t *d_out_ij, const ChainTable *ct)
 {
-    if (!t || !d_frames || !d_start_guesses || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chains: null pointer");
-    if (n_frames <= 0 || n_clips <= 0 || row_stride < t->fw || frame_stride < 0)
-        return fail(PDOG_E_ARG, "pdog_detect_chains: bad size/stride");
-    HIP_TRY(hipSetDevice(t->device));
     const Variant &v = *t->var;
     const int chain_strips = (t->n2 + ROLL_TW - 1) / ROLL_TW;
     // Enough clips to fill the GPU with one wave per strip → ONE persistent launch (a workgroup per clip walks
@@ -1866,22 +1944,32 @@ extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int6
     const bool fused_wins = t->fused_ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || (long long)n_clips * chain_strips < 1400);
     const bool persistent = v.roll && v.chain && chain_strips <= 8 && !fused_wins &&
                             (t->forced_variant || !t->small_twopass || (long long)n_clips * chain_strips >= 1000);
-    Request req; // n_clips clips of n_frames frames
+    // a table of one step is no chain for the kernels that walk a clip themselves (their chain_len = 1 means independent windows)
+    const bool walkers = !ct || n_steps > 1;
+    Request req; // n_clips clips of n_steps frames
     req.frames = d_frames; req.frame_stride = frame_stride; req.row_stride = row_stride;
-    req.guesses = d_start_guesses; req.n = n_clips; req.chain_len = n_frames;
+    req.guesses = d_start_guesses; req.n = n_clips; req.chain_len = n_steps;
     req.out_ij = d_out_ij;
-    if (t->sw.tiled_force && n_clips == 1 && !t->forced_variant) {
+    if (t->sw.tiled_force && n_clips == 1 && !t->forced_variant && !ct) {
         bool launched = false;
         if (int rc = launch_tiled(t, req, &launched)) return rc;
         if (launched) return PDOG_OK;
     }
-    if (v.fused || (!persistent && !t->forced_variant && t->fused_ok)) // one launch: a workgroup per clip loops over its frames
+    const bool fused = v.fused || (!persistent && !t->forced_variant && t->fused_ok);
+    const bool tiled = !fused && !persistent && !t->forced_variant && t->tiled_ok &&
+                       (long long)n_clips * t->tiled_ns1 * t->tiled_ns2 <= t->tiled_resident; // (what launch_tiled asks of clips)
+    if (ct && walkers && (fused || persistent || tiled)) {
+        if (int rc = upload_chain_table(t, *ct, n_clips, n_steps, false, &req.table.index, &req.table.len)) return rc;
+        req.table.first = ct->first;
+    }
+    if (fused && walkers) // one launch: a workgroup per clip loops over its frames
         return launch_fused(t, req);
-    if (persistent) {
+    if (persistent && walkers) {
         Request frames_only; // (the chain kernel takes its guesses from cg.start)
         frames_only.frames = d_frames; frames_only.frame_stride = frame_stride; frames_only.row_stride = row_stride;
         frames_only.n = n_clips;
-        ChainGeo cg;
+        ChainTableGeo cg; // (a launch without a table takes its ChainGeo part)
+        cg.tab = req.table;
         cg.g = base_geo(t, frames_only);
         LaunchGeo &g = cg.g;
         g.nstrips = chain_strips;
@@ -1889,7 +1977,7 @@ extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int6
         g.nslots = chain_strips;
         cg.start = d_start_guesses;
         cg.out_ij = d_out_ij;
-        cg.n_frames = n_frames;
+        cg.n_frames = n_steps;
         g.ex = exact_ctl(t, kFamRoll);
         cg.rp = t->exact ? t->d_rp.get() : nullptr;
         cg.taps_col_plain = t->d_taps_col.get();
@@ -1908,34 +1996,85 @@ extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int6
             break;
         }
         const size_t lds = base;
-        if (int rc = raise_lds_limit((const void *)v.chain, lds)) return rc;
-        hipLaunchKernelGGL(v.chain, dim3(n_clips), dim3(64 * chain_strips), lds, t->stream, cg,
-                           (const f2 *)t->d_taps_row.get(), (const f2 *)t->d_taps_roll.get());
+        if (int rc = raise_lds_limit(ct ? (const void *)v.chain_table : (const void *)v.chain, lds)) return rc;
+        const f2 *tr = t->d_taps_row.get(), *troll = t->d_taps_roll.get();
+        if (ct) hipLaunchKernelGGL(v.chain_table, dim3(n_clips), dim3(64 * chain_strips), lds, t->stream, cg, tr, troll);
+        else hipLaunchKernelGGL(v.chain, dim3(n_clips), dim3(64 * chain_strips), lds, t->stream, static_cast<const ChainGeo &>(cg), tr, troll);
         HIP_TRY(hipGetLastError());
         return PDOG_OK;
     }
     if (int rc = ensure_capacity(t, n_clips)) return rc;
-    if (!t->forced_variant) { // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that allows)
+    if (!t->forced_variant && walkers) { // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that allows)
         bool launched = false;
         if (int rc = launch_tiled(t, req, &launched)) return rc;
         if (launched) return PDOG_OK;
     }
-    if (n_clips == 1) return chain_by_launches(t, req);
+    req.table = ClipTable{nullptr, nullptr, 0}; // the launches below are independent windows
+    if (n_clips == 1) return chain_by_launches(t, req, ct);
     if (int rc = t->d_chain_tmp.reserve(4 * (size_t)n_clips, &t->stream)) return rc;
     int32_t *cur = t->d_chain_tmp.get(), *step = cur + 2 * (size_t)n_clips;
-    HIP_TRY(hipMemcpyAsync(cur, d_start_guesses, sizeof(int32_t) * 2 * (size_t)n_clips, hipMemcpyDeviceToDevice, t->stream));
-    Request batch; // step k: window c looks at clip c's frame k = frame (c*n_frames + k): a batch whose frame stride is one clip
-    batch.frame_stride = frame_stride * n_frames; batch.row_stride = row_stride;
+    const int blocks = (n_clips + 255) / 256;
+    Request batch;
+    batch.row_stride = row_stride;
     batch.guesses = cur; batch.n = n_clips;
     batch.out_ij = step;
-    for (int k = 0; k < n_frames; ++k) {
+    if (ct) { // step k: window c looks at frame table[c][k] of the shared stack — the batch's frame index is the table's column k
+        const int32_t *d_cols = nullptr, *d_len = nullptr;
+        if (int rc = upload_chain_table(t, *ct, n_clips, n_steps, true, &d_cols, &d_len)) return rc;
+        hipLaunchKernelGGL(dog_chain_table_init_kernel, dim3(blocks), dim3(256), 0, t->stream, d_start_guesses, d_len, cur, d_out_ij,
+                           n_clips, n_steps, ct->first);
+        HIP_TRY(hipGetLastError());
+        batch.frames = d_frames; batch.frame_stride = frame_stride;
+        for (int k = ct->first; k < ct->max_len; ++k) {
+            batch.frame_index = d_cols + (size_t)k * n_clips;
+            if (int rc = launch_detect(t, batch)) return rc;
+            hipLaunchKernelGGL(dog_chain_table_step_kernel, dim3(blocks), dim3(256), 0, t->stream, step, d_len, cur, d_out_ij,
+                               n_clips, n_steps, k);
+            HIP_TRY(hipGetLastError());
+        }
+        return PDOG_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(cur, d_start_guesses, sizeof(int32_t) * 2 * (size_t)n_clips, hipMemcpyDeviceToDevice, t->stream));
+    // step k: window c looks at clip c's frame k = frame (c*n_frames + k): a batch whose frame stride is one clip
+    batch.frame_stride = frame_stride * n_steps;
+    for (int k = 0; k < n_steps; ++k) {
         batch.frames = d_frames + (int64_t)k * frame_stride;
         if (int rc = launch_detect(t, batch)) return rc;
-        hipLaunchKernelGGL(dog_chain_step_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, t->stream, step, cur, d_out_ij,
-                           n_clips, n_frames, k);
+        hipLaunchKernelGGL(dog_chain_step_kernel, dim3(blocks), dim3(256), 0, t->stream, step, cur, d_out_ij,
+                           n_clips, n_steps, k);
         HIP_TRY(hipGetLastError());
     }
     return PDOG_OK;
+}
+
+} // namespace
+
+extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
+                                  int n_frames, int n_clips, const int32_t *d_start_guesses, int32_t *d_out_ij)
+{
+    if (!t || !d_frames || !d_start_guesses || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chains: null pointer");
+    if (n_frames <= 0 || n_clips <= 0 || row_stride < t->fw || frame_stride < 0)
+        return fail(PDOG_E_ARG, "pdog_detect_chains: bad size/stride");
+    HIP_TRY(hipSetDevice(t->device));
+    return run_chains(t, d_frames, frame_stride, row_stride, n_frames, n_clips, d_start_guesses, d_out_ij, nullptr);
+}
+
+// The chain over a frame table (include/pawsome_video.h).  The table is validated here, on the host, before anything is
+// launched: no entry a kernel reads names a frame outside the stack.
+extern "C" int pdog_detect_chains_indexed(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
+                                          int n_frames, const int32_t *h_table, int n_steps, int n_clips, int first,
+                                          const int32_t *d_start, int32_t *d_out_ij)
+{
+    if (!t || !d_frames || !h_table || !d_start || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: null pointer");
+    if (n_frames <= 0 || n_steps <= 0 || n_clips <= 0 || row_stride < t->fw || frame_stride < 0 || (long long)n_clips * n_steps > 0x7fffffffLL)
+        return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: bad size/stride");
+    if (first != 0 && first != 1) return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: first must be 0 or 1");
+    if (t->table_len.size() < (size_t)n_clips) t->table_len.resize((size_t)n_clips);
+    ChainTable ct{h_table, t->table_len.data(), first, 0};
+    if (int rc = chain_table_lengths("pdog_detect_chains_indexed", h_table, n_steps, n_clips, n_frames, t->table_len.data(), &ct.max_len)) return rc;
+    if (ct.max_len == 0) return PDOG_OK; // no clip has a step
+    HIP_TRY(hipSetDevice(t->device));
+    return run_chains(t, d_frames, frame_stride, row_stride, n_steps, n_clips, d_start, d_out_ij, &ct);
 }
 
 extern "C" int pdog_detect_chain(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,

@@ -27,6 +27,10 @@ void gaussian_1d(double s, int l, double *g);                // KernelFactors.ga
 void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, double *K); // :41-43, column-major
 struct ExactFactors { double sym_int, sym_sep, ring, rescan; };
 ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm); // exact mode's FP32 error-bound factors
+// A frame table (include/pawsome_video.h) checked on the host, before anything is launched: every entry below n_frames,
+// negative entries only as the tail of a row.  out_len[c] = steps of clip c (its row's leading non-negative entries),
+// *max_len the longest.  PDOG_E_ARG in `who`'s name, outputs undefined, otherwise.
+int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, int n_clips, int n_frames, int32_t *out_len, int *max_len);
 void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int fill, int L, int r1, int r2, int g1, int g2,
                    uint8_t *dst, int64_t pitch, bool stream = false);
 

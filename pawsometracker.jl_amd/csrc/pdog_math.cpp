@@ -114,6 +114,23 @@ void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int
     if (nt) _mm_sfence(); // the non-temporal stores are globally visible before the caller publishes the tile
 }
 
+int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, int n_clips, int n_frames, int32_t *out_len, int *max_len)
+{
+    *max_len = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        const int32_t *row = h_table + (size_t)c * n_steps;
+        int len = 0;
+        while (len < n_steps && row[len] >= 0) ++len;
+        for (int k = 0; k < n_steps; ++k)
+            if (row[k] >= n_frames || (k > len && row[k] >= 0))
+                return fail(PDOG_E_ARG, std::string(who) + ": entry " + std::to_string(k) + " of clip " + std::to_string(c) +
+                                            (row[k] >= n_frames ? " names a frame outside the stack" : " follows a negative one"));
+        out_len[c] = len;
+        *max_len = std::max(*max_len, len);
+    }
+    return PDOG_OK;
+}
+
 } // namespace pdog
 
 using namespace pdog;
@@ -215,6 +232,62 @@ int pdog_clips_plan(int n_clips, int n_frames, int first, const int32_t *h_fill,
         }
     out_group_start[ng] = n;
     *out_n_groups = ng;
+    return PDOG_OK;
+}
+
+// ---- start, stop, fps as host arithmetic (include/pawsome_video.h) ----
+namespace {
+// n = round(Int, fps * (stop - start)), src/PawsomeTracker.jl:150-151 (nearbyint: ties to even in the default rounding mode)
+int time_axis_len(const char *who, double start, double stop, double fps, int *n)
+{
+    if (!(stop > start) || !(fps > 0.0)) return fail(PDOG_E_ARG, std::string(who) + ": stop <= start or fps <= 0");
+    const double r = std::nearbyint(fps * (stop - start));
+    if (!(r >= 1.0) || r > 2147483647.0) return fail(PDOG_E_ARG, std::string(who) + ": round(fps * (stop - start)) outside 1 ... 2^31 - 1");
+    *n = (int)r;
+    return PDOG_OK;
+}
+} // namespace
+
+int pdog_time_axis(double start, double stop, double fps, double *out_ts, int cap, int *out_n)
+{
+#pragma clang fp contract(off)
+    if (!out_n) return fail(PDOG_E_ARG, "pdog_time_axis: out_n is null");
+    int n = 0;
+    if (int rc = time_axis_len("pdog_time_axis", start, stop, fps, &n)) return rc;
+    if (out_ts) {
+        if (cap < n) return fail(PDOG_E_ARG, "pdog_time_axis: out_ts has room for " + std::to_string(cap) + " of " + std::to_string(n) + " values");
+        out_ts[0] = start; // range(start, stop, 1) is [start]
+        if (n > 1) {
+            const double step = (stop - start) / (double)(n - 1);
+            for (int j = 0; j < n; ++j) out_ts[j] = start + (double)j * step;
+        }
+    }
+    *out_n = n;
+    return PDOG_OK;
+}
+
+int pdog_fps_table(double rate, int n_frames, double start, double stop, double fps, int32_t *out_index, int cap, int *out_n)
+{
+#pragma clang fp contract(off)
+    if (!out_n) return fail(PDOG_E_ARG, "pdog_fps_table: out_n is null");
+    if (!(rate > 0.0) || n_frames <= 0 || !(start >= 0.0)) return fail(PDOG_E_ARG, "pdog_fps_table: rate <= 0, no frames or start < 0");
+    int n = 0;
+    if (int rc = time_axis_len("pdog_fps_table", start, stop, fps, &n)) return rc;
+    const double first = std::ceil(start * rate); // the first frame at or after `start`
+    if (!(first < (double)n_frames)) return fail(PDOG_E_ARG, "pdog_fps_table: the stack holds no frame at or after start");
+    const int i0 = (int)first, last = n_frames - 1 - i0;
+    auto o = [&](int i) { return std::floor(((double)i * fps) / rate + 0.5); }; // output slot of input frame i (round = near)
+    const double m = std::min((double)n, o(last) + 1.0);
+    const int count = (int)m;
+    if (out_index) {
+        if (cap < count) return fail(PDOG_E_ARG, "pdog_fps_table: out_index has room for " + std::to_string(cap) + " of " + std::to_string(count) + " entries");
+        int i = 0; // max{ i : o(i) <= j } is monotone in j (o(0) = 0, so it exists for every j)
+        for (int j = 0; j < count; ++j) {
+            while (i < last && o(i + 1) <= (double)j) ++i;
+            out_index[j] = i0 + i;
+        }
+    }
+    *out_n = count;
     return PDOG_OK;
 }
 

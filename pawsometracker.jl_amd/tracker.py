@@ -36,6 +36,37 @@ def fix_window_size(window_size):
     return (int(window_size), int(window_size))
 
 
+DEFAULT_STOP = _lib.DEFAULT_STOP        # DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
+
+
+def time_axis(start, stop, fps, first=None):
+    """ts of src/PawsomeTracker.jl:150-152 (pdog_time_axis): n = round(Int, fps * (stop - start)) stamps from start to
+    stop, numpy float64.  Last-bit equality with Julia's range is unpinned (include/pawsome_video.h).  first = m: only
+    ts[:m] (:173) — the library reports n, and the m stamps are formed as it forms them, start + j * ((stop - start) / (n - 1))
+    in Float64, without the other n - m (the default stop is a day away: two million stamps at 24 per second)."""
+    start, stop, fps = float(start), float(stop), float(fps)
+    n = C.c_int()
+    _lib.check(_lib.lib().pdog_time_axis(start, stop, fps, None, 0, C.byref(n)))
+    if first is not None and 0 <= first < n.value and n.value > 1:
+        return start + np.arange(int(first), dtype=np.float64) * ((stop - start) / float(n.value - 1))
+    ts = np.empty(n.value, np.float64)
+    _lib.check(_lib.lib().pdog_time_axis(start, stop, fps, C.c_void_p(ts.ctypes.data), n.value, C.byref(n)))
+    return ts if first is None else ts[:max(int(first), 0)]
+
+
+def fps_table(rate, n_frames, start=0, stop=DEFAULT_STOP, fps=24):
+    """The frames `ffmpeg -ss start -i f -t stop-start -vf fps=fps` (src/PawsomeTracker.jl:155) selects from a stack of
+    n_frames frames at `rate` frames per second (pdog_fps_table), numpy int32: one frame index per output that exists.
+    The rule is a recollection of libavfilter's fps filter, unpinned (include/pawsome_video.h): a caller who knows better
+    builds their own table for BatchTracker.detect_chains_indexed."""
+    args = (float(rate), int(n_frames), float(start), float(stop), float(fps))
+    n = C.c_int()
+    _lib.check(_lib.lib().pdog_fps_table(*args, None, 0, C.byref(n)))
+    table = np.empty(n.value, np.int32)
+    _lib.check(_lib.lib().pdog_fps_table(*args, C.c_void_p(table.ctypes.data), n.value, C.byref(n)))
+    return table
+
+
 def mode(img):
     """mode(_img), src/PawsomeTracker.jl:47 (StatsBase tie rule, column-major scan)."""
     img = np.asarray(img)
@@ -298,5 +329,65 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
                 sub.view(-1, 2)[fi.long()] = bt.measure(flat, out.view(-1, 2)[fi.long()].contiguous(), fi)
             bt.sync()
             return out, sub
+        finally:
+            bt.close()
+
+
+def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
+                darker_target=True, sar=1.0, subpixel=False):
+    """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
+    its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
+    decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
+    chain walks that table over the shared frames in one indexed call.  `start_locations` is None, one location, or a
+    list with one location per target (several animals in one arena), each spelled as for get_guess.  As in the reference
+    the fill is the mode of the first SELECTED frame (:159, :47), every target gets its own bootstrap on that frame — the
+    sz .÷ 4 window for None (:99-107), the functor at the given guess otherwise (:92-97) — and the loop starts from the
+    second selected frame (:161-167).  Returns (ts, indices): ts numpy float64 [m], the time stamps of :150-152 cut to the m
+    frames that exist (:173), indices int32 cuda [n_targets, m, 2], 1-based (row, col).  With subpixel=True the result is
+    (ts, indices, sub), sub float64 cuda of the same shape: BatchTracker.measure at every position (this library's addition).
+    There is no diagnostic overlay here: the overlay's renderer walks a contiguous stack and takes no frame index; giving it
+    one is a separate change."""
+    import torch
+    from .batch import BatchTracker, mode_device
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3):
+        raise TypeError("frames must be a uint8 cuda tensor [n_frames, h, w]")
+    n, h, w = (int(v) for v in frames.shape)
+    table = fps_table(rate, n, start, stop, fps)
+    m = len(table)
+    ts = time_axis(start, stop, fps, first=m)
+    locs = list(start_locations) if isinstance(start_locations, list) else [start_locations]
+    if not locs:
+        raise ValueError("start_locations: an empty list names no target")
+    nt = len(locs)
+    if window_size is None:
+        window_size = guess_window_size(target_width)            # :136
+    window_size = fix_window_size(window_size)                   # :142
+    dev = frames.device
+    with torch.cuda.device(dev):
+        f0 = int(table[0])
+        fill = mode_device(frames[f0])                           # :159, :47
+        bt = BatchTracker(h, w, target_width, window_size, darker_target, fill, device=dev.index)
+        try:
+            # the first positions, :92-107: one functor application per target on the first selected frame
+            guesses = torch.tensor([get_guess(loc, frames[f0], sar) for loc in locs], dtype=torch.int32, device=dev).reshape(nt, 2)
+            on_f0 = torch.full((nt,), f0, dtype=torch.int32, device=dev)
+            starts = bt.detect(frames, guesses, on_f0)                                                    # :95
+            auto = torch.tensor([loc is None for loc in locs], device=dev)
+            if bool(auto.any()):
+                bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, fill, device=dev.index)   # :102-103
+                try:
+                    starts = torch.where(auto[:, None], bt4.detect(frames, guesses, on_f0), starts).contiguous()  # :104
+                    bt4.sync()           # a guess outside the padded frame raises here, like the reference's BoundsError
+                finally:
+                    bt4.close()
+            # the loop from the second selected frame on, :161-167: every target over the same table
+            out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
+            if not subpixel:
+                bt.sync()                # what the kernels raised (PdogError) surfaces before the positions are handed out
+                return ts, out
+            fi = torch.from_numpy(np.tile(table, nt)).to(dev)
+            sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
+            bt.sync()
+            return ts, out, sub
         finally:
             bt.close()
