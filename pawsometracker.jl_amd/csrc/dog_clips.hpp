@@ -1,6 +1,6 @@
 // dog_clips.hpp — the kernels of pawsome_clips.hip (pdog_clips_*): mode(_img) (src/PawsomeTracker.jl:47) of many
-// device-resident frames at once, and the two small kernels that carry a frame-by-frame walk over many clips from one
-// step to the next.  Included by pawsome_clips.hip only; nothing here touches the tracker's own kernels.
+// device-resident frames at once, and the kernel that starts a frame-by-frame walk over many clips (the step between two
+// frames is dog_step.hpp's).  Included by pawsome_clips.hip only; nothing here touches the tracker's own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -184,21 +184,6 @@ static __global__ void clips_init_kernel(const int32_t *__restrict__ order, int 
         out[o] = start[2 * p];
         out[o + 1] = start[2 * p + 1];
     }
-}
-
-// After the batches of frame k: every active slot's step result goes to out[clip][k] and becomes its next guess.
-static __global__ void clips_step_kernel(const int32_t *__restrict__ order, const int32_t *__restrict__ slot_len, int n_slots,
-                                         int n_frames, int k, const int32_t *__restrict__ step, int32_t *__restrict__ guess,
-                                         int32_t *__restrict__ out)
-{
-    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (p >= n_slots || slot_len[p] <= k) return;
-    const int i = step[2 * p], j = step[2 * p + 1];
-    const long long o = 2ll * ((long long)order[p] * n_frames + k);
-    out[o] = i;
-    out[o + 1] = j;
-    guess[2 * p] = i;
-    guess[2 * p + 1] = j;
 }
 
 } // namespace pdog

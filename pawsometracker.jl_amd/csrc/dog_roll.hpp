@@ -689,21 +689,8 @@ __global__ __launch_bounds__(512) void dog_chain_kernel(const std::conditional_t
 }
 
 #ifndef PDOG_ROLL_INST_ONLY
-// Step of a multi-clip chain run as ordinary batches: file the step's answers under [clip][frame] and make
-// them the next step's guesses.
-static __global__ void dog_chain_step_kernel(const int *__restrict__ step_ij, int *__restrict__ cur, int *__restrict__ out_ij,
-                                      int n_clips, int n_frames, int k)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_clips) return;
-    const int i = step_ij[2 * c], j = step_ij[2 * c + 1];
-    out_ij[2 * ((long long)c * n_frames + k)] = i;
-    out_ij[2 * ((long long)c * n_frames + k) + 1] = j;
-    cur[2 * c] = i;
-    cur[2 * c + 1] = j;
-}
-
-// The same for chains over a frame table run as ordinary batches (pdog_detect_chains_indexed): clip c has len[c] steps.
+// Chains over a frame table run as ordinary batches (pdog_detect_chains_indexed; the step between two batches is
+// dog_step.hpp's): clip c has len[c] steps.
 // Before the first step: a clip with a step to compute starts from its start guess, any other from (1, 1) — its window is
 // still part of every batch, its result is never stored, and a start that no step uses must raise nothing; with first = 1
 // row 0 of a clip that has one receives the start as given (src/PawsomeTracker.jl:104, :161).
@@ -719,18 +706,6 @@ static __global__ void dog_chain_table_init_kernel(const int *__restrict__ start
         out_ij[2 * (long long)c * n_steps] = i;
         out_ij[2 * (long long)c * n_steps + 1] = j;
     }
-}
-// After step k: a clip that has ended takes no part in the stored result and keeps its last guess.
-static __global__ void dog_chain_table_step_kernel(const int *__restrict__ step_ij, const int *__restrict__ len, int *__restrict__ cur,
-                                                   int *__restrict__ out_ij, int n_clips, int n_steps, int k)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_clips || k >= len[c]) return;
-    const int i = step_ij[2 * c], j = step_ij[2 * c + 1];
-    out_ij[2 * ((long long)c * n_steps + k)] = i;
-    out_ij[2 * ((long long)c * n_steps + k) + 1] = j;
-    cur[2 * c] = i;
-    cur[2 * c + 1] = j;
 }
 
 #endif // PDOG_ROLL_INST_ONLY

@@ -9,6 +9,7 @@
 // per-slot frame index, guesses and step results); a call whose sizes repeat allocates nothing.  Kernels: dog_clips.hpp.
 #include "pdog_host.hpp"
 #include "dog_clips.hpp"
+#include "dog_step.hpp"
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -21,11 +22,8 @@ struct pdog_clips {
     int device = 0;
     int fh = 0, fw = 0;
     DeviceBuffer<unsigned> d_table;  // multi-workgroup modes: 512 words per entry
-    DeviceBuffer<int32_t> d_plan;    // order[n_slots], slot_len[n_slots], len[n_clips]
+    StagedUpload<int32_t> plan;      // order[n_slots], slot_len[n_slots], len[n_clips], then a table's frames step-major
     DeviceBuffer<int32_t> d_work;    // fidx[n_slots], guess[2 n_slots], step[2 n_slots]
-    PinnedBuffer<int32_t> h_plan;    // what d_plan is uploaded from
-    hipEvent_t ev_upload = nullptr;  // the last upload has left h_plan
-    bool upload_pending = false;
     std::vector<int32_t> order, group_fill, group_start, active;
     std::vector<int32_t> table_len;  // steps per clip of the frame table being served (pdog_clips_track_indexed)
     int reserved = 0;                // windows the tracker's workspace was reserved for through this handle
@@ -98,14 +96,9 @@ int track_walk(pdog_clips *c, const uint8_t *d_frames, int64_t frame_stride, int
     for (int p = 0; p < n_slots; ++p) max_len = std::max(max_len, len_of(c->order[p]));
     const size_t head_words = 2 * (size_t)n_slots + (want_len ? (size_t)n_clips : 0);
     const size_t plan_words = head_words + (h_table ? (size_t)max_len * n_slots : 0);
-    if (c->upload_pending) HIP_TRY(hipEventSynchronize(c->ev_upload)); // the previous call's upload still reads h_plan
-    c->upload_pending = false;
-    if (plan_words) {
-        if (int rc = c->h_plan.reserve(plan_words, nullptr)) return rc;
-        if (int rc = c->d_plan.reserve(plan_words, &s)) return rc;
-    }
+    int32_t *hp = nullptr;
+    if (int rc = c->plan.staging(plan_words, s, &hp)) return rc;
     if (int rc = c->d_work.reserve(5 * (size_t)std::max(n_slots, 1), &s)) return rc;
-    int32_t *hp = c->h_plan.get();
     for (int p = 0; p < n_slots; ++p) {
         hp[p] = c->order[p];
         hp[n_slots + p] = len_of(c->order[p]);
@@ -117,14 +110,11 @@ int track_walk(pdog_clips *c, const uint8_t *d_frames, int64_t frame_stride, int
             const int len = len_of(c->order[p]);
             for (int k = 0; k < max_len; ++k) hp[head_words + (size_t)k * n_slots + p] = row[std::min(k, len - 1)]; // (a slot takes part: len > first)
         }
-    if (plan_words) {
-        HIP_TRY(hipMemcpyAsync(c->d_plan.get(), hp, sizeof(int32_t) * plan_words, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(c->ev_upload, s));
-        c->upload_pending = true;
-    }
-    const int32_t *d_order = c->d_plan.get(), *d_slot_len = d_order + n_slots;
+    if (plan_words)
+        if (int rc = c->plan.send(plan_words, s)) return rc;
+    const int32_t *d_order = c->plan.device(), *d_slot_len = d_order + n_slots;
     const int32_t *d_len = want_len ? d_slot_len + n_slots : nullptr;
-    const int32_t *d_steps = c->d_plan.get() + head_words;
+    const int32_t *d_steps = d_order + head_words;
     int32_t *d_fidx = c->d_work.get(), *d_guess = d_fidx + n_slots, *d_step = d_guess + 2 * (size_t)n_slots;
     const int n_init = std::max(n_slots, first ? n_clips : 0);
     if (n_init == 0) return PDOG_OK; // no clip has a frame to compute or a start to copy
@@ -151,7 +141,7 @@ int track_walk(pdog_clips *c, const uint8_t *d_frames, int64_t frame_stride, int
             any = true;
         }
         if (rc != PDOG_OK || !any) break;
-        hipLaunchKernelGGL(clips_step_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s, d_order, d_slot_len, n_slots, n_steps, k,
+        hipLaunchKernelGGL(dog_step_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s, d_order, d_slot_len, n_slots, n_steps, k,
                            (const int32_t *)d_step, d_guess, d_out_ij);
         if (hipGetLastError() != hipSuccess) rc = fail(PDOG_E_HIP, std::string(who) + ": the step kernel did not launch");
     }
@@ -176,8 +166,7 @@ int pdog_clips_create(pdog_tracker *t, pdog_clips **out)
     c->fh = info.frame_h;
     c->fw = info.frame_w;
     c->reserved = 1;
-    hipError_t e = hipGetDevice(&c->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming);
+    const hipError_t e = hipGetDevice(&c->device);
     if (e != hipSuccess) {
         delete c;
         return fail(PDOG_E_HIP, std::string("pdog_clips_create: ") + hipGetErrorString(e));
@@ -192,7 +181,6 @@ int pdog_clips_destroy(pdog_clips *c)
     (void)hipSetDevice(c->device);
     hipStream_t s = nullptr;
     if (stream_of(c, &s) == PDOG_OK) (void)hipStreamSynchronize(s); // kernels queued there may still use the workspace
-    if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
     delete c;
     return PDOG_OK;
 }
@@ -217,7 +205,7 @@ int pdog_clips_modes(pdog_clips *c, const uint8_t *d_frames, int64_t frame_strid
                      const int32_t *d_frame_index, int n, int32_t *d_out_mode)
 {
     if (!c) return fail(PDOG_E_ARG, "pdog_clips_modes: null handle");
-    if (n < 0 || n_frames <= 0 || row_stride < c->fw || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_clips_modes: bad size/stride");
+    if (int rc = check_stack("pdog_clips_modes", c->fw, n_frames, row_stride, frame_stride, n >= 0)) return rc;
     if (!d_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_clips_modes: more entries than frames and no frame index");
     if ((long long)c->fh * c->fw >= 0xffffffffLL) return fail(PDOG_E_ARG, "pdog_clips_modes: frame too large for 32-bit positions");
     if (n == 0) return PDOG_OK;
@@ -267,8 +255,7 @@ int pdog_clips_track(pdog_clips *c, const uint8_t *d_frames, int64_t frame_strid
 {
     if (!c) return fail(PDOG_E_ARG, "pdog_clips_track: null handle");
     if (!d_frames || !d_start || !d_out_ij) return fail(PDOG_E_ARG, "pdog_clips_track: null pointer");
-    if (n_frames <= 0 || n_clips <= 0 || row_stride < c->fw || frame_stride < 0 || (long long)n_clips * n_frames > 0x7fffffffLL)
-        return fail(PDOG_E_ARG, "pdog_clips_track: bad size/stride");
+    if (int rc = check_stack("pdog_clips_track", c->fw, n_frames, row_stride, frame_stride, n_clips > 0 && (long long)n_clips * n_frames <= 0x7fffffffLL)) return rc;
     if (first != 0 && first != 1) return fail(PDOG_E_ARG, "pdog_clips_track: first must be 0 or 1");
     return track_walk(c, d_frames, frame_stride, row_stride, n_frames, n_clips, h_fill, h_len, first, d_start, d_out_ij, nullptr, 0);
 }
@@ -279,8 +266,7 @@ int pdog_clips_track_indexed(pdog_clips *c, const uint8_t *d_frames, int64_t fra
 {
     if (!c) return fail(PDOG_E_ARG, "pdog_clips_track_indexed: null handle");
     if (!d_frames || !h_table || !d_start || !d_out_ij) return fail(PDOG_E_ARG, "pdog_clips_track_indexed: null pointer");
-    if (n_frames <= 0 || n_steps <= 0 || n_clips <= 0 || row_stride < c->fw || frame_stride < 0 || (long long)n_clips * n_steps > 0x7fffffffLL)
-        return fail(PDOG_E_ARG, "pdog_clips_track_indexed: bad size/stride");
+    if (int rc = check_stack("pdog_clips_track_indexed", c->fw, n_frames, row_stride, frame_stride, n_steps > 0 && n_clips > 0 && (long long)n_clips * n_steps <= 0x7fffffffLL)) return rc;
     if (first != 0 && first != 1) return fail(PDOG_E_ARG, "pdog_clips_track_indexed: first must be 0 or 1");
     // the lengths come from the table's negative tails; it is checked before anything is launched
     if (c->table_len.size() < (size_t)n_clips) c->table_len.resize((size_t)n_clips);

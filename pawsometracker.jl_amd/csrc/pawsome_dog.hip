@@ -13,6 +13,7 @@
 #include "dog_exact.hpp"
 #include "dog_tiled.hpp"
 #include "dog_measure.hpp"
+#include "dog_step.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -255,12 +256,8 @@ struct pdog_tracker {
     bool fused_c = false;          // … through its compile-time-l instance (dog_fused.hpp: l = 65, the default tracker's), whose tile layout is wider
     int hp_rows = HP_ROWS;         // RT rows (window columns) per column-pass workgroup: 16 (P = 13) or 8 (P = 7)
     DeviceBuffer<int32_t> d_chain_tmp; // [2][n_clips][2]: current guesses / step results of multi-clip chains
-    // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it, packed in
-    // pinned staging and uploaded on the stream; grow-only, like pdog_clips::h_plan / ev_upload
-    PinnedBuffer<int32_t> h_table;
-    DeviceBuffer<int32_t> d_table;
-    hipEvent_t ev_table = nullptr;     // the last upload has left h_table
-    bool table_pending = false;
+    // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it
+    StagedUpload<int32_t> table;
     std::vector<int32_t> table_len;    // steps per clip of the table being served
     int tp_ph1 = 13, tp_php = 7;   // outputs per task of the two-pass row / column pass (pick_twopass_p)
     // tiled kernel (dog_tiled.hpp): one large window cut into sub-windows, a workgroup each, one launch per batch / clip
@@ -339,7 +336,7 @@ struct pdog_tracker {
         for (int k = 0; k < kIngestSlots; ++k)
             for (hipEvent_t e : {ev_h2d[k], ev_used[k]})
                 if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_fork, ev_join, ev_switch, ev_table})
+        for (hipEvent_t e : {ev_fork, ev_join, ev_switch})
             if (e) (void)hipEventDestroy(e);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -347,10 +344,39 @@ struct pdog_tracker {
 
 namespace {
 
+// The instances of the latency kernels (dog_fused.hpp, dog_tiled.hpp): a row per compile-time length of lat_lengths.def, then
+// the row of the runtime-length instances (L = 0).  Per kernel: the plain instance, the one that also writes the response
+// map, and the one that walks a frame table (no response map: a chain has none).
 typedef void (*fused_fn_t)(const FusedGeo, const f2 *, const f2 *);
-fused_fn_t fused_kernel_for(const pdog_tracker *t, bool resp);
 typedef void (*fused_table_fn_t)(const FusedTableGeo, const f2 *, const f2 *);
-fused_table_fn_t fused_table_kernel_for(const pdog_tracker *t); // the instance that walks a frame table (no response map: a chain has none)
+typedef void (*tiled_fn_t)(const TiledGeo, const f2 *, const f2 *);
+enum { kLatPlain, kLatResp, kLatTable };
+struct LatInstances { int L; const void *fused[3], *tiled[3]; };
+#define PDOG_LAT_L(LT)                                                                                                                \
+    { LT, {(const void *)dog_fused_kernel<false, 0, LT>, (const void *)dog_fused_kernel<true, 0, LT>, (const void *)dog_fused_kernel<false, 0, LT, true>}, \
+          {(const void *)dog_tiled_kernel<false, LT>, (const void *)dog_tiled_kernel<true, LT>, (const void *)dog_tiled_kernel<false, LT, true>} },
+const LatInstances kLatInstances[] = {
+#include "lat_lengths.def"
+    PDOG_LAT_L(0)
+};
+#undef PDOG_LAT_L
+// compile_time: the row of the tracker's own length where there is one
+const LatInstances &lat_instances(int L, bool compile_time)
+{
+    const LatInstances &runtime_length = *(std::end(kLatInstances) - 1);
+    if (!compile_time) return runtime_length;
+    for (const LatInstances &row : kLatInstances)
+        if (row.L == L) return row;
+    return runtime_length;
+}
+const LatInstances &fused_instances(const pdog_tracker *t) { return lat_instances(t->L, t->fused_c); }
+const LatInstances &tiled_instances(const pdog_tracker *t) { return lat_instances(t->L, t->tiled_c); }
+int raise_lds_limits(const void *const (&fns)[3], size_t bytes)
+{
+    for (const void *fn : fns)
+        if (int rc = raise_lds_limit(fn, bytes)) return rc;
+    return PDOG_OK;
+}
 
 // LDS row pitches of the two-pass kernels: the sliding windows (and their one-block prefetch) of the last,
 // partly masked group of 13 outputs must stay inside the zero-padded row.  nout outputs, l taps.
@@ -484,25 +510,22 @@ int pick_outputs_per_task(int lines, int nout, std::initializer_list<int> ps, do
 
 // Tiled kernel (dog_tiled.hpp): windows too large for the fused kernel, cut into sub-windows of ≈48 rows/columns (a
 // 257×257 window: 6×6 of 43×43, each a tile of 107×107 like the default 45×45 window of the fused kernel).
-const void *tiled_table_kernel_for(const pdog_tracker *t) // the instance that walks a frame table (no response map: a chain has none)
+// A kernel whose own LDS (`base` bytes, at least the refinement's smallest form) doubles as the refinement's scratch: the
+// widest block of window columns whose fixed part plus 8 tile rows fits, then the tallest slice of its pixel tile (the whole
+// tile if possible) — exact mode then costs the kernel no occupancy.
+void fit_refine_scratch(const pdog_tracker *t, size_t base, int *ref_cbw, int *ref_rows)
 {
-    if (t->tiled_c) switch (t->L) {
-#define PDOG_LAT_L(LT) case LT: return (const void *)dog_tiled_kernel<false, LT, true>;
-#include "lat_lengths.def"
-#undef PDOG_LAT_L
-        default: break;
+    const int NA = t->n1 + t->L - 1;
+    *ref_cbw = 1;
+    *ref_rows = 8;
+    for (int cbw = std::min(t->n2, t->ref_cbw); cbw >= 1; --cbw) {
+        const size_t fixed_r = refine_lds_bytes(t->n1, t->L, cbw, 0);
+        if (fixed_r + (size_t)8 * refine_tile_pitch(cbw, t->L) > base) continue;
+        *ref_cbw = cbw;
+        *ref_rows = (int)std::min<size_t>((size_t)NA, (base - fixed_r) / (size_t)refine_tile_pitch(cbw, t->L));
+        while (*ref_rows > 8 && refine_lds_bytes(t->n1, t->L, cbw, *ref_rows) > base) --*ref_rows;
+        return;
     }
-    return (const void *)dog_tiled_kernel<false, 0, true>;
-}
-const void *tiled_kernel_for(const pdog_tracker *t, bool resp)
-{
-    if (t->tiled_c) switch (t->L) {
-#define PDOG_LAT_L(LT) case LT: return resp ? (const void *)dog_tiled_kernel<true, LT> : (const void *)dog_tiled_kernel<false, LT>;
-#include "lat_lengths.def"
-#undef PDOG_LAT_L
-        default: break;
-    }
-    return resp ? (const void *)dog_tiled_kernel<true> : (const void *)dog_tiled_kernel<false>;
 }
 int setup_tiled(pdog_tracker *t)
 {
@@ -543,30 +566,18 @@ int setup_tiled(pdog_tracker *t)
     // the refinement's scratch is the kernel's own LDS: at least its smallest form must fit; then the widest block that does
     const size_t base = std::max(need, refine_lds_bytes(t->n1, t->L, 1, 8));
     if (base > kMaxLds - 1024) return PDOG_OK;
-    const int NA = t->n1 + t->L - 1;
-    t->tiled_ref_cbw = 1;
-    t->tiled_ref_rows = 8;
-    for (int cbw = std::min(t->n2, t->ref_cbw); cbw >= 1; --cbw) {
-        const size_t fixed_r = refine_lds_bytes(t->n1, t->L, cbw, 0);
-        if (fixed_r + (size_t)8 * refine_tile_pitch(cbw, t->L) > base) continue;
-        t->tiled_ref_cbw = cbw;
-        t->tiled_ref_rows = (int)std::min<size_t>((size_t)NA, (base - fixed_r) / (size_t)refine_tile_pitch(cbw, t->L));
-        while (t->tiled_ref_rows > 8 && refine_lds_bytes(t->n1, t->L, cbw, t->tiled_ref_rows) > base) --t->tiled_ref_rows;
-        break;
-    }
+    fit_refine_scratch(t, base, &t->tiled_ref_cbw, &t->tiled_ref_rows);
     t->tiled_sn1 = sn1; t->tiled_sn2 = sn2; t->tiled_ns1 = ns1; t->tiled_ns2 = ns2;
     t->tiled_lds = base;
     t->tiled_cshift = 0;
     while ((1 << t->tiled_cshift) < (sn2 + t->L - 1 + 3) / 4) ++t->tiled_cshift;
     t->tiled_pr = t->tiled_c ? fusedc_row_outputs(sn1 + t->L - 1, sn2) : pick_outputs_per_task(sn1 + t->L - 1, sn2, {3, 4, 5, 6, 8}, 2.0);
     t->tiled_pc = pick_outputs_per_task(sn2, sn1, {2, 3, 4, 6, 8}, 1.5);
-    for (bool resp : {false, true})
-        if (int rc = raise_lds_limit(tiled_kernel_for(t, resp), base)) return rc;
-    if (int rc = raise_lds_limit(tiled_table_kernel_for(t), base)) return rc;
+    if (int rc = raise_lds_limits(tiled_instances(t).tiled, base)) return rc;
     int per_cu = 0, cus = 0, coop = 0;
     t->tiled_resident = 0; // chains need every workgroup of a clip resident at once: a cooperative launch, if the device has them
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, t->device) == hipSuccess && coop &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tiled_kernel_for(t, false), FUSED_NT, base) == hipSuccess && per_cu >= 1 &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tiled_instances(t).tiled[kLatPlain], FUSED_NT, base) == hipSuccess && per_cu >= 1 &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess)
         t->tiled_resident = per_cu * cus;
     t->part_slots = std::max(t->part_slots, 2 * ns1 * ns2); // … and the tiled kernel's partials: two sets per window
@@ -617,15 +628,20 @@ void use_partials(const pdog_tracker *t, LaunchGeo &g)
     g.part_mask = t->d_part_mask.get();
 }
 
+// What launch_tiled takes: n windows, or n clips of chain_len > 1 frames with every sub-window's workgroup resident at once.
+bool tiled_serves(const pdog_tracker *t, int n, int chain_len)
+{
+    return t->tiled_ok && n >= 1 && (chain_len <= 1 || (long long)n * t->tiled_ns1 * t->tiled_ns2 <= t->tiled_resident);
+}
+
 // req.n windows (chain_len = 1: independent; ordinary launch) or req.n clips of chain_len frames (cooperative launch: the
 // workgroups of a clip wait for each other's partials frame by frame).  *launched = false: not taken, the caller goes on.
 int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
 {
     *launched = false;
     const int n = req.n, chain_len = req.chain_len;
-    if (!t->tiled_ok || n < 1) return PDOG_OK;
+    if (!tiled_serves(t, n, chain_len)) return PDOG_OK;
     const int nsub = t->tiled_ns1 * t->tiled_ns2;
-    if (chain_len > 1 && (long long)n * nsub > t->tiled_resident) return PDOG_OK;
     if (int rc = ensure_capacity(t, n)) return rc;
     // the kernel leaves its counters at zero; the last word is the abort word
     if (int rc = t->d_tiled_ctl.reserve(4 * (size_t)n + 1, &t->stream, true)) return rc;
@@ -666,14 +682,13 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
         tg.tag_base = t->tiled_tag;
         t->tiled_tag += (unsigned)chain_len + 1u;
     }
-    const void *fn = req.table.index ? tiled_table_kernel_for(t) : tiled_kernel_for(t, req.out_resp != nullptr);
+    const void *fn = tiled_instances(t).tiled[req.table.index ? kLatTable : req.out_resp ? kLatResp : kLatPlain];
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
     if (chain_len > 1) {
         void *args[] = {(void *)&tg, (void *)&tr, (void *)&tc};
         const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(n * nsub), dim3(FUSED_NT), args, (unsigned)t->tiled_lds, t->stream);
         if (e != hipSuccess) { (void)hipGetLastError(); return PDOG_OK; } // refused: the caller's other paths
     } else {
-        typedef void (*tiled_fn_t)(const TiledGeo, const f2 *, const f2 *);
         hipLaunchKernelGGL((tiled_fn_t)fn, dim3(n * nsub), dim3(FUSED_NT), t->tiled_lds, t->stream, static_cast<const TiledGeo &>(tg), tr, tc);
         HIP_TRY(hipGetLastError());
     }
@@ -727,12 +742,8 @@ int choose_variant(pdog_tracker *t, int forced)
     t->forced_variant = forced >= 0;
     t->small_twopass = false;
     t->fused_ok = fused_total_lds(t) <= kMaxLds - 1024 && t->n2 + t->L - 1 <= 4 * FUSED_NT && t->fw >= 4;
-    if (t->fused_ok) {
-        for (bool resp : {false, true}) {
-            if (int rc = raise_lds_limit((const void *)fused_kernel_for(t, resp), fused_total_lds(t))) return rc;
-        }
-        if (int rc = raise_lds_limit((const void *)fused_table_kernel_for(t), fused_total_lds(t))) return rc;
-    }
+    if (t->fused_ok)
+        if (int rc = raise_lds_limits(fused_instances(t).fused, fused_total_lds(t))) return rc;
     if (int rc = setup_tiled(t)) return rc;
     if (best->fused) { t->nstrips = 1; return PDOG_OK; }
     {
@@ -791,28 +802,6 @@ int ensure_capacity(pdog_tracker *t, int n)
     if (int rc = t->d_part_sec.reserve(need, nullptr)) return rc;
     if (int rc = t->d_part_idx.reserve(need, nullptr)) return rc;
     return t->d_part_mask.reserve(need, nullptr);
-}
-
-// fused-kernel instance (runtime kernel length)
-fused_table_fn_t fused_table_kernel_for(const pdog_tracker *t)
-{
-    if (t->fused_c) switch (t->L) {
-#define PDOG_LAT_L(LT) case LT: return (fused_table_fn_t)dog_fused_kernel<false, 0, LT, true>;
-#include "lat_lengths.def"
-#undef PDOG_LAT_L
-        default: break;
-    }
-    return (fused_table_fn_t)dog_fused_kernel<false, 0, 0, true>;
-}
-fused_fn_t fused_kernel_for(const pdog_tracker *t, bool resp)
-{
-    if (t->fused_c) switch (t->L) {
-#define PDOG_LAT_L(LT) case LT: return resp ? (fused_fn_t)dog_fused_kernel<true, 0, LT> : (fused_fn_t)dog_fused_kernel<false, 0, LT>;
-#include "lat_lengths.def"
-#undef PDOG_LAT_L
-        default: break;
-    }
-    return resp ? (fused_fn_t)dog_fused_kernel<true> : (fused_fn_t)dog_fused_kernel<false>;
 }
 
 // Which kernel family a batch of n windows runs on (kPathFused, kPathTiled, kPathTwoPass, otherwise the tracker's
@@ -952,7 +941,7 @@ int launch_fused(pdog_tracker *t, const Request &req)
     fg.dc_host = req.dc_host;
     g.ex = exact_ctl(t, kFamFused);
     const size_t lds = fused_total_lds(t);
-    fused_fn_t fn = fused_kernel_for(t, req.out_resp != nullptr);
+    fused_fn_t fn = (fused_fn_t)fused_instances(t).fused[req.out_resp ? kLatResp : kLatPlain];
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
 #ifdef PDOG_ABLATIONS
     if (req.out_resp && t->sw.fused_diag) { // phase stamps instead of the response (tools/fused_phases.py)
@@ -997,7 +986,7 @@ int launch_fused(pdog_tracker *t, const Request &req)
         t->fused_resident = per_cu * cus;
     }
     const dim3 grid(std::min(n, t->fused_resident));
-    if (req.table.index) hipLaunchKernelGGL(fused_table_kernel_for(t), grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
+    if (req.table.index) hipLaunchKernelGGL((fused_table_fn_t)fused_instances(t).fused[kLatTable], grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
     else hipLaunchKernelGGL(fn, grid, dim3(FUSED_NT), lds, t->stream, static_cast<const FusedGeo &>(fg), tr, tc);
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
@@ -1230,6 +1219,25 @@ int upload(DeviceBuffer<T> &d, const std::vector<T> &h)
     HIP_TRY(hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
     return PDOG_OK;
 }
+
+// The packed window tile of the host paths (pack_tile_geo): the window with its halo of l÷2 pixels, fill materialised.  On
+// the device it is a frame of its own with the guess at its centre.
+struct TileFrame {
+    int hw, th, tw, pitch; // halo; rows, columns and row pitch of the tile
+    int centre[2];         // the tile's guess
+    explicit TileFrame(const pdog_tracker *t)
+        : hw(t->L >> 1), th(t->n1 + 2 * hw), tw(t->n2 + 2 * hw), pitch(round_up(tw, 16)), centre{t->r1 + hw + 1, t->r2 + hw + 1} {}
+    size_t bytes() const { return (size_t)th * pitch; }
+    // The reference's PaddedView extends radii + l past the frame (:45-46) and the filter reads radii + l÷2 around the
+    // guess: outside [-l÷2, sz + l÷2 + 1] it raises BoundsError.
+    bool holds(const pdog_tracker *t, int g1, int g2) const { return g1 >= -hw && g1 <= t->fh + hw + 1 && g2 >= -hw && g2 <= t->fw + hw + 1; }
+    // tile-local 1-based answer → padded-frame index → clamp (:60-61)
+    void to_frame(const pdog_tracker *t, const int32_t *guess, const int32_t *local, int32_t *out) const
+    {
+        out[0] = std::min(std::max(guess[0] - centre[0] + local[0], 1), t->fh);
+        out[1] = std::min(std::max(guess[1] - centre[1] + local[1], 1), t->fw);
+    }
+};
 
 } // namespace
 
@@ -1507,8 +1515,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
         t->fused_resident = 0;
         setup_refine_geometry(t); // the tile layout, and with it the refinement's share of the kernel's LDS
         if (t->fused_ok)
-            for (bool resp : {false, true})
-                if (int rc = raise_lds_limit((const void *)fused_kernel_for(t, resp), fused_total_lds(t))) return rc;
+            if (int rc = raise_lds_limits(fused_instances(t).fused, fused_total_lds(t))) return rc;
         if (int rc = setup_tiled(t)) return rc;
     } else if (k == "no_tiled") {
         t->sw.no_tiled = on;
@@ -1555,7 +1562,7 @@ int pdog_detect_batch(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_st
     if (!t) return fail(PDOG_E_ARG, "pdog_detect_batch: null tracker");
     if (n == 0) return PDOG_OK;
     if (!d_frames || !d_guesses || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_batch: null pointer");
-    if (n < 0 || n_frames <= 0 || row_stride < t->fw || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_detect_batch: bad size/stride");
+    if (int rc = check_stack("pdog_detect_batch", t->fw, n_frames, row_stride, frame_stride, n >= 0)) return rc;
     if (!d_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_detect_batch: more windows than frames and no frame index");
     if ((long long)n * t->nstrips > 0x7ffffff0LL) return fail(PDOG_E_ARG, "pdog_detect_batch: batch too large");
     HIP_TRY(hipSetDevice(t->device));
@@ -1582,7 +1589,7 @@ int pdog_measure(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride,
     if (!t) return fail(PDOG_E_ARG, "pdog_measure: null tracker");
     if (!d_frames || !d_ij) return fail(PDOG_E_ARG, "pdog_measure: null pointer");
     if (!d_out_resp5 && !d_out_sub) return fail(PDOG_E_ARG, "pdog_measure: both outputs are null");
-    if (n < 0 || n_frames <= 0 || row_stride < t->fw || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_measure: bad size/stride");
+    if (int rc = check_stack("pdog_measure", t->fw, n_frames, row_stride, frame_stride, n >= 0)) return rc;
     if (!d_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_measure: more positions than frames and no frame index");
     if (n == 0) return PDOG_OK;
     HIP_TRY(hipSetDevice(t->device));
@@ -1624,11 +1631,8 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
 {
     if (!t || !h_frame || !guess || !out_ij) return fail(PDOG_E_ARG, "pdog_detect_host: null pointer");
     if (row_stride < t->fw) return fail(PDOG_E_ARG, "pdog_detect_host: row_stride < frame width");
-    // The reference's PaddedView extends radii + l past the frame (:45-46) and the filter
-    // reads radii + l÷2 around the guess: outside [-l÷2, sz + l÷2 + 1] it raises BoundsError.
-    const int hw = t->L >> 1;
-    if (guess[0] < -hw || guess[0] > t->fh + hw + 1 || guess[1] < -hw || guess[1] > t->fw + hw + 1)
-        return fail(PDOG_E_RANGE, "pdog_detect_host: guess outside the padded frame (reference: BoundsError)");
+    const TileFrame tile(t);
+    if (!tile.holds(t, guess[0], guess[1])) return fail(PDOG_E_RANGE, "pdog_detect_host: guess outside the padded frame (reference: BoundsError)");
     HIP_TRY(hipSetDevice(t->device));
     if (h_resp)
         if (int rc = t->d_resp.reserve((size_t)t->n1 * t->n2, nullptr)) return rc;
@@ -1641,15 +1645,14 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         // answer is back before the kernel's end-of-grid bookkeeping, and the stream stays ordered for whatever is
         // queued next.  With a response copy, a pinned batch kernel that publishes no ticket, or a ticket that does
         // not show up in time (a failed launch), the stream is synchronised as usual.
-        const int th = t->n1 + 2 * hw, tw = t->n2 + 2 * hw, pitch = round_up(tw, 16);
-        if (int rc = t->h_tile.reserve((size_t)th * pitch, nullptr)) return rc;
+        if (int rc = t->h_tile.reserve(tile.bytes(), nullptr)) return rc;
         int32_t *mail = t->h_pinned.get(), *d_mail = t->h_pinned.device();
         const bool trace = t->sw.host_trace; // diagnostic: where a call's wall time goes
         const auto t0 = std::chrono::steady_clock::now();
         // cached stores: the functor's kernel reads this tile in place right away (non-temporal stores measured equal here)
-        pack_tile_geo(h_frame, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2, guess[0], guess[1], t->h_tile.get(), pitch, false);
-        mail[0] = t->r1 + hw + 1;   // the guess is the tile's centre
-        mail[1] = t->r2 + hw + 1;
+        pack_tile_geo(h_frame, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2, guess[0], guess[1], t->h_tile.get(), tile.pitch, false);
+        mail[0] = tile.centre[0];   // the guess is the tile's centre
+        mail[1] = tile.centre[1];
         const auto t1 = std::chrono::steady_clock::now();
         if (int rc = ensure_capacity(t, 1)) return rc;
         const int32_t ticket = t->ticket = t->ticket % 0x7fffffff + 1;   // 1 … 2^31 − 1, never the mailbox's initial 0
@@ -1660,15 +1663,15 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         {
             int total = 0;
             for (int k = 0; k < 1024; ++k)
-                total += t->h_tile.get()[(size_t)(int)(((long long)(k >> 5) * th) >> 5) * pitch + (size_t)(int)(((long long)(k & 31) * tw) >> 5)];
+                total += t->h_tile.get()[(size_t)(int)(((long long)(k >> 5) * tile.th) >> 5) * tile.pitch + (size_t)(int)(((long long)(k & 31) * tile.tw) >> 5)];
             dc_host = (total + 512) >> 10;
             if (std::abs(dc_host - t->fill) <= 8) dc_host = t->fill;
         }
         Request req;
-        req.frames = t->h_tile.device(); req.frame_stride = (int64_t)th * pitch; req.row_stride = pitch;
+        req.frames = t->h_tile.device(); req.frame_stride = (int64_t)tile.bytes(); req.row_stride = tile.pitch;
         req.guesses = d_mail; req.n = 1;
         req.out_ij = d_mail + 2; req.out_resp = h_resp ? t->d_resp.get() : nullptr;
-        req.fh = th; req.fw = tw;
+        req.fh = tile.th; req.fw = tile.tw;
         req.done_flag = d_mail + 4; req.done_value = ticket;
         req.dc_host = t->sw.no_host_dc ? -1 : dc_host;
         if (int rc = launch_detect(t, req, &armed)) return rc;
@@ -1689,8 +1692,7 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
             auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
             std::fprintf(stderr, "pdog functor: pack %.1f us, launch %.1f us, sync %.1f us\n", us(t0, t1), us(t1, t2), us(t2, t3));
         }
-        out_ij[0] = std::min(std::max(guess[0] - t->r1 - hw + mail[2] - 1, 1), t->fh);   // tile-local → frame, clamp (:60-61)
-        out_ij[1] = std::min(std::max(guess[1] - t->r2 - hw + mail[3] - 1, 1), t->fw);
+        tile.to_frame(t, guess, mail + 2, out_ij);
         return PDOG_OK;
     }
     if (int rc = t->d_frame.reserve((size_t)t->fh * t->fw, nullptr)) return rc;
@@ -1700,8 +1702,8 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         // Only the window's padded tile is read by the kernels (anything else they touch feeds masked
         // lanes), so only that rectangle of the frame crosses PCIe: 109×109 B instead of 2 MB for the
         // default 45×45 window on a 1080p frame.
-        const int r_lo = std::max(0, guess[0] - t->r1 - 1 - hw), r_hi = std::min(t->fh, guess[0] + t->r1 + hw);
-        const int c_lo = std::max(0, guess[1] - t->r2 - 1 - hw), c_hi = std::min(t->fw, guess[1] + t->r2 + hw);
+        const int r_lo = std::max(0, guess[0] - t->r1 - 1 - tile.hw), r_hi = std::min(t->fh, guess[0] + t->r1 + tile.hw);
+        const int c_lo = std::max(0, guess[1] - t->r2 - 1 - tile.hw), c_hi = std::min(t->fw, guess[1] + t->r2 + tile.hw);
         if (r_hi > r_lo && c_hi > c_lo)
             HIP_TRY(hipMemcpy2DAsync(t->d_frame.get() + (size_t)r_lo * t->fw + c_lo, t->fw, h_frame + (size_t)r_lo * row_stride + c_lo,
                                      row_stride, (size_t)(c_hi - c_lo), (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, t->stream));
@@ -1749,19 +1751,17 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
     if (!t) return fail(PDOG_E_ARG, "pdog_detect_batch_host: null tracker");
     if (n == 0) return PDOG_OK;
     if (!h_frames || !h_guesses || !h_out_ij) return fail(PDOG_E_ARG, "pdog_detect_batch_host: null pointer");
-    if (n < 0 || n_frames <= 0 || row_stride < t->fw || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_detect_batch_host: bad size/stride");
+    if (int rc = check_stack("pdog_detect_batch_host", t->fw, n_frames, row_stride, frame_stride, n >= 0)) return rc;
     if (!h_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_detect_batch_host: more windows than frames and no frame index");
-    const int hw = t->L >> 1;
+    const TileFrame tile(t);
     for (int b = 0; b < n; ++b) {
-        const int g1 = h_guesses[2 * b], g2 = h_guesses[2 * b + 1];
-        if (g1 < -hw || g1 > t->fh + hw + 1 || g2 < -hw || g2 > t->fw + hw + 1)
+        if (!tile.holds(t, h_guesses[2 * b], h_guesses[2 * b + 1]))
             return fail(PDOG_E_RANGE, "pdog_detect_batch_host: guess outside the padded frame (reference: BoundsError)");
         if (h_frame_index && (h_frame_index[b] < 0 || h_frame_index[b] >= n_frames))
             return fail(PDOG_E_ARG, "pdog_detect_batch_host: frame index out of range");
     }
     HIP_TRY(hipSetDevice(t->device));
-    const int th = t->n1 + 2 * hw, tw = t->n2 + 2 * hw, pitch = round_up(tw, 16);
-    const size_t tile_bytes = (size_t)th * pitch;
+    const size_t tile_bytes = tile.bytes();
     // chunk: ≈32 MB of tiles, at least 64 windows (the batch kernels want ≥ 1000 strip-waves when they can get them)
     int chunk = (int)std::max<size_t>(64, ((size_t)32 << 20) / tile_bytes);
     if (t->sw.ingest_chunk) chunk = t->sw.ingest_chunk;
@@ -1784,7 +1784,7 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
     if (t->d_ingest_guess.capacity() < 2 * (size_t)chunk) { // every tile's guess is its centre
         if (int rc = t->d_ingest_guess.reserve(2 * (size_t)chunk, &t->stream)) return rc;
         std::vector<int32_t> centre(2 * (size_t)chunk);
-        for (int b = 0; b < chunk; ++b) { centre[2 * b] = t->r1 + hw + 1; centre[2 * b + 1] = t->r2 + hw + 1; }
+        for (int b = 0; b < chunk; ++b) { centre[2 * b] = tile.centre[0]; centre[2 * b + 1] = tile.centre[1]; }
         HIP_TRY(hipMemcpy(t->d_ingest_guess.get(), centre.data(), sizeof(int32_t) * centre.size(), hipMemcpyHostToDevice));
     }
     if (int rc = t->d_ingest_out.reserve(2 * (size_t)n, &t->stream)) return rc;
@@ -1814,7 +1814,7 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
             const int f = h_frame_index ? h_frame_index[b] : b;
             const bool nt_stores = !t->sw.ingest_no_nt;
             pack_tile_geo(h_frames + (int64_t)f * frame_stride, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2,
-                          h_guesses[2 * b], h_guesses[2 * b + 1], t->h_stage[c % NS].get() + (size_t)(b - c * chunk) * tile_bytes, pitch, nt_stores);
+                          h_guesses[2 * b], h_guesses[2 * b + 1], t->h_stage[c % NS].get() + (size_t)(b - c * chunk) * tile_bytes, tile.pitch, nt_stores);
             packed[c].fetch_add(1, std::memory_order_release);
         }
     };
@@ -1839,10 +1839,10 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
         if (e == hipSuccess) e = hipStreamWaitEvent(t->stream, t->ev_h2d[slot], 0);
         if (e != hipSuccess) { rc = fail(PDOG_E_HIP, std::string("pdog_detect_batch_host: ") + hipGetErrorString(e)); break; }
         Request req;
-        req.frames = t->d_tiles[slot].get(); req.frame_stride = (int64_t)tile_bytes; req.row_stride = pitch;
+        req.frames = t->d_tiles[slot].get(); req.frame_stride = (int64_t)tile_bytes; req.row_stride = tile.pitch;
         req.guesses = t->d_ingest_guess.get(); req.n = nw;
         req.out_ij = t->d_ingest_out.get() + 2 * (size_t)w0;
-        req.fh = th; req.fw = tw;
+        req.fh = tile.th; req.fw = tile.tw;
         rc = launch_detect(t, req);
         if (rc == PDOG_OK && hipEventRecord(t->ev_used[slot], t->stream) != hipSuccess)
             rc = fail(PDOG_E_HIP, "pdog_detect_batch_host: hipEventRecord failed");
@@ -1859,14 +1859,7 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
                      n, nchunks, chunk, nthreads, std::chrono::duration<double, std::milli>(t_submitted - t_begin).count(), wait_pack_ms,
                      std::chrono::duration<double, std::milli>(t_end - t_submitted).count());
     }
-    const int32_t *local = t->h_ingest_out.get();
-    for (int b = 0; b < n; ++b) {
-        // tile-local 1-based (p, q)  ->  padded-frame index  ->  clamp (:60-61)
-        const int i = h_guesses[2 * b] - t->r1 - hw + local[2 * b] - 1;
-        const int j = h_guesses[2 * b + 1] - t->r2 - hw + local[2 * b + 1] - 1;
-        h_out_ij[2 * b] = std::min(std::max(i, 1), t->fh);
-        h_out_ij[2 * b + 1] = std::min(std::max(j, 1), t->fw);
-    }
+    for (int b = 0; b < n; ++b) tile.to_frame(t, h_guesses + 2 * b, t->h_ingest_out.get() + 2 * b, h_out_ij + 2 * b);
     return PDOG_OK;
 }
 
@@ -1886,12 +1879,8 @@ struct ChainTable {
 int upload_chain_table(pdog_tracker *t, const ChainTable &ct, int n_clips, int n_steps, bool by_step, const int32_t **d_tab, const int32_t **d_len)
 {
     const size_t cells = (size_t)n_clips * (by_step ? ct.max_len : n_steps), words = cells + (size_t)n_clips;
-    if (!t->ev_table) HIP_TRY(hipEventCreateWithFlags(&t->ev_table, hipEventDisableTiming));
-    if (t->table_pending) HIP_TRY(hipEventSynchronize(t->ev_table)); // the previous call's upload still reads h_table
-    t->table_pending = false;
-    if (int rc = t->h_table.reserve(words, nullptr)) return rc;
-    if (int rc = t->d_table.reserve(words, &t->stream)) return rc;
-    int32_t *hp = t->h_table.get();
+    int32_t *hp = nullptr;
+    if (int rc = t->table.staging(words, t->stream, &hp)) return rc;
     if (!by_step) std::memcpy(hp, ct.h, sizeof(int32_t) * cells);
     else
         for (int c = 0; c < n_clips; ++c) {
@@ -1899,152 +1888,158 @@ int upload_chain_table(pdog_tracker *t, const ChainTable &ct, int n_clips, int n
             for (int k = 0; k < ct.max_len; ++k) hp[(size_t)k * n_clips + c] = k < ct.len[c] ? row[k] : (ct.len[c] ? row[ct.len[c] - 1] : 0);
         }
     std::memcpy(hp + cells, ct.len, sizeof(int32_t) * (size_t)n_clips);
-    HIP_TRY(hipMemcpyAsync(t->d_table.get(), hp, sizeof(int32_t) * words, hipMemcpyHostToDevice, t->stream));
-    HIP_TRY(hipEventRecord(t->ev_table, t->stream));
-    t->table_pending = true;
-    *d_tab = t->d_table.get();
-    *d_len = t->d_table.get() + cells;
+    if (int rc = t->table.send(words, t->stream)) return rc;
+    *d_tab = t->table.device();
+    *d_len = t->table.device() + cells;
     return PDOG_OK;
 }
 
-// stream-ordered fallback for one clip of req.chain_len frames: frame k's guess is frame k-1's (clamped) answer, read
-// straight from the output array — stream order is the dependency, no host round trip per frame.  With a table the
-// host names each step's frame itself.
-int chain_by_launches(pdog_tracker *t, const Request &clip, const ChainTable *ct)
+int chain_strips(const pdog_tracker *t) { return (t->n2 + ROLL_TW - 1) / ROLL_TW; }
+
+// The persistent roll chain: one launch, a workgroup per clip (a wave per strip) walks the clip's req.chain_len frames,
+// contiguous or over req.table.
+int launch_persistent(pdog_tracker *t, const Request &req)
 {
-    Request req = clip;
-    req.n = 1;
-    req.chain_len = 1;
+    const Variant &v = *t->var;
+    const int strips = chain_strips(t);
+    ChainTableGeo cg; // (a launch without a table takes its ChainGeo part)
+    cg.tab = req.table;
+    cg.g = base_geo(t, req);
+    LaunchGeo &g = cg.g;
+    g.guesses = nullptr; // (the chain kernel takes its guesses from cg.start)
+    g.nstrips = strips; g.nslots = strips; g.nblocks = req.n * strips;
+    g.ex = exact_ctl(t, kFamRoll);
+    cg.start = req.guesses; cg.out_ij = req.out_ij; cg.n_frames = req.chain_len;
+    cg.rp = t->exact ? t->d_rp.get() : nullptr;
+    cg.taps_col_plain = t->d_taps_col.get();
+    // the strips' LDS doubles as the refinement's scratch
+    const size_t lds = std::max((size_t)strips * roll_lds_bytes(v.LT), refine_lds_bytes(t->n1, t->L, 1, 8));
+    fit_refine_scratch(t, lds, &cg.ref_cbw, &cg.ref_rows);
+    if (int rc = raise_lds_limit(req.table.index ? (const void *)v.chain_table : (const void *)v.chain, lds)) return rc;
+    const f2 *tr = t->d_taps_row.get(), *troll = t->d_taps_roll.get();
+    if (req.table.index) hipLaunchKernelGGL(v.chain_table, dim3(req.n), dim3(64 * strips), lds, t->stream, cg, tr, troll);
+    else hipLaunchKernelGGL(v.chain, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainGeo &>(cg), tr, troll);
+    HIP_TRY(hipGetLastError());
+    return PDOG_OK;
+}
+
+// What a chain runs on: a kernel that walks its clips itself, or the stepped walk below, a batch per step.
+enum class ChainPath { Fused, Persistent, Tiled, Stepped };
+
+// n_clips clips of n_steps steps, contiguous or over a table; progress: one clip whose kernel publishes k + 1 after frame k.
+ChainPath chain_path(const pdog_tracker *t, int n_clips, int n_steps, bool table, bool progress)
+{
+    const Variant &v = *t->var;
+    // a table of one step is no chain for the kernels that walk a clip themselves (their chain_len = 1 means independent windows)
+    if (table && n_steps == 1) return ChainPath::Stepped;
+    // Enough clips to fill the GPU with one wave per strip → ONE persistent launch (a workgroup per clip walks
+    // its frames).  Fewer clips are latency-bound by that single wave per strip; then each frame is a small
+    // batch that the two-pass kernels spread over many workgroups (21 µs vs 48 µs per frame, one 45×45 window).
+    // (round 3: the fused kernel's compile-time-l instances walk 256 … 4096 clips of 45×45 windows at 27–30 M frames/s, the persistent
+    // roll chain 19–28 M; at 63×63 the chain wins from ≈1400 clips: 23.5 against 18.0 M frames/s at 2048)
+    const long long strip_waves = (long long)n_clips * chain_strips(t);
+    const bool fused_wins = t->fused_ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || strip_waves < 1400);
+    const bool persistent = !progress && v.roll && v.chain && chain_strips(t) <= 8 && !fused_wins && // (the chain kernel publishes no progress)
+                            (t->forced_variant || !t->small_twopass || strip_waves >= 1000);
+    if (v.fused || (!persistent && !t->forced_variant && t->fused_ok)) return ChainPath::Fused; // one launch: a workgroup per clip loops over its frames
+    if (persistent) return ChainPath::Persistent;
+    // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that
+    // allows); with progress its combining workgroup publishes k + 1 after every frame
+    if (!t->forced_variant && tiled_serves(t, n_clips, n_steps)) return ChainPath::Tiled;
+    return ChainPath::Stepped;
+}
+
+// The stepped walk of ONE clip: a launch per step, stream order the only dependency — step k's guess is step k − 1's
+// (clamped) answer, read straight from the output array (device or host-mapped), no host round trip per frame.  With a
+// table the host names each step's frame itself.  With clip.done_flag every step publishes k + 1 there: by the kernels'
+// own ticket where the launch arms one, by dog_publish_kernel behind them otherwise.
+int walk_clip(pdog_tracker *t, const Request &clip, const ChainTable *ct)
+{
+    if (int rc = ensure_capacity(t, 1)) return rc;
+    Request req = clip; // one independent window per launch
+    req.n = 1; req.chain_len = 1; req.progress = false;
+    req.table = ClipTable{nullptr, nullptr, 0};
     const int len = ct ? ct->len[0] : clip.chain_len, first = ct ? ct->first : 0;
     if (first && len >= 1) { // the bootstrap's position, stored as given (:161); step 1 starts from the caller's copy of it
         HIP_TRY(hipMemcpyAsync(req.out_ij, clip.guesses, sizeof(int32_t) * 2, hipMemcpyDeviceToDevice, t->stream));
         req.out_ij += 2;
     }
     for (int k = first; k < len; ++k) {
-        if (ct) req.frames = clip.frames + (int64_t)ct->h[k] * clip.frame_stride;
-        if (int rc = launch_detect(t, req)) return rc;
-        req.frames += clip.frame_stride;
+        req.frames = clip.frames + (int64_t)(ct ? ct->h[k] : k) * clip.frame_stride;
+        if (req.done_flag) req.done_value = k + 1;
+        bool armed = false;
+        if (int rc = launch_detect(t, req, req.done_flag ? &armed : nullptr)) return rc;
+        if (req.done_flag && !armed) {
+            hipLaunchKernelGGL(dog_publish_kernel, dim3(1), dim3(64), 0, t->stream, req.done_flag, k + 1);
+            HIP_TRY(hipGetLastError());
+        }
         req.guesses = req.out_ij;
         req.out_ij += 2;
     }
     return PDOG_OK;
 }
 
-// n_clips clips of n_steps frames each: contiguous (ct null: clip c's frame k is frame c*n_steps + k) or over a table.
-int run_chains(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride, int n_steps, int n_clips,
-               const int32_t *d_start_guesses, int32_t *d_out_ij, const ChainTable *ct)
+// The stepped walk of SEVERAL clips: step k of all clips is one batch, and dog_step_kernel files its answers under [clip][k]
+// and makes them the next guesses.  Contiguous: window c looks at frame c*n_steps + k, a batch whose frame stride is one
+// clip.  Table: the batch's frame index is the table's column k; a clip that has ended rides along and stores nothing.
+int walk_clips(pdog_tracker *t, const Request &clips, const ChainTable *ct)
 {
-    const Variant &v = *t->var;
-    const int chain_strips = (t->n2 + ROLL_TW - 1) / ROLL_TW;
-    // Enough clips to fill the GPU with one wave per strip → ONE persistent launch (a workgroup per clip walks
-    // its frames).  Fewer clips are latency-bound by that single wave per strip; then each frame is a small
-    // batch that the two-pass kernels spread over many workgroups (21 µs vs 48 µs per frame, one 45×45 window).
-    // (round 3: the fused kernel's compile-time-l instances walk 256 … 4096 clips of 45×45 windows at 27–30 M frames/s, the persistent
-    // roll chain 19–28 M; at 63×63 the chain wins from ≈1400 clips: 23.5 against 18.0 M frames/s at 2048)
-    const bool fused_wins = t->fused_ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || (long long)n_clips * chain_strips < 1400);
-    const bool persistent = v.roll && v.chain && chain_strips <= 8 && !fused_wins &&
-                            (t->forced_variant || !t->small_twopass || (long long)n_clips * chain_strips >= 1000);
-    // a table of one step is no chain for the kernels that walk a clip themselves (their chain_len = 1 means independent windows)
-    const bool walkers = !ct || n_steps > 1;
-    Request req; // n_clips clips of n_steps frames
-    req.frames = d_frames; req.frame_stride = frame_stride; req.row_stride = row_stride;
-    req.guesses = d_start_guesses; req.n = n_clips; req.chain_len = n_steps;
-    req.out_ij = d_out_ij;
-    if (t->sw.tiled_force && n_clips == 1 && !t->forced_variant && !ct) {
-        bool launched = false;
-        if (int rc = launch_tiled(t, req, &launched)) return rc;
-        if (launched) return PDOG_OK;
-    }
-    const bool fused = v.fused || (!persistent && !t->forced_variant && t->fused_ok);
-    const bool tiled = !fused && !persistent && !t->forced_variant && t->tiled_ok &&
-                       (long long)n_clips * t->tiled_ns1 * t->tiled_ns2 <= t->tiled_resident; // (what launch_tiled asks of clips)
-    if (ct && walkers && (fused || persistent || tiled)) {
-        if (int rc = upload_chain_table(t, *ct, n_clips, n_steps, false, &req.table.index, &req.table.len)) return rc;
-        req.table.first = ct->first;
-    }
-    if (fused && walkers) // one launch: a workgroup per clip loops over its frames
-        return launch_fused(t, req);
-    if (persistent && walkers) {
-        Request frames_only; // (the chain kernel takes its guesses from cg.start)
-        frames_only.frames = d_frames; frames_only.frame_stride = frame_stride; frames_only.row_stride = row_stride;
-        frames_only.n = n_clips;
-        ChainTableGeo cg; // (a launch without a table takes its ChainGeo part)
-        cg.tab = req.table;
-        cg.g = base_geo(t, frames_only);
-        LaunchGeo &g = cg.g;
-        g.nstrips = chain_strips;
-        g.nblocks = n_clips * chain_strips;
-        g.nslots = chain_strips;
-        cg.start = d_start_guesses;
-        cg.out_ij = d_out_ij;
-        cg.n_frames = n_steps;
-        g.ex = exact_ctl(t, kFamRoll);
-        cg.rp = t->exact ? t->d_rp.get() : nullptr;
-        cg.taps_col_plain = t->d_taps_col.get();
-        // the strips' LDS doubles as the refinement's scratch: the widest block (with its pixel tile if possible) that
-        // fits what the strips need anyway, so that exact mode does not cost the chain kernel occupancy
-        const int NAc = t->n1 + t->L - 1;
-        const size_t base = std::max((size_t)chain_strips * roll_lds_bytes(v.LT), refine_lds_bytes(t->n1, t->L, 1, 8));
-        cg.ref_cbw = 1;
-        cg.ref_rows = 8;
-        for (int cbw = std::min(t->n2, t->ref_cbw); cbw >= 1; --cbw) { // widest block first; its tile fully resident if possible, else the tallest slice
-            const size_t fixed_r = refine_lds_bytes(t->n1, t->L, cbw, 0);
-            if (fixed_r + (size_t)8 * refine_tile_pitch(cbw, t->L) > base) continue;
-            cg.ref_cbw = cbw;
-            cg.ref_rows = (int)std::min<size_t>((size_t)NAc, (base - fixed_r) / (size_t)refine_tile_pitch(cbw, t->L));
-            while (cg.ref_rows > 8 && refine_lds_bytes(t->n1, t->L, cbw, cg.ref_rows) > base) --cg.ref_rows;
-            break;
-        }
-        const size_t lds = base;
-        if (int rc = raise_lds_limit(ct ? (const void *)v.chain_table : (const void *)v.chain, lds)) return rc;
-        const f2 *tr = t->d_taps_row.get(), *troll = t->d_taps_roll.get();
-        if (ct) hipLaunchKernelGGL(v.chain_table, dim3(n_clips), dim3(64 * chain_strips), lds, t->stream, cg, tr, troll);
-        else hipLaunchKernelGGL(v.chain, dim3(n_clips), dim3(64 * chain_strips), lds, t->stream, static_cast<const ChainGeo &>(cg), tr, troll);
-        HIP_TRY(hipGetLastError());
-        return PDOG_OK;
-    }
+    const int n_clips = clips.n, n_steps = clips.chain_len, blocks = (n_clips + 255) / 256;
     if (int rc = ensure_capacity(t, n_clips)) return rc;
-    if (!t->forced_variant && walkers) { // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that allows)
-        bool launched = false;
-        if (int rc = launch_tiled(t, req, &launched)) return rc;
-        if (launched) return PDOG_OK;
-    }
-    req.table = ClipTable{nullptr, nullptr, 0}; // the launches below are independent windows
-    if (n_clips == 1) return chain_by_launches(t, req, ct);
     if (int rc = t->d_chain_tmp.reserve(4 * (size_t)n_clips, &t->stream)) return rc;
     int32_t *cur = t->d_chain_tmp.get(), *step = cur + 2 * (size_t)n_clips;
-    const int blocks = (n_clips + 255) / 256;
     Request batch;
-    batch.row_stride = row_stride;
+    batch.frames = clips.frames; batch.row_stride = clips.row_stride;
     batch.guesses = cur; batch.n = n_clips;
     batch.out_ij = step;
-    if (ct) { // step k: window c looks at frame table[c][k] of the shared stack — the batch's frame index is the table's column k
-        const int32_t *d_cols = nullptr, *d_len = nullptr;
+    const int32_t *d_cols = nullptr, *d_len = nullptr;
+    if (ct) {
         if (int rc = upload_chain_table(t, *ct, n_clips, n_steps, true, &d_cols, &d_len)) return rc;
-        hipLaunchKernelGGL(dog_chain_table_init_kernel, dim3(blocks), dim3(256), 0, t->stream, d_start_guesses, d_len, cur, d_out_ij,
+        hipLaunchKernelGGL(dog_chain_table_init_kernel, dim3(blocks), dim3(256), 0, t->stream, clips.guesses, d_len, cur, clips.out_ij,
                            n_clips, n_steps, ct->first);
         HIP_TRY(hipGetLastError());
-        batch.frames = d_frames; batch.frame_stride = frame_stride;
-        for (int k = ct->first; k < ct->max_len; ++k) {
-            batch.frame_index = d_cols + (size_t)k * n_clips;
-            if (int rc = launch_detect(t, batch)) return rc;
-            hipLaunchKernelGGL(dog_chain_table_step_kernel, dim3(blocks), dim3(256), 0, t->stream, step, d_len, cur, d_out_ij,
-                               n_clips, n_steps, k);
-            HIP_TRY(hipGetLastError());
-        }
-        return PDOG_OK;
+        batch.frame_stride = clips.frame_stride;
+    } else {
+        HIP_TRY(hipMemcpyAsync(cur, clips.guesses, sizeof(int32_t) * 2 * (size_t)n_clips, hipMemcpyDeviceToDevice, t->stream));
+        batch.frame_stride = clips.frame_stride * n_steps;
     }
-    HIP_TRY(hipMemcpyAsync(cur, d_start_guesses, sizeof(int32_t) * 2 * (size_t)n_clips, hipMemcpyDeviceToDevice, t->stream));
-    // step k: window c looks at clip c's frame k = frame (c*n_frames + k): a batch whose frame stride is one clip
-    batch.frame_stride = frame_stride * n_steps;
-    for (int k = 0; k < n_steps; ++k) {
-        batch.frames = d_frames + (int64_t)k * frame_stride;
+    for (int k = ct ? ct->first : 0; k < (ct ? ct->max_len : n_steps); ++k) {
+        if (ct) batch.frame_index = d_cols + (size_t)k * n_clips;
+        else batch.frames = clips.frames + (int64_t)k * clips.frame_stride;
         if (int rc = launch_detect(t, batch)) return rc;
-        hipLaunchKernelGGL(dog_chain_step_kernel, dim3(blocks), dim3(256), 0, t->stream, step, cur, d_out_ij,
-                           n_clips, n_steps, k);
+        hipLaunchKernelGGL(dog_step_kernel, dim3(blocks), dim3(256), 0, t->stream, (const int32_t *)nullptr, d_len, n_clips, n_steps, k,
+                           (const int32_t *)step, cur, clips.out_ij);
         HIP_TRY(hipGetLastError());
     }
     return PDOG_OK;
+}
+
+// clips.n clips of clips.chain_len steps each: contiguous (ct null: clip c's step k is frame c*chain_len + k) or over a table.
+int run_chains(pdog_tracker *t, Request clips, const ChainTable *ct)
+{
+    if (t->sw.tiled_force && clips.n == 1 && !t->forced_variant && !ct && !clips.progress) { // experiment switch: the tiled kernel first
+        bool launched = false;
+        if (int rc = launch_tiled(t, clips, &launched)) return rc;
+        if (launched) return PDOG_OK;
+    }
+    const ChainPath path = chain_path(t, clips.n, clips.chain_len, ct != nullptr, clips.progress);
+    if (ct && path != ChainPath::Stepped) { // the kernels that walk a clip themselves read the table's rows
+        if (int rc = upload_chain_table(t, *ct, clips.n, clips.chain_len, false, &clips.table.index, &clips.table.len)) return rc;
+        clips.table.first = ct->first;
+    }
+    switch (path) {
+    case ChainPath::Fused: return launch_fused(t, clips);
+    case ChainPath::Persistent: return launch_persistent(t, clips);
+    case ChainPath::Tiled: {
+        bool launched = false;
+        if (int rc = launch_tiled(t, clips, &launched)) return rc;
+        if (launched) return PDOG_OK;
+        break; // not taken (the cooperative launch was refused): the stepped walk
+    }
+    case ChainPath::Stepped:
+        break;
+    }
+    return clips.n == 1 ? walk_clip(t, clips, ct) : walk_clips(t, clips, ct);
 }
 
 } // namespace
@@ -2053,10 +2048,12 @@ extern "C" int pdog_detect_chains(pdog_tracker *t, const uint8_t *d_frames, int6
                                   int n_frames, int n_clips, const int32_t *d_start_guesses, int32_t *d_out_ij)
 {
     if (!t || !d_frames || !d_start_guesses || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chains: null pointer");
-    if (n_frames <= 0 || n_clips <= 0 || row_stride < t->fw || frame_stride < 0)
-        return fail(PDOG_E_ARG, "pdog_detect_chains: bad size/stride");
+    if (int rc = check_stack("pdog_detect_chains", t->fw, n_frames, row_stride, frame_stride, n_clips > 0)) return rc;
     HIP_TRY(hipSetDevice(t->device));
-    return run_chains(t, d_frames, frame_stride, row_stride, n_frames, n_clips, d_start_guesses, d_out_ij, nullptr);
+    Request clips;
+    clips.frames = d_frames; clips.frame_stride = frame_stride; clips.row_stride = row_stride;
+    clips.guesses = d_start_guesses; clips.n = n_clips; clips.chain_len = n_frames; clips.out_ij = d_out_ij;
+    return run_chains(t, clips, nullptr);
 }
 
 // The chain over a frame table (include/pawsome_video.h).  The table is validated here, on the host, before anything is
@@ -2066,15 +2063,17 @@ extern "C" int pdog_detect_chains_indexed(pdog_tracker *t, const uint8_t *d_fram
                                           const int32_t *d_start, int32_t *d_out_ij)
 {
     if (!t || !d_frames || !h_table || !d_start || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: null pointer");
-    if (n_frames <= 0 || n_steps <= 0 || n_clips <= 0 || row_stride < t->fw || frame_stride < 0 || (long long)n_clips * n_steps > 0x7fffffffLL)
-        return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: bad size/stride");
+    if (int rc = check_stack("pdog_detect_chains_indexed", t->fw, n_frames, row_stride, frame_stride, n_steps > 0 && n_clips > 0 && (long long)n_clips * n_steps <= 0x7fffffffLL)) return rc;
     if (first != 0 && first != 1) return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: first must be 0 or 1");
     if (t->table_len.size() < (size_t)n_clips) t->table_len.resize((size_t)n_clips);
     ChainTable ct{h_table, t->table_len.data(), first, 0};
     if (int rc = chain_table_lengths("pdog_detect_chains_indexed", h_table, n_steps, n_clips, n_frames, t->table_len.data(), &ct.max_len)) return rc;
     if (ct.max_len == 0) return PDOG_OK; // no clip has a step
     HIP_TRY(hipSetDevice(t->device));
-    return run_chains(t, d_frames, frame_stride, row_stride, n_steps, n_clips, d_start, d_out_ij, &ct);
+    Request clips;
+    clips.frames = d_frames; clips.frame_stride = frame_stride; clips.row_stride = row_stride;
+    clips.guesses = d_start; clips.n = n_clips; clips.chain_len = n_steps; clips.out_ij = d_out_ij;
+    return run_chains(t, clips, &ct);
 }
 
 extern "C" int pdog_detect_chain(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,
@@ -2110,7 +2109,7 @@ extern "C" int pdog_detect_chain_progress(pdog_tracker *t, const uint8_t *d_fram
                                           int n_frames, const int32_t start_guess[2], int32_t *h_out_ij, int32_t *h_progress)
 {
     if (!t || !d_frames || !start_guess || !h_out_ij || !h_progress) return fail(PDOG_E_ARG, "pdog_detect_chain_progress: null pointer");
-    if (n_frames <= 0 || row_stride < t->fw || frame_stride < 0) return fail(PDOG_E_ARG, "pdog_detect_chain_progress: bad size/stride");
+    if (int rc = check_stack("pdog_detect_chain_progress", t->fw, n_frames, row_stride, frame_stride)) return rc;
     HIP_TRY(hipSetDevice(t->device));
     int32_t *d_out = nullptr, *d_prog = nullptr;
     if (hipHostGetDevicePointer((void **)&d_out, h_out_ij, 0) != hipSuccess || hipHostGetDevicePointer((void **)&d_prog, h_progress, 0) != hipSuccess)
@@ -2119,29 +2118,7 @@ extern "C" int pdog_detect_chain_progress(pdog_tracker *t, const uint8_t *d_fram
     HIP_TRY(hipMemcpyAsync(t->d_small.get(), start_guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
     Request req; // one clip whose kernel publishes k + 1 after every frame
     req.frames = d_frames; req.frame_stride = frame_stride; req.row_stride = row_stride;
-    req.guesses = t->d_small.get(); req.n = 1; req.chain_len = n_frames;
-    req.out_ij = d_out;
+    req.guesses = t->d_small.get(); req.n = 1; req.chain_len = n_frames; req.out_ij = d_out;
     req.done_flag = d_prog; req.progress = true;
-    if (t->var->fused || (!t->forced_variant && t->fused_ok)) return launch_fused(t, req); // one launch
-    if (int rc = ensure_capacity(t, 1)) return rc;
-    if (!t->forced_variant) { // the tiled kernel: the combining workgroup publishes k + 1 after every frame
-        bool launched = false;
-        if (int rc = launch_tiled(t, req, &launched)) return rc;
-        if (launched) return PDOG_OK;
-    }
-    req.chain_len = 1;
-    req.progress = false;
-    for (int k = 0; k < n_frames; ++k) { // stream-ordered launches per frame; frame k's guess is read from the (host-mapped) answer k − 1
-        bool armed = false;
-        req.done_value = k + 1;
-        if (int rc = launch_detect(t, req, &armed)) return rc;
-        req.frames += frame_stride;
-        req.guesses = req.out_ij;
-        req.out_ij += 2;
-        if (!armed) {
-            hipLaunchKernelGGL(dog_publish_kernel, dim3(1), dim3(64), 0, t->stream, d_prog, k + 1);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return PDOG_OK;
+    return run_chains(t, req, nullptr);
 }

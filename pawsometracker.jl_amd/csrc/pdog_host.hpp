@@ -7,7 +7,9 @@
 // private copies whose LDS limit was never raised.  So every include of a dog_*.hpp header of the tracker, every launch of
 // its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
 // this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip and pawsome_group.hip launch their own
-// kernels, dog_diag.hpp's and group_compact_kernel, which no other unit names.)
+// kernels, dog_diag.hpp's and group_compact_kernel, which no other unit names.)  The one exception is dog_step.hpp, which
+// pawsome_dog.hip and pawsome_clips.hip both include: its kernel uses no dynamic LDS, so no limit is ever raised for it and
+// a private copy per unit is harmless.
 #pragma once
 #include "../../include/pawsome_dog.h"
 #include <string>
@@ -31,6 +33,12 @@ ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<doub
 // negative entries only as the tail of a row.  out_len[c] = steps of clip c (its row's leading non-negative entries),
 // *max_len the longest.  PDOG_E_ARG in `who`'s name, outputs undefined, otherwise.
 int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, int n_clips, int n_frames, int32_t *out_len, int *max_len);
+// The test the entry points share for a stack of frames (and `counts_ok`: the entry point's own sizes); PDOG_E_ARG in `who`'s name.
+inline int check_stack(const char *who, int fw, int n_frames, int64_t row_stride, int64_t frame_stride, bool counts_ok = true)
+{
+    if (counts_ok && n_frames > 0 && row_stride >= fw && frame_stride >= 0) return PDOG_OK;
+    return fail(PDOG_E_ARG, std::string(who) + ": bad size/stride");
+}
 void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int fill, int L, int r1, int r2, int g1, int g2,
                    uint8_t *dst, int64_t pitch, bool stream = false);
 
@@ -110,6 +118,42 @@ private:
 };
 template <typename T> using DeviceBuffer = Buffer<T, false>;
 template <typename T> using PinnedBuffer = Buffer<T, true>;
+
+// Host words on their way to the device: pinned staging, the device copy, and the event that tells when the last upload
+// has left the staging.  Grow-only.  Two calls may follow each other without a synchronisation between them, so staging()
+// waits for the previous upload before the caller overwrites the words; send() queues the copy and records the event.
+template <typename T>
+class StagedUpload {
+public:
+    ~StagedUpload() { if (ev_) (void)hipEventDestroy(ev_); } // (the owner has drained its stream)
+
+    // Room for n words on both sides (`stream` is drained if the device copy, which kernels queued there may still read,
+    // has to grow); *out = the staging, the caller's to fill.
+    int staging(size_t n, hipStream_t stream, T **out)
+    {
+        if (pending_) HIP_TRY(hipEventSynchronize(ev_));
+        pending_ = false;
+        if (int rc = host_.reserve(n, nullptr)) return rc;
+        if (int rc = dev_.reserve(n, &stream)) return rc;
+        *out = host_.get();
+        return PDOG_OK;
+    }
+    int send(size_t n, hipStream_t stream)
+    {
+        if (!ev_) HIP_TRY(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(dev_.get(), host_.get(), sizeof(T) * n, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(ev_, stream));
+        pending_ = true;
+        return PDOG_OK;
+    }
+    const T *device() const { return dev_.get(); }
+
+private:
+    PinnedBuffer<T> host_;
+    DeviceBuffer<T> dev_;
+    hipEvent_t ev_ = nullptr;
+    bool pending_ = false;
+};
 
 } // namespace pdog
 #pragma GCC visibility pop

@@ -441,3 +441,100 @@ def test_track_video_is_track_frames_on_the_selected_frames(pt):
     t3 = vr.fps_table(rate, nf, 1.0, BIG, fps)
     assert len(ts3) == len(t3) == idx3.shape[1] and np.array_equal(ts3, vr.time_axis_float(1.0, BIG, fps)[:len(t3)])
     assert _as_lists(idx3)[0] == [tuple(p) for p in pt.track_frames([frames[i] for i in t3], tw, None)]
+
+
+# ---- 7. the host orchestration's rarely taken branches ----
+def test_progress_chain_on_kernels_that_arm_no_ticket(pt, oracle):
+    """The batch kernels (the l = 29 ring and roll instances pinned) publish no ticket of their own: the stepped walk queues
+    a publishing kernel behind every step.  The positions equal detect_chain's on the same pinned tracker and the oracle's
+    chain, and the counter ends at the number of frames."""
+    st, ws, nf = _stack("small"), (21, 21), 8
+    frames, row = st.dev()[:nf], list(range(nf))
+    start = st.starts([row])[0]
+    want = st.chain(oracle, row, ws, start, 0)
+    bt = pt.BatchTracker(st.h, st.w, st.tw, ws, True, st.fill(oracle))
+    try:
+        for variant in (20, 129):
+            bt.set_variant(variant)
+            assert bt.info().variant == variant and bt.kernel_for_batch(1) == variant
+            plain = bt.detect_chain(frames, start)
+            bt.sync()
+            cp = bt.detect_chain_progress(frames, start)
+            got = cp.wait()
+            assert cp.done() == nf, variant
+            assert [tuple(int(v) for v in p) for p in got] == want == _as_lists(plain[None])[0], variant
+            cp.close()
+    finally:
+        bt.close()
+
+
+def test_back_to_back_table_uploads_need_no_sync_between(pt, oracle):
+    """Two (then three) indexed calls on the per-step batches (variant 20 is the l = 29 ring kernel: the table goes up
+    step-major, dog_chain_table_init_kernel, then a batch and a step kernel per step) with nothing waiting between them:
+    the second table is larger and grows the staging, the third is packed into staging that the second's upload may still
+    be reading.  After one sync every output equals what its call gives alone, and the restatement."""
+    import torch
+    st, ws = _stack("small"), (21, 21)
+    tabs = _tables(st.nf, 6)
+    tables = [np.asarray(tabs[name], np.int32) for name in ("identity", "ragged", "identity")]
+    starts = [st.starts(tb) for tb in tables]
+    d_starts = [torch.tensor(s, dtype=torch.int32).cuda() for s in starts]
+    outs = [torch.full(tb.shape + (2,), SENT, dtype=torch.int32).cuda() for tb in tables]
+    alone = [torch.full(tb.shape + (2,), SENT, dtype=torch.int32).cuda() for tb in tables]
+    frames = st.dev()
+    bt = pt.BatchTracker(st.h, st.w, st.tw, ws, True, st.fill(oracle))
+    try:
+        bt.set_variant(20)
+        assert bt.info().variant == 20
+        bt.sync()
+        for tb, s, o in zip(tables, d_starts, outs):
+            bt.detect_chains_indexed(frames, tb, s, out=o)
+        bt.sync()
+        for tb, s, o in zip(tables, d_starts, alone):
+            bt.detect_chains_indexed(frames, tb, s, out=o)
+            bt.sync()
+    finally:
+        bt.close()
+    for tb, s, o, a in zip(tables, starts, outs, alone):
+        got = _as_lists(o)
+        assert got == _as_lists(a)
+        for c, row in enumerate(tb):
+            n = vr.row_len(row)
+            assert got[c][:n] == st.chain(oracle, row, ws, s[c], 0), c
+            assert all(p == (SENT, SENT) for p in got[c][n:]), c
+
+
+def test_back_to_back_clip_plans_need_no_sync_between(pt, oracle):
+    """The same for the clips handle: two calls of two fills each (so each uploads a plan), the second with more clips,
+    nothing waiting between them.  Each equals its own result when run alone, and the restatement under each clip's fill."""
+    import torch
+    st, ws = _stack("small"), (21, 21)
+    a = np.arange(6)
+    calls = [(np.array([a, a + 2], np.int32), [30, 128]),
+             (np.array([a + 6, a[::-1] + 3, list(a[:4]) + [-1, -1], a + 1, [7] + [-1] * 5], np.int32), [128, 30, 128, 30, 30])]
+    starts = [st.starts(tb) for tb, _ in calls]
+    d_starts = [torch.tensor(s, dtype=torch.int32).cuda() for s in starts]
+    outs = [torch.full(tb.shape + (2,), SENT, dtype=torch.int32).cuda() for tb, _ in calls]
+    alone = [torch.full(tb.shape + (2,), SENT, dtype=torch.int32).cuda() for tb, _ in calls]
+    frames = st.dev()
+    bt = pt.BatchTracker(st.h, st.w, st.tw, ws, True, 7)
+    try:
+        bt.clip_modes(frames[:1])          # the handle exists before the calls under test
+        bt.sync()
+        before = bt.clips_counters()
+        for (tb, fills), s, o in zip(calls, d_starts, outs):
+            bt.track_clips_indexed(frames, tb, s, fills=fills, out=o)
+        bt.sync()
+        assert bt.clips_counters()[3] == before[3]       # neither call took the one-fill fast path
+        for (tb, fills), s, o in zip(calls, d_starts, alone):
+            bt.track_clips_indexed(frames, tb, s, fills=fills, out=o)
+            bt.sync()
+    finally:
+        bt.close()
+    for (tb, fills), s, o, al in zip(calls, starts, outs, alone):
+        got = _as_lists(o)
+        assert got == _as_lists(al)
+        for c, row in enumerate(tb):
+            n = vr.row_len(row)
+            assert got[c][:n] == st.chain(oracle, row, ws, s[c], 0, fill=fills[c]), c
+            assert all(p == (SENT, SENT) for p in got[c][n:]), c
