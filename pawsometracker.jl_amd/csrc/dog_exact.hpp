@@ -20,6 +20,10 @@
 //     ⇒ δ = u·(V/255)·F·1.02, F evaluated numerically over the tracker's own Float64 taps per kernel FAMILY (pawsome_dog.hip,
 //       exact_factors): l = 65: F = 157 (roll), 94 (fused, tiled), 138 (ring) against 6l + 4 = 394; the two-pass kernels add
 //       every chain of one register-ring trip from zero and sum the chains (dog_twopass.hpp): l = 293: F = 72 against 1762.
+// THE EXECUTABLE STATEMENT OF THESE ORDERS is tests/fp32_restatement.py: each family's order once, as data, a float32 emulation
+// that runs it and the factor F summed over the same description.  tests/test_gpu_fp32_order.py holds every family's response
+// map to that emulation BIT FOR BIT (so a reassociation, another chain split or a compiler that contracts differently fails
+// there, not silently inside δ) and the threshold T to the derived F; a kernel that changes its order changes it there too.
 // The reference's own Float64 rounding (≤ l²·2⁻⁵³·2·V/255) is negligible beside it.  The FLAG uses V = 255 (δ(l = 65) = 9.5e-6
 // for the roll kernels against a typical peak of 0.09 and a typical peak-to-neighbour gap of 4.7e-4) or, on the two-pass path,
 // the window's own V, which its row pass collects.  The REFINEMENT of a flagged window may take the window's own

@@ -836,7 +836,7 @@ double twopass_factor(const pdog_tracker *t, bool hr8)
         double F = 0, total = 0;
         const int n = (int)terms.size();
         for (int c = 0, a = 0; c <= n_full; ++c) {
-            const int b = c < n_full ? a + m : n;
+            const int b = c < n_full ? std::min(a + m, n) : n; // (the column pass's last full trip may end in the table's zero padding: l = 113, 117, 137, …)
             double w = 0;
             for (int i = a; i < b; ++i) { w += terms[i]; F += w; } // the chain's own running sums, from zero
             total += w;

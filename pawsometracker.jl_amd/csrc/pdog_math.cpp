@@ -60,6 +60,8 @@ void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, do
 //   two-pass: every chain is one trip of the register ring long, the chains' sums are added up (dog_twopass.hpp) — per chain its own
 //   cumulative weights from zero, plus the running total's weight per addition (twopass_factor, pawsome_dog.hip)
 // l = 65: 157 (roll) / 94 (fused, tiled) / 138 (ring) against the order-blind 6l + 4 = 394;  l = 293 two-pass: 72 against 1762.
+// tests/fp32_restatement.py states the same orders as data and sums the same factors over them; tests/test_gpu_fp32_order.py holds the
+// kernels' response maps to those orders bit for bit and the thresholds built from the factors below to the ones derived there.
 ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm)
 {
     const int l = (int)gp.size(), H = l / 2;
