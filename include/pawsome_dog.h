@@ -149,6 +149,7 @@ int pdog_set_exact(pdog_tracker *t, int on);
  *   "fault_inject" tests: one workgroup of a tiled chain skips an arrival (the bounded device-side waits must give up)
  *   "no_roll_map"  hard batches keep recomputing their refinement candidates
  *   "no_fold" / "fold_always"  a single remainder column always / never goes to the remainder-column kernel
+ *   "no_pad_skip"  the roll kernels run their full path also on sub-chunks (8 tile rows of a strip) that hold padding only
  *   "measure_global" pdog_measure reads the frame itself instead of staging each position's pixels in LDS (its path for l > 93)
  * Unknown key: PDOG_E_ARG.  Drains the tracker's stream. */
 int pdog_set_tuning(pdog_tracker *t, const char *key, int value);

@@ -181,6 +181,7 @@ struct LaunchGeo {
     // [n][n1 + L − 1]; dog_finish_kernel runs that one column's column pass.  Same operation order as a strip: the column's
     // values are bit-identical to what a strip would have produced.
     f2 *__restrict__ fold_r;
+    int no_pad_skip;                     // roll kernels: padding-only sub-chunks run the full path (pdog_set_tuning "no_pad_skip")
 };
 
 constexpr int FOLD_GO = 5; // output rows per lane and pass of a folded remainder column (257 rows = 64 lanes × 5 + 1 …)

@@ -22,6 +22,31 @@
 //   * completed outputs feed a running (max, first column-major index) per lane;
 //     wave-shuffle reduction at the end, one partial per strip.
 //
+//   * PADDING ROWS.  The reference pads the frame with `fill` (PaddedView, src/PawsomeTracker.jl:48), so a window near the
+//     frame's edge has sub-chunks — 8 tile rows of a strip — that hold padding only: all 8 rows above or below the frame, or a
+//     strip whose staged columns all lie left or right of it.  When the window's DC level equals the fill (dc_from_sum snaps
+//     to it within 8 levels) every input of such a sub-chunk is fill − dc = +0, and the sub-chunk skips the u8 → f32
+//     conversion and its LDS stores, the row pass with both fence / barrier pairs, the R reads and the column FMAs
+//     (roll_col_zero instead of roll_col_body); the prefetch of the next sub-chunk, the emit part and the peak tracking
+//     stay.  The test is wave-uniform (kernel arguments and readfirstlane(dc), kept as two sub-chunk numbers per strip:
+//     padding above pad_top, padding from pad_bot on): the translation units are built with
+//     -structurizecfg-skip-uniform-regions and rely on it.  Rows past the tile's end (a ≥ n1 + l − 1) already read as fill,
+//     but a last sub-chunk that mixes them with in-frame rows is NOT padding: the test looks at frame rows only.
+//     Why the bits do not change:
+//       row pass      v = +0 for every input: each pair sum is +0, every Gaussian tap is positive, fma(+0, g, +0) = +0,
+//                     so R = (+0, +0).
+//       first term    of an output: the multiply gives (+0)·(s·g₊[0]) = ±0, the next FMA adds (+0)·(−s·g₋[0]) = ∓0: +0 for
+//                     either sign of s.  The odd output of the register pair starts from (+0)·T[−1] = +0.  "slot := +0" is
+//                     what the full body computes.
+//       later terms   fma(+0, t, a) = a for every a ≠ −0, and a = −0 cannot stand in an accumulator at a row boundary: a
+//                     finished (+, −) pair of zero products cancels to +0 under round-to-nearest, sums of non-zero terms that
+//                     cancel give +0 too, and the values do not underflow.  Taps are finite: no 0·inf.
+//     (tests/test_pad_rows_cpu.py states this in float32; tests/test_gpu_pad_rows.py compares the maps with the skip off.)
+//     Out of scope, on purpose: dc ≠ fill (R is a non-zero constant there, only the row pass could go, and the case is
+//     rare); rows inside the frame that happen to equal the fill; partially padded sub-chunks (in the row pass rows are
+//     lanes: nothing would be saved); dog_thin_kernel (it runs beside the strips and is shorter than they are); the ring,
+//     two-pass, fused and tiled kernels.  pdog_set_tuning "no_pad_skip" pins the full path.
+//
 // On gfx950 v_pk_fma_f32 issues at the same FLOP rate as v_fma_f32 (4 vs 2 cycles per
 // wave64, tools/ubench_valu.hip), so what counts is the number of lane-operations, and one
 // wave per SIMD already reaches ≈84 % of the packed-FMA rate: occupancy 2 waves/SIMD
@@ -40,9 +65,10 @@ constexpr int ROLL_CH = 8;   // rows per sub-chunk (16 measured equal on cfg3: t
 constexpr int ROLL_P = 8;    // row-pass outputs per lane
 constexpr int ROLL_TW = 64;  // strip width = lanes
 constexpr int ROLL_PR = 65;  // R pitch (f2)
-constexpr int ROLL_LMIN = 17, ROLL_LMAX = PDOG_ROLL_LMAX; // kernel lengths with a roll instance (l = 4m+1): the l + 7 accumulators, the row-pass
-                                              // windows and the loop state fit 168 VGPRs up to l = 81 (three waves per SIMD) and 256 from there to
-                                              // l = 149 (two; roll_lengths.def builds every length, none spills); longer kernels go to dog_twopass.hpp
+constexpr int ROLL_LMIN = 17, ROLL_LMAX = PDOG_ROLL_LMAX; // kernel lengths with a roll instance (l = 4m+1): the (l + 7 rounded up to 8)
+                                              // accumulator slots, the row-pass windows and the loop state fit 168 VGPRs up to l = 81 (three waves
+                                              // per SIMD) and 256 from there to l = 149 (two; roll_lengths.def builds every length, none spills:
+                                              // profiles/pad_skip_kernel_regs.txt); longer kernels go to dog_twopass.hpp
 __host__ __device__ constexpr int roll_waves(int L) { return L <= 81 ? 3 : 2; } // waves per SIMD the instance is compiled for
 // Kernel lengths whose instances can FOLD a single remainder column into the last strip (LaunchGeo::fold_r).  The second
 // row-pass variant costs ≈18 VGPRs: l = 65 (the reference's default target_width) absorbs them inside its three-waves budget
@@ -262,6 +288,16 @@ __device__ __forceinline__ void roll_col_body(f2 (&acc2)[roll_slots(L) / 2], con
     }
 }
 
+// Column pass of a PADDING-ONLY sub-chunk (roll_strip, "padding rows"): every R value is (+0, +0), so all the body would do
+// is restart the slot pairs of the even rows' first term (the tt == 0 multiply) at (+0, +0) and add exact zeros elsewhere.
+template <int L, int SC>
+__device__ __forceinline__ void roll_col_zero(f2 (&acc2)[roll_slots(L) / 2])
+{
+    constexpr int S = roll_slots(L), CH = ROLL_CH;
+#pragma unroll
+    for (int i = 0; i < CH; i += 2) acc2[((CH * SC + i) % S) / 2] = f2{0.f, 0.f};
+}
+
 // ABL: timing-only ablation bits (tools/tune): 1 = no column FMAs, 2 = no row pass, 4 = no staging
 // conversion/LDS writes, 8 = no global loads.  ABL != 0 gives wrong results by design.
 // One strip of one window, executed by ONE wave with wave-private LDS at `smem`: everything from the DC
@@ -362,6 +398,19 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     // tests, fill pre-load and 64-bit row multiply, ≈10 VALU instructions fewer per sub-chunk: 0.4–0.6 % SLOWER in a three-way
     // same-session comparison.  The kernel does not feel a handful of VALU instructions beside its 900 packed ones.)
     const int nsub = (NA + CH - 1) / CH;
+    // ---- padding rows (header comment): the per-sub-chunk test as two wave-uniform sub-chunk numbers — sc holds padding only
+    // when sc < pad_top (ti0 + 8·sc + 7 < 0) or sc >= pad_bot (ti0 + 8·sc >= fh); with the row test itself in the loop the
+    // folding l = 65 instances spilled 11 VGPRs ----
+    const bool pad_ok = (ABL & 15) == 0 && !g.no_pad_skip && __builtin_amdgcn_readfirstlane(dc) == g.fill;
+    // (a folding strip also stages frame column tj0 + 8·SB for its ninth output: that column must lie outside as well)
+    const bool strip_cols_out = tj0 + 8 * SB + ((FOLD_EXTRA && fold) ? 1 : 0) <= 0 || tj0 >= g.fw;
+    const int pad_top = !pad_ok ? 0 : strip_cols_out ? nsub : max(0, -ti0) / CH;
+    const int pad_bot = !pad_ok ? nsub : max(0, (g.fh - ti0 + CH - 1) >> 3);
+    // a folding strip owes the finishing kernel the R values of its ninth column for EVERY input row: the padding-only
+    // sub-chunks' (+0, +0) are stored here, ahead of the loop (inside it the store cost the l = 65 instances 5 VGPRs and spills)
+    if (FOLD_OK && fold)
+        for (int a = lane; a < NA; a += 64)
+            if (a < pad_top * CH || a >= pad_bot * CH) g.fold_r[(long long)b * NA + a] = f2{0.f, 0.f};
     uint32_t pre[SB / 4];
     load16(srow, pre);
     uint32_t pre_x = 0;
@@ -370,62 +419,69 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     const long long resp_base = (long long)b * g.n1 * g.n2;
 
     for (int sc = 0; sc < nsub; ++sc) {
+        // padding rows (see above): all 8 rows outside the frame, or a strip whose staged columns all are — wave-uniform
+        const bool pad_sc = sc < pad_top || sc >= pad_bot;
         // ---- stage this sub-chunk from the prefetched registers, request the next ----
         if (!(ABL & 4)) {
-            float *dst = A + roll_row_base(srow, L) + SB * sseg; // 16-byte aligned: ds_write_b128
-            const f2 ndc = f2{-(float)dc, -(float)dc};
+            if (!pad_sc) {
+                float *dst = A + roll_row_base(srow, L) + SB * sseg; // 16-byte aligned: ds_write_b128
+                const f2 ndc = f2{-(float)dc, -(float)dc};
 #pragma unroll
-            for (int q = 0; q < SB / 4; ++q) { // two pixels per v_pk_add_f32 (v_cvt_f32_ubyteN each): exact integers either way
-                const uint32_t word = pre[q];
-                const f2 v01 = f2{(float)(word & 0xffu), (float)((word >> 8) & 0xffu)} + ndc;
-                const f2 v23 = f2{(float)((word >> 16) & 0xffu), (float)(word >> 24)} + ndc;
-                *reinterpret_cast<f4 *>(dst + 4 * q) = f4{v01.x, v01.y, v23.x, v23.y};
+                for (int q = 0; q < SB / 4; ++q) { // two pixels per v_pk_add_f32 (v_cvt_f32_ubyteN each): exact integers either way
+                    const uint32_t word = pre[q];
+                    const f2 v01 = f2{(float)(word & 0xffu), (float)((word >> 8) & 0xffu)} + ndc;
+                    const f2 v23 = f2{(float)((word >> 16) & 0xffu), (float)(word >> 24)} + ndc;
+                    *reinterpret_cast<f4 *>(dst + 4 * q) = f4{v01.x, v01.y, v23.x, v23.y};
+                }
+                if (FOLD_EXTRA && fold && sseg == SEGS - 1)
+                    A[roll_row_base(srow, L) + 8 * SB] = (float)(extra_ok(sc * CH + srow) ? (int)pre_x : g.fill) - (float)dc;
             }
-            if (FOLD_EXTRA && fold && sseg == SEGS - 1)
-                A[roll_row_base(srow, L) + 8 * SB] = (float)(extra_ok(sc * CH + srow) ? (int)pre_x : g.fill) - (float)dc;
-            if (!(ABL & 8)) {
+            if (!(ABL & 8)) { // (also from a padding-only sub-chunk: the next one may be real)
                 load16((sc + 1) * CH + srow, pre);
                 if (FOLD_EXTRA && fold) pre_x = load_extra((sc + 1) * CH + srow);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier(); // the LDS traffic is wave-private: the fences' waits are all the ordering needed
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        // ---- row pass: rounds of 8 rows × 8 groups of 8 outputs ----
-        if (!(ABL & 2)) {
-            static_assert(RPASS == 1, "one row-pass round per sub-chunk");
-            const float *arow = A + roll_row_base(rr, L) + rgx * P;
-            f2 *dst = Rb + rr * ROLL_PR + rgx * P;
-            if (FOLD_OK && fold) {
-                f2 racc[P + 2];
-#pragma unroll
-                for (int o = 0; o < P + 2; ++o) racc[o] = f2{0.f, 0.f};
-                roll_row_pass<L, P + 1>(racc, arow, trow);
-#pragma unroll
-                for (int o = 0; o < P; ++o) dst[o] = racc[o];
-                // the last lane group's ninth output is window column 64·nstrips of input row sc·8 + rr
-                if (rgx == TW / P - 1 && sc * CH + rr < NA) g.fold_r[(long long)b * NA + sc * CH + rr] = racc[P];
-            } else {
-                f2 racc[P];
-#pragma unroll
-                for (int o = 0; o < P; ++o) racc[o] = f2{0.f, 0.f};
-                roll_row_pass<L>(racc, arow, trow);
-#pragma unroll
-                for (int o = 0; o < P; ++o) dst[o] = racc[o];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        // ---- column pass: 8 new R rows into the rolling accumulators ----
         f2 rv[CH];
+        if (!pad_sc) { // (a padding-only sub-chunk touches no LDS)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier(); // the LDS traffic is wave-private: the fences' waits are all the ordering needed
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // ---- row pass: rounds of 8 rows × 8 groups of 8 outputs ----
+            if (!(ABL & 2)) {
+                static_assert(RPASS == 1, "one row-pass round per sub-chunk");
+                const float *arow = A + roll_row_base(rr, L) + rgx * P;
+                f2 *dst = Rb + rr * ROLL_PR + rgx * P;
+                if (FOLD_OK && fold) {
+                    f2 racc[P + 2];
 #pragma unroll
-        for (int i = 0; i < CH; ++i) rv[i] = Rb[i * ROLL_PR + lane];
+                    for (int o = 0; o < P + 2; ++o) racc[o] = f2{0.f, 0.f};
+                    roll_row_pass<L, P + 1>(racc, arow, trow);
+#pragma unroll
+                    for (int o = 0; o < P; ++o) dst[o] = racc[o];
+                    // the last lane group's ninth output is window column 64·nstrips of input row sc·8 + rr
+                    if (rgx == TW / P - 1 && sc * CH + rr < NA) g.fold_r[(long long)b * NA + sc * CH + rr] = racc[P];
+                } else {
+                    f2 racc[P];
+#pragma unroll
+                    for (int o = 0; o < P; ++o) racc[o] = f2{0.f, 0.f};
+                    roll_row_pass<L>(racc, arow, trow);
+#pragma unroll
+                    for (int o = 0; o < P; ++o) dst[o] = racc[o];
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // ---- column pass: 8 new R rows into the rolling accumulators ----
+#pragma unroll
+            for (int i = 0; i < CH; ++i) rv[i] = Rb[i * ROLL_PR + lane];
+        }
         const int phase = sc % NBODY;
         const int sc_e = roll_epi_c0(g.n1) / 2 + 1; // first sub-chunk whose rows need no tap of the first block(s)
         auto emit = [&](auto SCc, auto QHIc, auto QLOc) {
             constexpr int SC = decltype(SCc)::value, QHI = decltype(QHIc)::value, QLO = decltype(QLOc)::value;
-            if (!(ABL & 1)) roll_col_body<L, SC, QHI, QLO>(acc2, rv, tcol);
+            if (pad_sc) roll_col_zero<L, SC>(acc2); // (harmless in a shortened body: the slots it resets there have no output)
+            else if (!(ABL & 1)) roll_col_body<L, SC, QHI, QLO>(acc2, rv, tcol);
             // outputs y = a − (l−1) for the 8 rows of this sub-chunk are complete.  A lane owns ONE
             // column and meets its rows in increasing y (= increasing column-major index), so a strict
             // '>' keeps the first maximum of the lane (findmax, :59); ties between lanes and strips

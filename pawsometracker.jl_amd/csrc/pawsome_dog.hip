@@ -81,6 +81,7 @@ struct Switches {
     bool no_roll_map = false;             // hard batches on the roll / ring kernels keep recomputing their candidates
     bool no_fold = false;                 // a single remainder column always goes to dog_thin_kernel
     bool fold_always = false;             // … always into the last strip, also below 8 strips per window
+    bool no_pad_skip = false;             // roll kernels: sub-chunks that hold padding only run the full path (dog_roll.hpp, "padding rows")
     bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
     bool measure_global = false;          // pdog_measure reads the frame itself instead of staging each position's pixel tile in LDS
     bool fault_inject = false;            // tests: one sub-window of a tiled chain never delivers its second frame's partial (the device-side waits must give up)
@@ -117,6 +118,7 @@ Switches read_switches()
     w.no_tiled = on("PDOG_NO_TILED");
     w.no_fold = on("PDOG_NO_FOLD");
     w.fold_always = on("PDOG_FOLD_ALWAYS");
+    w.no_pad_skip = on("PDOG_NO_PAD_SKIP");
     w.no_roll_map = on("PDOG_NO_ROLL_MAP");
     w.no_host_dc = on("PDOG_NO_HOST_DC");
     w.tiled_force = on("PDOG_TILED_FORCE");
@@ -618,6 +620,7 @@ LaunchGeo base_geo(const pdog_tracker *t, const Request &req)
     g.fh = req.fh ? req.fh : t->fh; g.fw = req.fw ? req.fw : t->fw;
     g.r1 = t->r1; g.r2 = t->r2; g.n1 = t->n1; g.n2 = t->n2;
     g.L = t->L; g.fill = t->fill; g.n = req.n;
+    g.no_pad_skip = t->sw.no_pad_skip;
     return g;
 }
 void use_partials(const pdog_tracker *t, LaunchGeo &g)
@@ -1508,6 +1511,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "no_roll_map") t->sw.no_roll_map = on;
     else if (k == "no_fold") t->sw.no_fold = on;
     else if (k == "fold_always") t->sw.fold_always = on;
+    else if (k == "no_pad_skip") t->sw.no_pad_skip = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "no_fused_c") {
