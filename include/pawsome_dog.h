@@ -35,6 +35,21 @@ extern "C" {
 
 #define PDOG_ABI_VERSION 1
 
+/* ---- frame layouts every entry point that takes frames accepts ----
+ * Frame k starts at frames + k*frame_stride, its rows lie row_stride bytes apart, a row's pixels are adjacent bytes.
+ *  - row_stride: frame_w ... PDOG_MAX_ROW_STRIDE.  Bytes between a row's last pixel and the next row (slack), and between
+ *    one frame's last row and the next frame (gap), are never taken for pixels and never written;
+ *  - the base address needs no alignment (a cropped view big[:, 3:, 5:] is a valid argument);
+ *  - frame_stride: any value >= 0.  It need not be a multiple of row_stride, nor reach h*row_stride: frames may overlap
+ *    (frame k = rows k*s ... of one tall image), and 0 makes every frame the same memory.
+ * A response depends on the pixel values only: the same pixels behind another layout give the same response bits and
+ * the same positions.  A row_stride outside its range, or a negative frame_stride, is PDOG_E_ARG before anything is
+ * launched; the text names PDOG_MAX_ROW_STRIDE where that was exceeded.
+ * The upper bound comes from the one-workgroup-per-window kernel, which keeps 32-bit byte offsets from its tile's first
+ * pixel: its tile has at most 160 KiB / (4 B * 23 floats per row) = 1780 rows (what fits its LDS for the shortest kernel,
+ * l = 5), and 1780 * 2^21 + 4096 < 2^32. */
+#define PDOG_MAX_ROW_STRIDE (1 << 21)
+
 enum pdog_status {
     PDOG_OK = 0,
     PDOG_E_ARG = 1,    /* bad argument (null pointer, non-positive size, ...) */

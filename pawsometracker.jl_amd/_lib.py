@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PAWSOME_DOG_LIB") or os.path.join(_HERE, "libpawsome_dog.so")
 
 PDOG_OK, PDOG_E_ARG, PDOG_E_HIP, PDOG_E_NODEV, PDOG_E_RANGE, PDOG_E_ALLOC = range(6)
+PDOG_MAX_ROW_STRIDE = 1 << 21   # include/pawsome_dog.h: the largest row stride an entry point accepts
 
 class PdogInfo(C.Structure):
     _fields_ = [

@@ -224,6 +224,13 @@ const Variant kVariants[] = {
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 constexpr size_t kMaxLds = 160 * 1024;
+// The fused kernel's interior staging path keeps 32-bit byte offsets from the tile's first pixel (dog_fused.hpp, rs32): at most
+// (NA - 1) * row_stride + 4 * FUSED_NT.  A fused instance only runs where its tile of NA rows fits LDS (fused_lds_bytes >=
+// fused_a_bytes = NA * pitch * 4, the pitch smallest for a one-column window under the shortest kernel, l = 5), which bounds NA;
+// PDOG_MAX_ROW_STRIDE (check_row_stride) bounds the other factor.  Every other family forms its addresses in 64 bits.
+constexpr long long kFusedMaxRows = (long long)(kMaxLds / (4 * (size_t)fused_pitch_a(1, 5)));
+static_assert(fused_a_bytes(1, 1, 5) >= 5 * fused_pitch_a(1, 5) * 4 && fused_pitch_a(1, 5) <= fusedc_pitch_a(1, 5), "the tile's LDS bytes are at least rows * pitch * 4");
+static_assert(kFusedMaxRows * (long long)PDOG_MAX_ROW_STRIDE + 4 * FUSED_NT < (1LL << 32), "PDOG_MAX_ROW_STRIDE: the fused kernel's 32-bit offsets would wrap");
 constexpr int kThinMax = 6; // remainder columns done by dog_thin_kernel instead of one more strip
 
 bool has_roll_instance(int L)
@@ -1634,7 +1641,7 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
                      int32_t out_ij[2], float *h_resp)
 {
     if (!t || !h_frame || !guess || !out_ij) return fail(PDOG_E_ARG, "pdog_detect_host: null pointer");
-    if (row_stride < t->fw) return fail(PDOG_E_ARG, "pdog_detect_host: row_stride < frame width");
+    if (int rc = check_row_stride("pdog_detect_host", t->fw, row_stride)) return rc;
     const TileFrame tile(t);
     if (!tile.holds(t, guess[0], guess[1])) return fail(PDOG_E_RANGE, "pdog_detect_host: guess outside the padded frame (reference: BoundsError)");
     HIP_TRY(hipSetDevice(t->device));
@@ -2084,7 +2091,7 @@ extern "C" int pdog_detect_chain(pdog_tracker *t, const uint8_t *d_frames, int64
                                  int n_frames, const int32_t start_guess[2], int32_t *d_out_ij)
 {
     if (!t || !d_frames || !start_guess || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chain: null pointer");
-    if (n_frames <= 0 || row_stride < t->fw) return fail(PDOG_E_ARG, "pdog_detect_chain: bad size/stride");
+    if (int rc = check_stack("pdog_detect_chain", t->fw, n_frames, row_stride, frame_stride)) return rc; // (before the start guess is queued)
     HIP_TRY(hipSetDevice(t->device));
     HIP_TRY(hipMemcpyAsync(t->d_small.get(), start_guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
     return pdog_detect_chains(t, d_frames, frame_stride, row_stride, n_frames, 1, t->d_small.get(), d_out_ij);

@@ -34,10 +34,19 @@ ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<doub
 // *max_len the longest.  PDOG_E_ARG in `who`'s name, outputs undefined, otherwise.
 int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, int n_clips, int n_frames, int32_t *out_len, int *max_len);
 // The test the entry points share for a stack of frames (and `counts_ok`: the entry point's own sizes); PDOG_E_ARG in `who`'s name.
+// Accepted layouts (include/pawsome_dog.h, "frame layouts"): rows fw … PDOG_MAX_ROW_STRIDE bytes apart, any non-negative
+// frame stride (overlapping frames and 0 included), any base address.
+inline int check_row_stride(const char *who, int fw, int64_t row_stride)
+{
+    if (row_stride < fw) return fail(PDOG_E_ARG, std::string(who) + ": bad size/stride (row_stride < frame width)");
+    if (row_stride > PDOG_MAX_ROW_STRIDE)
+        return fail(PDOG_E_ARG, std::string(who) + ": row_stride " + std::to_string((long long)row_stride) + " exceeds PDOG_MAX_ROW_STRIDE (" + std::to_string((long long)PDOG_MAX_ROW_STRIDE) + ")");
+    return PDOG_OK;
+}
 inline int check_stack(const char *who, int fw, int n_frames, int64_t row_stride, int64_t frame_stride, bool counts_ok = true)
 {
-    if (counts_ok && n_frames > 0 && row_stride >= fw && frame_stride >= 0) return PDOG_OK;
-    return fail(PDOG_E_ARG, std::string(who) + ": bad size/stride");
+    if (!(counts_ok && n_frames > 0 && frame_stride >= 0)) return fail(PDOG_E_ARG, std::string(who) + ": bad size/stride");
+    return check_row_stride(who, fw, row_stride);
 }
 void pack_tile_geo(const uint8_t *frame, int fh, int fw, int64_t row_stride, int fill, int L, int r1, int r2, int g1, int g2,
                    uint8_t *dst, int64_t pitch, bool stream = false);
