@@ -165,6 +165,7 @@ int pdog_set_exact(pdog_tracker *t, int on);
  *   "no_roll_map"  hard batches keep recomputing their refinement candidates
  *   "no_fold" / "fold_always"  a single remainder column always / never goes to the remainder-column kernel
  *   "no_pad_skip"  the roll kernels run their full path also on sub-chunks (8 tile rows of a strip) that hold padding only
+ *   "no_prune"     roll batches stay dense: no pre-pass, every strip computes every sub-chunk (pdog_get_prune_counts)
  *   "measure_global" pdog_measure reads the frame itself instead of staging each position's pixels in LDS (its path for l > 93)
  * Unknown key: PDOG_E_ARG.  Drains the tracker's stream. */
 int pdog_set_tuning(pdog_tracker *t, const char *key, int value);
@@ -412,5 +413,6 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
  * in device memory, and the chain (:163-169) over such a table of frame indices are declared in pawsome_video.h, which
  * is part of this ABI and of this header. */
 #include "pawsome_video.h"
+#include "pawsome_prune.h" /* kept ranges of the roll batch path: pdog_get_prune_counts, pdog_get_batch_maxima */
 
 #endif /* PAWSOME_DOG_H */

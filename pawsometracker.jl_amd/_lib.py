@@ -98,6 +98,14 @@ VIDEO_PROTOTYPES = {
     "pdog_clips_track_indexed": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _i, _p, _i, _p, _p]),
 }
 VIDEO_SYMBOLS = tuple(VIDEO_PROTOTYPES)
+
+# the same for include/pawsome_prune.h, which pawsome_dog.h includes too: kept ranges of the roll batch path
+# (tests/test_prune_cpu.py holds this table against that header)
+PRUNE_PROTOTYPES = {
+    "pdog_get_prune_counts": (_i, [_p, _pu64]),
+    "pdog_get_batch_maxima": (_i, [_p, _i, _p]),
+}
+PRUNE_SYMBOLS = tuple(PRUNE_PROTOTYPES)
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -142,7 +150,7 @@ def lib():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -218,6 +226,19 @@ class TrackerHandle(Handle):
         out = (C.c_uint64 * 4)()
         check(lib().pdog_get_exact_detail(self._h, out))
         return tuple(int(v) for v in out)
+
+    def prune_counts(self):
+        """(kept, total) (strip, sub-chunk) pairs of the batches that ran the bounding pre-pass — pdog_get_prune_counts."""
+        out = (C.c_uint64 * 2)()
+        check(lib().pdog_get_prune_counts(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def batch_maxima(self, n):
+        """Test hook (not stable ABI): FP32 maxima of the n windows of the last strip-kernel batch (numpy float32 [n]) — pdog_get_batch_maxima."""
+        import numpy as np
+        out = np.empty(int(n), np.float32)
+        check(lib().pdog_get_batch_maxima(self._h, int(n), C.c_void_p(out.ctypes.data)))
+        return out
 
     def kernel_for_batch(self, n):
         """Variant id of the kernel family a batch of n windows runs on (300 fused, 400 tiled, 200 two-pass, else info().variant)."""

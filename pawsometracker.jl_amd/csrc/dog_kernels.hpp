@@ -182,6 +182,9 @@ struct LaunchGeo {
     // values are bit-identical to what a strip would have produced.
     f2 *__restrict__ fold_r;
     int no_pad_skip;                     // roll kernels: padding-only sub-chunks run the full path (pdog_set_tuning "no_pad_skip")
+    // roll and thin kernels (dog_prune.hpp): on entry part_mask[b][slot] holds the slot's kept range of 8-row output blocks,
+    // (first | one past the last << 32), and only that range is computed (the struct's size does not change: this word was padding)
+    int prune;
 };
 
 constexpr int FOLD_GO = 5; // output rows per lane and pass of a folded remainder column (257 rows = 64 lanes × 5 + 1 …)

@@ -87,6 +87,13 @@ __host__ __device__ constexpr int roll_rs(int L) { return (8 * roll_sb(L) + 40 +
 __host__ __device__ constexpr int roll_row_base(int r, int L) { return r * roll_rs(L) + 4 * (((r & 1) ? 1 : 0) + ((r & 2) ? 8 : 0)); }
 __host__ __device__ constexpr size_t roll_lds_bytes(int L) { return (size_t)ROLL_CH * roll_rs(L) * 4 + (size_t)ROLL_CH * ROLL_PR * 8; }
 
+// KEPT RANGES (dog_prune.hpp; LaunchGeo::prune): a slot's pre-pass leaves the range [ba, bb) of 8-row output blocks that can
+// hold the window's peak or a near-tie.  Block j reads the input rows of sub-chunks j … j + prune_span(l) − 1; the range
+// needs sub-chunks ba … prune_sc_hi − 1.
+__host__ __device__ constexpr int prune_span(int L) { return (ROLL_CH + L - 1 + ROLL_CH - 1) / ROLL_CH; }
+__host__ __device__ constexpr int prune_tail(int L) { return (L - 1 + ROLL_CH - 1) / ROLL_CH; }
+__host__ __device__ constexpr int prune_sc_hi(int ba, int bb, int L, int nsub) { return bb > ba ? (bb + prune_tail(L) < nsub ? bb + prune_tail(L) : nsub) : ba; }
+
 // Re-derive a tap pointer through an empty asm: the scalar loads that use it cannot be hoisted above
 // this point (hoisted, every block's taps are live at once and the SGPRs spill through v_writelane).
 // A fake use + redefinition of an accumulator pair: the FMAs that feed it cannot be sunk below this
@@ -303,7 +310,14 @@ __device__ __forceinline__ void roll_col_zero(f2 (&acc2)[roll_slots(L) / 2])
 // One strip of one window, executed by ONE wave with wave-private LDS at `smem`: everything from the DC
 // level to the wave-level peak reduction.  (best, best_idx) are valid in lane 0 on return.
 // EPI ≥ 0: the instance for windows of height class EPI (roll_epi_class): statically shortened epilogue bodies too.
-template <int LT, bool RESP, int ABL, int EPI = -1>
+// PRUNE: the instance that honours a kept range (dog_prune.hpp).  A template flag, not a run-time branch: the two more uniform
+// values cost the l = 65 height-class instances, which sit at their 168-VGPR budget, 27 … 166 spilled VGPRs.  With the flag
+// the height-class instances compile as before, figure for figure; the other dense instances and the chain instances share
+// the loop's new start and the skipped-strip test with constant operands and move by at most 2 VGPRs and 2 SGPR spills
+// (l = 65 without a height class: 22 → 24 SGPR spills; three chain instances from l = 121 on spill one VGPR more) — all
+// inside their budgets (profiles/prune_kernel_regs.txt).  The PRUNE instances exist for EPI = −1 only (a kept range seldom
+// reaches the window's last rows, where the shortened epilogue bodies pay).
+template <int LT, bool RESP, int ABL, int EPI = -1, bool PRUNE = false>
 __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col,
                                            unsigned char *smem, const uint8_t *__restrict__ frame, int g1, int g2, int s,
                                            int b, int logical, Peak &peak_out, unsigned long long &mask_out)
@@ -411,14 +425,29 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     if (FOLD_OK && fold)
         for (int a = lane; a < NA; a += 64)
             if (a < pad_top * CH || a >= pad_bot * CH) g.fold_r[(long long)b * NA + a] = f2{0.f, 0.f};
+    // ---- kept range (dog_prune.hpp): two more wave-uniform sub-chunk numbers.  The loop runs over the sub-chunks
+    // [sc_lo, sc_hi) that hold the input rows of the kept output blocks.  Outputs above row y_lo = 8·sc_lo lack their first
+    // terms and are not fed to the peak; every output from y_lo on that the loop emits is complete (its last input row,
+    // y + l − 1, lies in the sub-chunk that emits it), so the few rows it may emit past the range's end are the window's own
+    // values and harmless.  Starting late needs no reset (every output's first term is a multiply), and the shortened
+    // prologue bodies stay right: they are chosen by the sub-chunk NUMBER and leave out only taps whose outputs lie above row 0 ----
+    static_assert(!PRUNE || (!RESP && ABL == 0 && EPI < 0), "kept ranges: the plain instances only");
+    int sc_lo = 0, sc_hi = nsub, y_lo = 0;
+    if constexpr (PRUNE) {
+        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + s];
+        const int ba = __builtin_amdgcn_readfirstlane((int)(unsigned)rng), bb = __builtin_amdgcn_readfirstlane((int)(unsigned)(rng >> 32));
+        sc_lo = ba;
+        sc_hi = prune_sc_hi(ba, bb, L, nsub);
+        y_lo = ba * CH;
+    }
     uint32_t pre[SB / 4];
-    load16(srow, pre);
+    load16(sc_lo * CH + srow, pre);
     uint32_t pre_x = 0;
-    if (FOLD_EXTRA && fold) pre_x = load_extra(srow);
+    if (FOLD_EXTRA && fold) pre_x = load_extra(sc_lo * CH + srow);
     const int rr = lane & 7, rgx = lane >> 3; // row-pass task: row rr, output group rgx
     const long long resp_base = (long long)b * g.n1 * g.n2;
 
-    for (int sc = 0; sc < nsub; ++sc) {
+    for (int sc = sc_lo; sc < sc_hi; ++sc) {
         // padding rows (see above): all 8 rows outside the frame, or a strip whose staged columns all are — wave-uniform
         const bool pad_sc = sc < pad_top || sc >= pad_bot;
         // ---- stage this sub-chunk from the prefetched registers, request the next ----
@@ -487,13 +516,13 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
             // '>' keeps the first maximum of the lane (findmax, :59); ties between lanes and strips
             // are settled by index in the reductions.  Column validity is applied once at the end.
             const int ybase = sc * CH - (L - 1);
-            if (ybase + CH > 0 && ybase < g.n1) {
-                const bool full = (ybase >= 0) && (ybase + CH <= g.n1); // wave-uniform
+            if (ybase + CH > y_lo && ybase < g.n1) { // (y_lo = 0 unless a kept range says otherwise)
+                const bool full = (ybase >= y_lo) && (ybase + CH <= g.n1); // wave-uniform
 #pragma unroll
                 for (int i = 0; i < CH; ++i) {
                     const int slot = ((CH * SC + i - (L - 1)) % S + S) % S;
                     const float v = (slot & 1) ? acc2[slot / 2].y : acc2[slot / 2].x;
-                    const bool rowok = full || ((ybase + i >= 0) && (ybase + i < g.n1));
+                    const bool rowok = full || ((ybase + i >= y_lo) && (ybase + i < g.n1));
                     if (RESP && rowok && lane < ws) g.resp[resp_base + (long long)(x0 + lane) * g.n1 + ybase + i] = v;
                     if (rowok) {
                         second = __builtin_amdgcn_fmed3f(v, best, second); // runner-up of the lane's column (exact mode)
@@ -554,14 +583,15 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     pk.best = best;
     pk.second = second;
     pk.idx = (x0 + lane) * g.n1 + best_y;
-    if (lane >= ws) peak_init(pk);
+    const bool skipped = sc_lo >= sc_hi; // an empty kept range: the partial is an initialised Peak and mask 0
+    if (lane >= ws || skipped) peak_init(pk);
     const float colbest = pk.best;
     peak_wave_reduce(pk);
     peak_out = pk;         // valid in lane 0
     // exact mode: which columns of the strip can hold a pixel within T of the window's maximum (≥ the strip's): the
     // refinement rescans only those
     const float sb = __shfl(pk.best, 0, 64);
-    mask_out = __builtin_amdgcn_ballot_w64(colbest >= sb - g.ex.T);
+    mask_out = skipped ? 0ull : __builtin_amdgcn_ballot_w64(colbest >= sb - g.ex.T);
 }
 
 
@@ -595,7 +625,7 @@ __device__ __attribute__((noinline)) void roll_strip_call(const LaunchGeo *gp, c
 // barrier), so that the strips of a window — which read each other's halo columns — run on one CU at one time.  The HBM
 // traffic did not move (553.6 vs 557.6 MB per cfg3 step: the 1.31× over the algorithmic bytes is the fetch granularity on
 // unaligned 321-byte rows, not re-fetched halos) and cfg3 ran 2 % slower (cfg4 0.6 % faster): dropped.
-template <int LT, bool RESP, int ABL = 0, int EPI = -1>
+template <int LT, bool RESP, int ABL = 0, int EPI = -1, bool PRUNE = false>
 __global__ __launch_bounds__(64, roll_waves(LT)) void dog_roll_kernel(const LaunchGeo g, const f2 *__restrict__ taps_row,
                                                                       const f2 *__restrict__ taps_col)
 {
@@ -611,7 +641,7 @@ __global__ __launch_bounds__(64, roll_waves(LT)) void dog_roll_kernel(const Laun
     const uint8_t *__restrict__ frame = g.frames + (long long)fidx * g.frame_stride;
     Peak pk;
     unsigned long long mask;
-    roll_strip<LT, RESP, ABL, EPI>(g, taps_row, taps_col, smem, frame, g1, g2, s, b, logical, pk, mask);
+    roll_strip<LT, RESP, ABL, EPI, PRUNE>(g, taps_row, taps_col, smem, frame, g1, g2, s, b, logical, pk, mask);
     if (threadIdx.x == 0) {
         g.part_mask[b * g.nslots + s] = mask;
         g.part_val[b * g.nslots + s] = pk.best;
@@ -816,6 +846,18 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
         dc = dc_from_sum(tot, g.fill);
     }
     const float fdc = (float)dc;
+    // ---- kept range (dog_prune.hpp): output rows [y_lo, y_hi) and the input rows [a_lo, a_hi) they read; an empty range
+    // leaves an initialised Peak ----
+    int a_lo = 0, a_hi = NA, y_lo = 0, y_hi = g.n1;
+    if (!RESP && g.prune) {
+        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + g.nstrips + rc];
+        const int ba = (int)(unsigned)rng, bb = (int)(unsigned)(rng >> 32);
+        y_lo = ba * ROLL_CH;
+        y_hi = bb > ba ? min(g.n1, bb * ROLL_CH) : y_lo;
+        a_lo = y_lo;
+        a_hi = bb > ba ? y_hi + L - 1 : a_lo;
+    }
+    const int na = a_hi - a_lo; // input rows to stage
 
     // ---- the column's input patch, NA rows × l pixels, → LDS bytes: a dword per item, loaded unconditionally at an
     // address clamped into the frame (a clamped dword still holds every in-frame byte its item needs, at a shifted
@@ -827,16 +869,16 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
     const int gj0 = wj0 + x; // frame col of input k = 0
     if (ti0 >= 0 && ti0 + NA <= g.fh && gj0 >= 0 && gj0 + TP <= g.fw) { // the whole patch inside the frame (workgroup-uniform): a plain copy
 #pragma unroll 4
-        for (int e = tid; e < NA * TQ; e += NT) {
-            const int a = e / TQ, q = e - a * TQ;
+        for (int e = tid; e < na * TQ; e += NT) {
+            const int a = a_lo + e / TQ, q = e - (a - a_lo) * TQ;
             uint32_t w;
             __builtin_memcpy(&w, frame + (long long)(ti0 + a) * g.row_stride + gj0 + 4 * q, 4);
             *reinterpret_cast<uint32_t *>(tile + a * TP + 4 * q) = w;
         }
     } else if (g.fw >= 4) {
 #pragma unroll 4
-        for (int e = tid; e < NA * TQ; e += NT) {
-            const int a = e / TQ, q = e - a * TQ;
+        for (int e = tid; e < na * TQ; e += NT) {
+            const int a = a_lo + e / TQ, q = e - (a - a_lo) * TQ;
             const int gi = ti0 + a, gj = gj0 + 4 * q;
             const int gjc = min(max(gj, 0), g.fw - 4);
             uint32_t w;
@@ -852,15 +894,15 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
             *reinterpret_cast<uint32_t *>(tile + a * TP + 4 * q) = o;
         }
     } else {
-        for (int e = tid; e < NA * TP; e += NT) {
-            const int a = e / TP, cc = e - a * TP;
+        for (int e = tid; e < na * TP; e += NT) {
+            const int a = a_lo + e / TP, cc = e - (a - a_lo) * TP;
             const int gi = ti0 + a, gj = gj0 + cc;
-            tile[e] = (gi >= 0 && gi < g.fh && gj >= 0 && gj < g.fw) ? frame[(long long)gi * g.row_stride + gj] : (uint8_t)g.fill;
+            tile[a * TP + cc] = (gi >= 0 && gi < g.fh && gj >= 0 && gj < g.fw) ? frame[(long long)gi * g.row_stride + gj] : (uint8_t)g.fill;
         }
     }
     __syncthreads();
     // ---- row pass: R[a] for input rows a = tid, tid + 256, … (same operation order as the strips: pairs k ascending, centre last) ----
-    for (int a = tid; a < NA; a += NT) {
+    for (int a = a_lo + tid; a < a_hi; a += NT) {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(tile + a * TP);
         float v[L];
 #pragma unroll
@@ -887,7 +929,7 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
     // ---- column pass + argmax: outputs y = tid, tid + 256, … ----
     Peak pk;
     peak_init(pk);
-    for (int y = tid; y < g.n1; y += NT) {
+    for (int y = y_lo + tid; y < y_hi; y += NT) {
         float acc = 0.f;
 #pragma unroll 13
         for (int t = 0; t < L; ++t) {

@@ -8,6 +8,7 @@
 #include "pdog_host.hpp"
 #include "dog_kernels.hpp"
 #include "dog_roll.hpp"
+#include "dog_prune.hpp"
 #include "dog_twopass.hpp"
 #include "dog_fused.hpp"
 #include "dog_exact.hpp"
@@ -49,6 +50,7 @@ namespace pdog {
 #define PDOG_ROLL_L(LT)                                                                                          \
     extern template __global__ void dog_roll_kernel<LT, false, 0>(const LaunchGeo, const f2 *, const f2 *);      \
     extern template __global__ void dog_roll_kernel<LT, true, 0>(const LaunchGeo, const f2 *, const f2 *);       \
+    extern template __global__ void dog_roll_kernel<LT, false, 0, -1, true>(const LaunchGeo, const f2 *, const f2 *); \
     extern template __global__ void dog_thin_kernel<LT, false>(const LaunchGeo, const f2 *, const f2 *);         \
     extern template __global__ void dog_thin_kernel<LT, true>(const LaunchGeo, const f2 *, const f2 *);          \
     extern template __global__ void dog_chain_kernel<LT>(const ChainGeo, const f2 *, const f2 *);                \
@@ -82,6 +84,7 @@ struct Switches {
     bool no_fold = false;                 // a single remainder column always goes to dog_thin_kernel
     bool fold_always = false;             // … always into the last strip, also below 8 strips per window
     bool no_pad_skip = false;             // roll kernels: sub-chunks that hold padding only run the full path (dog_roll.hpp, "padding rows")
+    bool no_prune = false;                // roll batches stay dense: no pre-pass, no kept ranges (dog_prune.hpp)
     bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
     bool measure_global = false;          // pdog_measure reads the frame itself instead of staging each position's pixel tile in LDS
     bool fault_inject = false;            // tests: one sub-window of a tiled chain never delivers its second frame's partial (the device-side waits must give up)
@@ -119,6 +122,7 @@ Switches read_switches()
     w.no_fold = on("PDOG_NO_FOLD");
     w.fold_always = on("PDOG_FOLD_ALWAYS");
     w.no_pad_skip = on("PDOG_NO_PAD_SKIP");
+    w.no_prune = on("PDOG_NO_PRUNE");
     w.no_roll_map = on("PDOG_NO_ROLL_MAP");
     w.no_host_dc = on("PDOG_NO_HOST_DC");
     w.tiled_force = on("PDOG_TILED_FORCE");
@@ -174,6 +178,7 @@ struct Variant {
     typedef void (*chain_table_fn)(const ChainTableGeo, const f2 *, const f2 *);
     chain_table_fn chain_table = nullptr; // … its instance that walks a frame table
     bool fused = false;        // dog_fused.hpp: one workgroup per window, whole tile in LDS
+    kernel_fn fn_prune = nullptr; // the roll instance that honours kept ranges (dog_prune.hpp)
     int tw() const { return P * XG; }
     int ring(int L) const { return LT ? ring_rows(CH, LT, Q) : ring_rows(CH, L, Q); }
     int pa(int L) const { return pitch_a(tw() + L - 1); }
@@ -190,7 +195,8 @@ struct Variant {
 #define PDOG_ROLL_VARIANT(id, LT) \
     Variant { id, ROLL_P, ROLL_TW / ROLL_P, ROLL_CH, ROLL_CH, LT, 64, (kernel_fn)dog_roll_kernel<LT, false>, \
               (kernel_fn)dog_roll_kernel<LT, true>, true, (kernel_fn)dog_thin_kernel<LT, false>, \
-              (kernel_fn)dog_thin_kernel<LT, true>, 0, dog_chain_kernel<LT>, dog_chain_kernel<LT, true> }
+              (kernel_fn)dog_thin_kernel<LT, true>, 0, dog_chain_kernel<LT>, dog_chain_kernel<LT, true>, false, \
+              (kernel_fn)dog_roll_kernel<LT, false, 0, -1, true> }
 
 const Variant kVariants[] = {
     // runtime-L (any target_width)
@@ -287,6 +293,12 @@ struct pdog_tracker {
     unsigned flag_last = 0, win_last = 0, win_launched = 0; // flagged / finished windows last seen (h_pinned[6], [7]); windows handed to finishing kernels so far
     int flag_calm = 0;
     bool roll_map = false;
+    // kept ranges on the roll family's batch path (dog_prune.hpp; launch_strips, "pruning policy")
+    double K_norm = 0;                       // ‖K‖₂ of the dense kernel, rounded up (dog_kernel_norm_up)
+    DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] arrivals of the pre-pass in flight
+    unsigned prune_kept_last = 0, prune_total_last = 0; // the published counts last seen (h_pinned[8], [9])
+    int prune_sleep = 0;                     // batches left to run dense before the next probe
+    int last_n = 0, last_nslots = 0;         // windows and partial slots per window of the last launch_strips batch (pdog_get_batch_maxima)
     DeviceBuffer<float> d_map; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
     DeviceBuffer<int> d_dc;    // [cap] DC levels, then [cap] the windows' own V (exact mode)
     DeviceBuffer<int> d_counter; // [kLowLatMax] zero between launches: delivered column-pass partials per window (low-latency two-pass)
@@ -321,7 +333,8 @@ struct pdog_tracker {
     DeviceBuffer<uint8_t> d_frame;
     DeviceBuffer<int32_t> d_small; // [0..1] guess, [2..3] result
     // pinned, host-coherent, device-mapped mailbox: [0..1] guess, [2..3] result, [4] completion ticket of the functor,
-    // [5] raised by kernels (drain_and_check), [6] / [7] flagged / finished windows (launch_strips)
+    // [5] raised by kernels (drain_and_check), [6] / [7] flagged / finished windows (launch_strips), [8] / [9] kept / total
+    // (slot, sub-chunk) pairs of the pre-pass (one 64-bit word: dog_prune.hpp)
     PinnedBuffer<int32_t> h_pinned{hipHostMallocMapped | hipHostMallocCoherent};
     int32_t ticket = 0;
     DeviceBuffer<float> d_resp;
@@ -1101,6 +1114,34 @@ int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticke
     return launch_finish(t, g, fin);
 }
 
+// ---- pruning policy (dog_prune.hpp) ----
+// The pre-pass pays where it lets the strips skip more than it costs.  Measured on the flagship batch, kernel trace of
+// bench.py (profiles/prune_profile_this.txt, profiles/prune_profile_parent.txt): dog_prune_kernel takes 0.474 ms beside the
+// dense roll kernel's 1.314 ms, 36 % of it (kPrunePrePct), so a batch that keeps more than 64 % of its (slot, sub-chunk) pairs
+// (kPruneBreakEvenPct) is better off dense.  Noise-only windows and heavy texture are such batches (nothing can be excluded).
+// The pre-pass publishes its cumulative kept / total counts through host-coherent memory, as the finishing kernel publishes
+// its flagged count; when the pairs counted since the last look kept more than the break-even share, the next
+// kPruneProbeEvery batches run dense, then one batch probes again.  Nothing here waits for the GPU.
+constexpr int kPrunePrePct = 36;
+constexpr int kPruneBreakEvenPct = 100 - kPrunePrePct;
+constexpr int kPruneProbeEvery = 64;
+constexpr size_t kPruneMaxLds = 64 * 1024; // (the pre-pass's dynamic LDS without raising the kernel's limit; larger windows stay dense)
+bool use_pruning(pdog_tracker *t, const Variant &v, bool want_resp, int nslots)
+{
+    // dense: the response-writing instances, pdog_set_exact(t, 2) (infinite thresholds), "no_prune", every other kernel family
+    if (!v.roll || !v.fn_prune || want_resp || t->exact_all || t->sw.no_prune || prune_lds(t->n1, t->n2, t->L, nslots).total > kPruneMaxLds) return false;
+    const unsigned long long pub = __atomic_load_n(reinterpret_cast<const unsigned long long *>(t->h_pinned.get() + 8), __ATOMIC_ACQUIRE);
+    const unsigned kept = (unsigned)pub, total = (unsigned)(pub >> 32); // (low halves of cumulative counts: differences wrap correctly)
+    const long long dk = (long long)(unsigned)(kept - t->prune_kept_last), dt = (long long)(unsigned)(total - t->prune_total_last);
+    if (dt > 0) {
+        t->prune_kept_last = kept;
+        t->prune_total_last = total;
+        t->prune_sleep = dk * 100 > dt * kPruneBreakEvenPct ? kPruneProbeEvery : 0;
+    }
+    if (t->prune_sleep > 0) { --t->prune_sleep; return false; }
+    return true;
+}
+
 // The tracker's batch kernel: one wave (roll) or workgroup (ring) per strip of every window, the thin remainder columns beside
 // them, then the finishing kernel.  `g` arrives as launch_detect filled it.
 int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
@@ -1139,9 +1180,22 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     // 49 packed instructions per sub-chunk) and the finishing kernel gains the column pass — +2.7 % per cfg3 step (4 strips per
     // window), −0.8 % per cfg4 step (8 strips).  A variant that kept the R column in the strip's LDS and ran the column pass in
     // the strip's own wave cost a wave per SIMD (12.9 KB per wave) and +5 %.  So: folded from 8 strips per window on.
-    const bool fold = v.roll && roll_folds(v.LT) && t->nthin == 1 && !want_resp && !t->sw.no_fold && (t->nstrips >= 8 || t->sw.fold_always) &&
+    const bool prune = use_pruning(t, v, want_resp, g.nslots);
+    const bool fold = v.roll && roll_folds(v.LT) && t->nthin == 1 && !want_resp && !prune && !t->sw.no_fold && (t->nstrips >= 8 || t->sw.fold_always) &&
                       (size_t)FINISH_WPB * fold_wave_lds <= kMaxLds - 1024;
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
+    if (prune) { // the pre-pass leaves every slot's kept range in part_mask, ahead of the strips and (through the fork) the thin kernel
+        PruneGeo pg;
+        pg.g = g;
+        pg.kinv = 255.0 / t->K_norm;
+        pg.tmax = std::max(g.ex.T, g.ex.T_rescan);
+        pg.darker = t->darker;
+        pg.stat = t->d_prune_stat.get();
+        pg.host = reinterpret_cast<unsigned long long *>(t->h_pinned.device() + 8);
+        hipLaunchKernelGGL(dog_prune_kernel, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
+        HIP_TRY(hipGetLastError());
+        g.prune = 1;
+    }
     if (fold) {
         if (int rc = t->d_fold_r.reserve((size_t)n * NA, &t->stream)) return rc;
         g.fold_r = t->d_fold_r.get();
@@ -1161,8 +1215,8 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         (void)raise_lds_limit((const void *)(want_resp ? v.fn_resp : v.fn), lds_bytes);
     }
 #endif
-    kernel_fn fn = want_resp ? v.fn_resp : v.fn;
-    if (!want_resp && v.roll && v.LT == 65 && v.id == 100) { // instances with statically shortened epilogue bodies for the common window heights
+    kernel_fn fn = want_resp ? v.fn_resp : prune ? v.fn_prune : v.fn;
+    if (!want_resp && !prune && v.roll && v.LT == 65 && v.id == 100) { // instances with statically shortened epilogue bodies for the common window heights
         const int cls = roll_epi_class(t->n1, 65);
 #define PDOG_EPI_PICK(C) if (cls == C) fn = (kernel_fn)dog_roll_kernel<65, false, 0, C>;
         PDOG_EPI_CLASSES(PDOG_EPI_PICK)
@@ -1173,6 +1227,8 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     if (t->nthin && !fold) HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0)); // join before the strip combine
     // roll: 64-column strips over the first `covered` columns, the last one shifted left to stay inside; ring: tw() columns each
     const int covered = t->nthin ? t->thin_x0 : t->n2;
+    t->last_n = n;
+    t->last_nslots = g.nslots;
     Finish fin;
     fin.slot_w = v.tw();
     if (v.roll) fin.slot_last = std::max(0, covered - v.tw());
@@ -1351,7 +1407,7 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
         if (int rc = upload(t->d_taps_roll, tab)) return rc;
     }
     if (int rc = t->d_small.reserve(4, nullptr)) return rc;
-    if (int rc = t->h_pinned.reserve(8, nullptr, true)) return rc;
+    if (int rc = t->h_pinned.reserve(10, nullptr, true)) return rc;
     {
         // exact mode (dog_exact.hpp): the reference's dense kernel in Float64, built exactly as :41-43 builds it
         // (K = dir·(g₊⊗g₊ − g₋⊗g₋), column-major), and the decision threshold T = 2δ, δ = u·(6l + 4) for |pixel − dc| ≤ 255
@@ -1364,6 +1420,8 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
             const ExactFactors ef = exact_factors(gp, gm);
             t->F_sym_int = ef.sym_int; t->F_sym_sep = ef.sym_sep; t->F_ring = ef.ring; t->F_rescan = ef.rescan;
         }
+        t->K_norm = dog_kernel_norm_up(gp, gm);
+        if (int rc = t->d_prune_stat.reserve(4, nullptr, true)) return rc;
         if (int rc = t->d_ref_stat.reserve(16, nullptr, true)) return rc; // [4..7] unused, [8..15]: phase cycles of the refinement (diagnostic build)
         {
             std::vector<double> g2(2 * (size_t)t->L);
@@ -1519,6 +1577,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "no_fold") t->sw.no_fold = on;
     else if (k == "fold_always") t->sw.fold_always = on;
     else if (k == "no_pad_skip") t->sw.no_pad_skip = on;
+    else if (k == "no_prune") t->sw.no_prune = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "no_fused_c") {
@@ -1546,6 +1605,28 @@ int pdog_get_exact_detail(pdog_tracker *t, uint64_t out[4])
     std::fprintf(stderr, "pdog refine phases (shader cycles, thread 0): setup %llu, tile %llu, row32 %llu, col32 %llu, row64 %llu, cand64 %llu, verdict %llu\n",
                  v[8], v[9], v[10], v[11], v[12], v[13], v[14]);
 #endif
+    return PDOG_OK;
+}
+
+int pdog_get_prune_counts(pdog_tracker *t, uint64_t out[2])
+{
+    if (!t || !out) return fail(PDOG_E_ARG, "pdog_get_prune_counts: null pointer");
+    if (int rc = drain_and_check(t, "pdog_get_prune_counts")) return rc;
+    unsigned long long v[2];
+    HIP_TRY(hipMemcpy(v, t->d_prune_stat.get(), sizeof v, hipMemcpyDeviceToHost));
+    out[0] = (uint64_t)v[0];
+    out[1] = (uint64_t)v[1];
+    return PDOG_OK;
+}
+
+int pdog_get_batch_maxima(pdog_tracker *t, int n, float *h_out)
+{
+    if (!t || !h_out || n <= 0) return fail(PDOG_E_ARG, "pdog_get_batch_maxima: bad argument");
+    if (int rc = drain_and_check(t, "pdog_get_batch_maxima")) return rc;
+    if (n != t->last_n || t->last_nslots <= 0) return fail(PDOG_E_ARG, "pdog_get_batch_maxima: the last batch on the strip kernels had another size (or there was none)");
+    std::vector<float> pv((size_t)n * t->last_nslots);
+    HIP_TRY(hipMemcpy(pv.data(), t->d_part_val.get(), sizeof(float) * pv.size(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < n; ++b) h_out[b] = *std::max_element(pv.begin() + (size_t)b * t->last_nslots, pv.begin() + (size_t)(b + 1) * t->last_nslots);
     return PDOG_OK;
 }
 

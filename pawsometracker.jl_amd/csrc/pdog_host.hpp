@@ -29,6 +29,7 @@ void gaussian_1d(double s, int l, double *g);                // KernelFactors.ga
 void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, double *K); // :41-43, column-major
 struct ExactFactors { double sym_int, sym_sep, ring, rescan; };
 ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm); // exact mode's FP32 error-bound factors
+double dog_kernel_norm_up(const std::vector<double> &gp, const std::vector<double> &gm);  // ‖K‖₂ of the dense kernel, rounded up (dog_prune.hpp's bound)
 // A frame table (include/pawsome_video.h) checked on the host, before anything is launched: every entry below n_frames,
 // negative entries only as the tail of a row.  out_len[c] = steps of clip c (its row's leading non-negative entries),
 // *max_len the longest.  PDOG_E_ARG in `who`'s name, outputs undefined, otherwise.

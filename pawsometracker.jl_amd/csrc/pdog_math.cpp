@@ -83,6 +83,23 @@ ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<doub
     return f;
 }
 
+// ‖K‖₂ (Frobenius) of the dense kernel K = g₊⊗g₊ − g₋⊗g₋, for the pre-pass's Cauchy–Schwarz bound (dog_prune.hpp):
+// ‖K‖₂² = (Σg₊²)² + (Σg₋²)² − 2(Σg₊g₋)², in double from the tracker's own f32-rounded taps — and from the Float64 taps the
+// error bound δ is stated against; the larger of the two, rounded UP to the next float.
+double dog_kernel_norm_up(const std::vector<double> &gp, const std::vector<double> &gm)
+{
+    auto norm = [&](bool f32) {
+        double pp = 0, mm = 0, pm = 0;
+        for (size_t k = 0; k < gp.size(); ++k) {
+            const double a = f32 ? (double)(float)gp[k] : gp[k], b = f32 ? (double)(float)gm[k] : gm[k];
+            pp += a * a; mm += b * b; pm += a * b;
+        }
+        return std::sqrt(std::max(0.0, pp * pp + mm * mm - 2.0 * pm * pm));
+    };
+    const double n = std::max(norm(true), norm(false));
+    return (double)std::nextafter((float)n, 2.0f); // (the float nearest to n may lie below it; its successor does not)
+}
+
 // One window's padded tile, (n1+l-1) rows of `pitch` bytes: the frame rectangle the functor reads, with the
 // PaddedView fill (:48) materialised wherever the rectangle leaves the frame.  Tile row a, column b is the
 // padded frame at 1-based (g1 - r1 - l÷2 + a, g2 - r2 - l÷2 + b).

@@ -10,6 +10,7 @@ namespace pdog {
 #define PDOG_ROLL_L(LT)                                                                                   \
     template __global__ void dog_roll_kernel<LT, false, 0>(const LaunchGeo, const f2 *, const f2 *);      \
     template __global__ void dog_roll_kernel<LT, true, 0>(const LaunchGeo, const f2 *, const f2 *);       \
+    template __global__ void dog_roll_kernel<LT, false, 0, -1, true>(const LaunchGeo, const f2 *, const f2 *); \
     template __global__ void dog_thin_kernel<LT, false>(const LaunchGeo, const f2 *, const f2 *);         \
     template __global__ void dog_thin_kernel<LT, true>(const LaunchGeo, const f2 *, const f2 *);          \
     template __global__ void dog_chain_kernel<LT>(const ChainGeo, const f2 *, const f2 *);                \
