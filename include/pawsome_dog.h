@@ -414,5 +414,8 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
  * is part of this ABI and of this header. */
 #include "pawsome_video.h"
 #include "pawsome_prune.h" /* kept ranges of the roll batch path: pdog_get_prune_counts, pdog_get_batch_maxima */
+/* the overlay over a frame table and for several targets: pdog_diag_set_targets, pdog_diag_get_targets,
+ * pdog_diag_render_indexed.  On a handle set to several targets pdog_diag_render above returns PDOG_E_ARG. */
+#include "pawsome_overlay.h"
 
 #endif /* PAWSOME_DOG_H */

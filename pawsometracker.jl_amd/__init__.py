@@ -8,4 +8,4 @@ from .tracker import (DEFAULT_STOP, Tracker, fix_window_size, fps_table, get_gue
                       get_start_ij_and_tracker, guess_window_size, mode, subpixel, time_axis, track_clips, track_frames,
                       track_segments, track_video)
 from .batch import BatchTracker, GroupTracker, gather_positions, mode_device, shard_range  # noqa: F401
-from .diagnose import DIAG_SIZE, Diagnose, diag_point  # noqa: F401
+from .diagnose import DIAG_MAX_TARGETS, DIAG_SIZE, Diagnose, diag_point  # noqa: F401

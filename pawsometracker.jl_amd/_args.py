@@ -74,3 +74,34 @@ def host_table(v, name):
     if a.size and (a.min() < -2**31 or a.max() >= 2**31):
         raise ValueError(f"{name}: entries beyond int32")
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def host_steps(v, name):
+    """One row of a frame table — a sequence, a numpy array or a tensor of integers [n_steps] — as a contiguous host int32
+    array.  Its entries are the library's to judge, as for host_table."""
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v)
+    if a.ndim != 1:
+        raise ValueError(f"{name}: shape {a.shape}, expected (n_steps,)")
+    if a.size == 0:
+        return np.zeros(0, np.int32)
+    return host_table(a[None, :], name)[0]
+
+
+def device_positions(t, name, n_steps, device=None):
+    """Positions of several targets as the overlay reads them: an int32 cuda tensor [n_targets, n_steps, 2] whose pairs and steps
+    lie densely (strides 1 and 2) and whose targets lie an even number of words >= 2 * n_steps apart — a column slice
+    out[:, k0:k1] of a chains result as it lies.  Returns the distance between two targets in positions."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 3:
+        raise TypeError(f"{name} must be an int32 cuda tensor [n_targets, n_steps, 2]")
+    if t.shape[0] < 1 or t.shape[1] != n_steps or t.shape[2] != 2:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected (n_targets, {n_steps}, 2)")
+    if t.stride(2) != 1 or (n_steps > 1 and t.stride(1) != 2):
+        raise ValueError(f"{name}: pairs and steps must lie densely (strides 2 and 1), not {t.stride(1)} and {t.stride(2)}")
+    stride = t.stride(0) if t.shape[0] > 1 else max(2 * n_steps, 2)      # (one target: the stride is never used)
+    if stride < 2 * n_steps or stride % 2:
+        raise ValueError(f"{name}: targets must lie an even number of words >= {2 * n_steps} apart, not {stride}")
+    _on_device(t, name, device)
+    return stride // 2

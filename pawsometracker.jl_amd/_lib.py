@@ -106,6 +106,16 @@ PRUNE_PROTOTYPES = {
     "pdog_get_batch_maxima": (_i, [_p, _i, _p]),
 }
 PRUNE_SYMBOLS = tuple(PRUNE_PROTOTYPES)
+
+# the same for include/pawsome_overlay.h, the third header pawsome_dog.h includes: the overlay over a frame table and for
+# several targets (tests/test_overlay_cpu.py holds this table against that header)
+OVERLAY_PROTOTYPES = {
+    "pdog_diag_set_targets": (_i, [_p, _i]),
+    "pdog_diag_get_targets": (_i, [_p, _pi]),
+    "pdog_diag_render_indexed": (_i, [_p, _p, _p, _i64, _i64, _i, _i, _i, _p, _i, _p, _i64, _i, _p]),
+}
+OVERLAY_SYMBOLS = tuple(OVERLAY_PROTOTYPES)
+DIAG_MAX_TARGETS = 1024      # PDOG_DIAG_MAX_TARGETS
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -150,7 +160,7 @@ def lib():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

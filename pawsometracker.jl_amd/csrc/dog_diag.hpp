@@ -13,11 +13,20 @@
 //                            so overlapping pixels need no order.  Workgroup 0 of the call's last launch also writes the
 //                            trace state the next call starts from (double-buffered: the state it reads stays intact).
 //
+// Over a frame table and several targets (include/pawsome_overlay.h):
+//   dog_diag_resize_kernel<·, TABLE>  output k is frame table[k] of the stack: one uniform load per workgroup.  The table
+//                            travels in DiagResizeTableGeo, which derives from the plain argument struct, so the two plain
+//                            instances are passed the bytes they were passed before.
+//   dog_diag_overlay_targets_kernel   workgroups over (step, target): workgroup (k, t) draws target t's segments and dot
+//                            onto output k, from target t's positions (ij_stride positions apart) and target t's 99
+//                            inherited points; workgroup (0, t) of the call's last launch writes target t's next state.
+//
 // Every scaled point lies in [0, 360] × [0, 640] (positions are clamped into the frame first), every write is
 // checked against the buffer, and a segment has at most 641 steps.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -42,6 +51,10 @@ struct DiagResizeGeo {
     uint8_t *out;               // first output frame of this launch
 };
 
+struct DiagResizeTableGeo : DiagResizeGeo { // frames: frame 0 of the stack
+    const int32_t *table;       // frame index of this launch's first output
+};
+
 struct DiagOverlayGeo {
     const int32_t *ij;          // the call's 1-based positions, n x 2
     const int2 *hist_in;        // the last hcnt scaled points before the call, oldest first
@@ -51,6 +64,10 @@ struct DiagOverlayGeo {
     int h, w;
     double ry, rx;              // 360 / h, 640 / w (host)
     int color;
+};
+
+struct DiagOverlayTargetsGeo : DiagOverlayGeo { // ij, hist_in, hist_out: target 0's; target t's hist lies t * kDiagHist further
+    int64_t ij_stride;          // positions between two targets' rows of ij
 };
 
 // one output index I (1-based) -> first tap, second tap (= first where its weight is 0), weight of the second
@@ -64,8 +81,9 @@ __device__ __forceinline__ void diag_tap(int I, double s, double off, int n, int
     i1 = f == 0.0 ? i0 : min(i0 + 1, n);
 }
 
-template <bool kAligned>
-__global__ __launch_bounds__(kDiagResizeThreads) void dog_diag_resize_kernel(const DiagResizeGeo g, const double *lut)
+template <bool kAligned, bool TABLE = false>
+__global__ __launch_bounds__(kDiagResizeThreads) void dog_diag_resize_kernel(const std::conditional_t<TABLE, DiagResizeTableGeo, DiagResizeGeo> g,
+                                                                             const double *lut)
 {
     __shared__ double p[256]; // raw / 255.0, computed on the host (assumption (a))
     p[threadIdx.x] = lut[threadIdx.x];
@@ -77,7 +95,9 @@ __global__ __launch_bounds__(kDiagResizeThreads) void dog_diag_resize_kernel(con
     int i0, i1;
     double fy;
     diag_tap(I, g.sy, g.offy, g.h, g.clamp, i0, i1, fy);
-    const uint8_t *src = g.frames + (int64_t)k * g.frame_stride;
+    int fidx = k;
+    if constexpr (TABLE) fidx = g.table[k]; // (checked on the host: 0 ... n_frames - 1)
+    const uint8_t *src = g.frames + (int64_t)fidx * g.frame_stride;
     const uint8_t *r0 = src + (int64_t)(i0 - 1) * g.row_stride, *r1 = src + (int64_t)(i1 - 1) * g.row_stride;
     const double gy = 1.0 - fy;
     uint32_t wd[4] = {0u, 0u, 0u, 0u};
@@ -124,9 +144,10 @@ __device__ __forceinline__ void diag_plot(uint8_t *o, int a, int b, uint8_t colo
     if (a >= 1 && a <= kDiagH && b >= 1 && b <= kDiagW) o[(a - 1) * kDiagW + (b - 1)] = color; // drawifinbounds!
 }
 
-__global__ __launch_bounds__(kDiagOverlayThreads) void dog_diag_overlay_kernel(const DiagOverlayGeo g)
+// what workgroup `blk` of a launch draws onto output k = g.k0 + blk of one target's trace
+__device__ __forceinline__ void diag_draw(const DiagOverlayGeo &g, int blk)
 {
-    const int k = g.k0 + (int)blockIdx.x, t = threadIdx.x;
+    const int k = g.k0 + blk, t = threadIdx.x;
     uint8_t *o = g.out + (int64_t)k * kDiagFrameBytes;
     const uint8_t color = (uint8_t)g.color;
     int2 p0, p1;
@@ -151,10 +172,25 @@ __global__ __launch_bounds__(kDiagOverlayThreads) void dog_diag_overlay_kernel(c
         for (int a = -1; a <= 1; ++a) // ((a/2)^2 + (b/2)^2 < 1: the 3 x 3 block
             for (int b = -1; b <= 1; ++b) diag_plot(o, p0.x + a, p0.y + b, color);
     }
-    if (g.write_hist && blockIdx.x == 0) {
+    if (g.write_hist && blk == 0) {
         const int cnt = min(kDiagHist, g.hcnt + g.n);
         if (t < cnt && diag_point(g, g.n - cnt + t, p1)) g.hist_out[t] = p1;
     }
+}
+
+__global__ __launch_bounds__(kDiagOverlayThreads) void dog_diag_overlay_kernel(const DiagOverlayGeo g)
+{
+    diag_draw(g, (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(kDiagOverlayThreads) void dog_diag_overlay_targets_kernel(const DiagOverlayTargetsGeo tg)
+{
+    const int t = blockIdx.y;
+    DiagOverlayGeo g = tg; // target t's view: the outputs are shared
+    g.ij += 2 * ((int64_t)t * tg.ij_stride);
+    g.hist_in += t * kDiagHist;
+    g.hist_out += t * kDiagHist;
+    diag_draw(g, (int)blockIdx.x);
 }
 
 } // namespace pdog

@@ -265,8 +265,34 @@ def _track_one(frames, target_width, start_location, window_size, darker_target,
     return indices
 
 
+def _check_sink(diagnostic, diagnostic_chunk):
+    """The overlay keywords of track_video and track_clips, judged before anything touches the device."""
+    if diagnostic is not None and not callable(diagnostic):
+        raise TypeError("diagnostic must be None or a callable")
+    if isinstance(diagnostic_chunk, bool) or not isinstance(diagnostic_chunk, (int, np.integer)):
+        raise TypeError("diagnostic_chunk must be an integer")
+    if diagnostic_chunk < 1:
+        raise ValueError(f"diagnostic_chunk: {diagnostic_chunk} is not a positive number of steps")
+    return int(diagnostic_chunk)
+
+
+def _render_steps(dia, frames, table, ij, chunk, sink):
+    """Steps 1 ... len(table)-1 of a chain's result ij [n_targets, len(table), 2] over `table` drawn by `dia` (the bootstrap
+    frame is not drawn, src/PawsomeTracker.jl:163-168), at most `chunk` steps at a time into ONE buffer that the next chunk
+    overwrites: sink(k0, overlays), overlays[i] belonging to step k0 + i."""
+    import torch
+    from .diagnose import DIAG_SIZE
+    n = len(table)
+    if n < 2:
+        return
+    buf = torch.empty((min(chunk, n - 1),) + DIAG_SIZE, dtype=torch.uint8, device=frames.device)
+    for k0 in range(1, n, chunk):
+        k1 = min(n, k0 + chunk)
+        sink(k0, dia.render_indexed(frames, table[k0:k1], ij[:, k0:k1], out=buf[:k1 - k0]))
+
+
 def track_clips(frames, target_width=25, start_locations=None, window_size=None, darker_target=True, sar=1.0,
-                lengths=None, subpixel=False):
+                lengths=None, subpixel=False, diagnostic=None, diagnostic_clips=None, diagnostic_chunk=256):
     """The reference's `track` for every clip of a device-resident stack at once: frames is a uint8 cuda tensor
     [n_clips, n_frames, h, w] (clips stacked contiguously), the device is the tensor's.  Each clip is tracked as its own
     `Tracker` would track it (src/PawsomeTracker.jl:39-52): the fill is the mode of ITS first frame (:47-48), the first
@@ -275,12 +301,23 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
     or one entry per clip, spelled as for get_guess; `lengths` is None or the number of frames of each clip
     (0 ... n_frames).  Returns int32 cuda [n_clips, n_frames, 2], 1-based (row, col); rows beyond a clip's length hold 0.
     With subpixel=True the result is (indices, sub), sub float64 cuda of the same shape: BatchTracker.measure at every
-    returned position under that clip's fill (this library's addition; the indices are unchanged)."""
+    returned position under that clip's fill (this library's addition; the indices are unchanged).
+    `diagnostic` stands in for the reference's diagnostic_file (:126) as in track_frames, here on the device: None, or a
+    callable.  Every clip of `diagnostic_clips` (None: all) is then drawn as a `track` call of its own would draw it, with
+    a fresh trace per clip: its frames 2 ... len (the bootstrap frame is not drawn, :163-168; a clip shorter than two frames
+    draws nothing), rendered from the stack as it lies, at most `diagnostic_chunk` frames at a time, and handed over as
+    diagnostic(clip, k0, overlays): overlays uint8 cuda [<= diagnostic_chunk, 360, 640], overlays[i] belonging to frame
+    k0 + i of that clip.  The buffer is reused once the sink returns: the sink consumes it with torch work on the current
+    stream, or copies it.  Positions and sub are what they are without the keyword."""
     import torch
     from .batch import BatchTracker
+    chunk = _check_sink(diagnostic, diagnostic_chunk)
     if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4):
         raise TypeError("frames must be a uint8 cuda tensor [n_clips, n_frames, h, w]")
     nc, nf, h, w = (int(v) for v in frames.shape)
+    drawn = range(nc) if diagnostic_clips is None else [int(c) for c in diagnostic_clips]
+    if any(not 0 <= c < nc for c in drawn):
+        raise ValueError(f"diagnostic_clips: clip numbers 0 ... {nc - 1} expected")
     locs = [None] * nc if start_locations is None else list(start_locations)
     if len(locs) != nc:
         raise ValueError(f"{nc} clips but {len(locs)} start locations")
@@ -316,25 +353,31 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
             starts = out[:, 0].contiguous()
             # 3. the loop from the second frame on, :161-167
             bt.track_clips(frames, starts, fills, lens, first=1, out=out)
-            if not subpixel:
-                bt.sync()                # what the kernels raised (PdogError) surfaces before the positions are handed out
-                return out
-            sub = torch.zeros((nc, nf, 2), dtype=torch.float64, device=dev)
-            k = np.arange(nf)
-            for f in np.unique(fills[has]):
-                clips = np.nonzero(has & (fills == f))[0]
-                idx = np.concatenate([c * nf + k[: lens[c]] for c in clips])
-                fi = torch.from_numpy(idx.astype(np.int32)).to(dev)
-                bt.set_fill(int(f))
-                sub.view(-1, 2)[fi.long()] = bt.measure(flat, out.view(-1, 2)[fi.long()].contiguous(), fi)
-            bt.sync()
-            return out, sub
+            sub = None
+            if subpixel:
+                sub = torch.zeros((nc, nf, 2), dtype=torch.float64, device=dev)
+                k = np.arange(nf)
+                for f in np.unique(fills[has]):
+                    clips = np.nonzero(has & (fills == f))[0]
+                    idx = np.concatenate([c * nf + k[: lens[c]] for c in clips])
+                    fi = torch.from_numpy(idx.astype(np.int32)).to(dev)
+                    bt.set_fill(int(f))
+                    sub.view(-1, 2)[fi.long()] = bt.measure(flat, out.view(-1, 2)[fi.long()].contiguous(), fi)
+            bt.sync()                    # what the kernels raised (PdogError) surfaces before the positions are handed out
+            if diagnostic is not None:
+                from .diagnose import Diagnose
+                with Diagnose(darker_target, dev.index) as dia:     # one handle for all clips
+                    for c in drawn:
+                        dia.set_targets(1)                           # a fresh trace per clip, as per `track` call (:201)
+                        table = c * nf + np.arange(int(lens[c]), dtype=np.int32)
+                        _render_steps(dia, flat, table, out[c:c + 1], chunk, lambda k0, ov, c=c: diagnostic(c, k0, ov))
+            return (out, sub) if subpixel else out
         finally:
             bt.close()
 
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
-                darker_target=True, sar=1.0, subpixel=False):
+                darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -345,10 +388,16 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     second selected frame (:161-167).  Returns (ts, indices): ts numpy float64 [m], the time stamps of :150-152 cut to the m
     frames that exist (:173), indices int32 cuda [n_targets, m, 2], 1-based (row, col).  With subpixel=True the result is
     (ts, indices, sub), sub float64 cuda of the same shape: BatchTracker.measure at every position (this library's addition).
-    There is no diagnostic overlay here: the overlay's renderer walks a contiguous stack and takes no frame index; giving it
-    one is a separate change."""
+    `diagnostic` stands in for the reference's diagnostic_file (:126) as in track_frames, here on the device: None, or a
+    callable.  The overlay of the selected frames 2 ... m (the bootstrap frame is not drawn, :163-168) is then rendered
+    through the same table, without a copy of the frames, at most `diagnostic_chunk` steps at a time, and handed over as
+    diagnostic(k0, overlays): overlays uint8 cuda [<= diagnostic_chunk, 360, 640], overlays[i] belonging to step k0 + i of
+    ts and indices.  The buffer is reused once the sink returns: the sink consumes it with torch work on the current
+    stream, or copies it.  ALL targets are drawn onto the same overlay, each with its own dot and trace — this library's
+    addition: the reference has one target per video.  ts, indices and sub are what they are without the keyword."""
     import torch
     from .batch import BatchTracker, mode_device
+    chunk = _check_sink(diagnostic, diagnostic_chunk)
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3):
         raise TypeError("frames must be a uint8 cuda tensor [n_frames, h, w]")
     n, h, w = (int(v) for v in frames.shape)
@@ -382,12 +431,16 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     bt4.close()
             # the loop from the second selected frame on, :161-167: every target over the same table
             out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
-            if not subpixel:
-                bt.sync()                # what the kernels raised (PdogError) surfaces before the positions are handed out
-                return ts, out
-            fi = torch.from_numpy(np.tile(table, nt)).to(dev)
-            sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
-            bt.sync()
-            return ts, out, sub
+            sub = None
+            if subpixel:
+                fi = torch.from_numpy(np.tile(table, nt)).to(dev)
+                sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
+            bt.sync()                    # what the kernels raised (PdogError) surfaces before the positions are handed out
+            if diagnostic is not None:
+                from .diagnose import Diagnose
+                with Diagnose(darker_target, dev.index) as dia:
+                    dia.set_targets(nt)
+                    _render_steps(dia, frames, table, out, chunk, diagnostic)
+            return (ts, out, sub) if subpixel else (ts, out)
         finally:
             bt.close()
