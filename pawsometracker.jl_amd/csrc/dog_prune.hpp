@@ -42,6 +42,7 @@
 // thin kernels start (LaunchGeo::prune) and the strip's column mask, as ever, when they end.
 #pragma once
 #include "dog_roll.hpp"
+#include "dog_prune_words.hpp"
 
 namespace pdog {
 
@@ -56,35 +57,64 @@ struct PruneGeo {
 
 constexpr int PRUNE_NT = 256;
 constexpr int PRUNE_B = 8; // the L pixels: PRUNE_B × PRUNE_B outputs
-struct PruneLds { size_t cell, E, R, patch, total; };
+// The segment sums (S) are dead once the energies are formed and the L block's buffers (R, patch) live only after that: they
+// share one region.  The patch carries 8 bytes of slack: its row pass reads whole dwords, up to 3 bytes past a row's last pixel.
+struct PruneLds { size_t cell, E, segd, strd, S, R, patch, total; };
 __host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots)
 {
     const size_t NA = n1 + L - 1, nsub = (NA + ROLL_CH - 1) / ROLL_CH, ncx = (size_t)(n2 + L - 1 + 7) / 8;
-    const size_t PH = PRUNE_B + L - 1, PP = (PH + 3) / 4 * 4;
+    const size_t PH = PRUNE_B + L - 1, PP = (PH + 3) / 4 * 4, nseg = 2 * (size_t)nslots + 1;
     PruneLds o;
     o.cell = 0;
     o.E = o.cell + nsub * ncx * 4;
-    o.R = (o.E + (size_t)nslots * nsub * 4 + 7) / 8 * 8;
+    o.segd = o.E + (size_t)nslots * nsub * 4;
+    o.strd = o.segd + (2 * ncx * 2 + 3) / 4 * 4;
+    o.S = (o.strd + 2 * (size_t)nslots * 2 + 7) / 8 * 8;
+    o.R = o.S;
     o.patch = o.R + PH * PRUNE_B * sizeof(f2);
-    o.total = (o.patch + PH * PP + 15) / 16 * 16;
+    const size_t endS = o.S + nsub * nseg * 8, endL = o.patch + PH * PP + 8;
+    o.total = ((endS > endL ? endS : endL) + 15) / 16 * 16;
     return o;
 }
 
 #ifndef PDOG_ROLL_INST_ONLY
 // One workgroup per window.
+//
+// HOW THE ENERGIES ARE FORMED (dog_prune_words.hpp has the arithmetic).  The slots' column ranges [c0, c1) cut the tile's columns
+// into a handful of segments (cfg3: cuts at 0, 64, 128, 192, 256, 320, 321); column c lies in segment seg_id(c) = the number
+// of cuts ≤ c.  The energy pass keeps the raw-pixel moments (Σ p², Σ p) per (band, segment), E[slot][band] is formed once at
+// the end from the slot's segments, and the cell sums are Σ p − n·dc of two neighbouring dwords.
+//   * One item = one 8 × 8-pixel cell: the 8 rows of a band × two dwords of columns, one 8-byte load per row.  The cells of
+//     the whole tile are dealt out to the threads in order (consecutive lanes read consecutive cells of a row: coalesced;
+//     94 % of the lanes busy at cfg3, where a lane per dword of ONE row left 17 of 64 busy in its second pass);
+//     (band, cell) advance by the constant (NT ÷ ncx, NT mod ncx): no division in the loop.  A first version dealt out
+//     single dwords and paired them by DPP: its per-item index, mask and segment work outweighed the 13 instructions per
+//     dword of the sums themselves (1.81e4 VALU instructions per window); per cell that work is paid once per 16.
+//   * How partial sums meet: the lane STORES its cell's sum (every cell has exactly one item: no atomic, no zeroing) and adds
+//     the cell's moments to its (band, segment) with two LDS atomics — per wave-instruction 64 lanes on about nine
+//     addresses.  A wave reduction per segment would need the lanes aligned to the cuts, which the in-order deal does not
+//     give (a band is 41 cells), and a band per wave leaves the lanes idle as above; a cell whose dwords lie in different
+//     segments adds per dword.
+//   * A dword that straddles a cut (strips shifted to ncols − 64, remainder columns) adds nothing to the segments in the main
+//     pass; the few such dwords are listed and a second, byte-masked pass adds them column by column.
+// (Tried: 80 SGPRs at most, for eight resident workgroups per CU instead of six at 106: 35 SGPR spills, the kernel no faster.)
 static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneGeo pg, const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
     constexpr int NT = PRUNE_NT, NW = NT / 64, CH = ROLL_CH, TW = ROLL_TW, PB = PRUNE_B;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const LaunchGeo &g = pg.g;
     const int L = g.L, hw = L / 2, H = L / 2;
-    const int NA = g.n1 + L - 1, TWin = g.n2 + L - 1, nsub = (NA + CH - 1) / CH, ncx = (TWin + 7) / 8, TQ = (TWin + 3) / 4;
+    const int NA = g.n1 + L - 1, TWin = g.n2 + L - 1, nsub = (NA + CH - 1) / CH, ncx = (TWin + 7) / 8, TQ2 = 2 * ncx;
+    const int nseg = 2 * g.nslots + 1;
     const PruneLds lo = prune_lds(g.n1, g.n2, L, g.nslots);
     int *cell = reinterpret_cast<int *>(smem + lo.cell);           // [nsub][ncx] Σ v over 8 × 8-pixel cells of the tile
     unsigned *E = reinterpret_cast<unsigned *>(smem + lo.E);       // [nslots][nsub]
+    short *segd = reinterpret_cast<short *>(smem + lo.segd);       // [2ncx] a dword's segment; −1: it straddles a cut or lies past the tile
+    unsigned short *strd = reinterpret_cast<unsigned short *>(smem + lo.strd); // the dwords that straddle a cut (at most one per cut)
+    unsigned *S = reinterpret_cast<unsigned *>(smem + lo.S);       // [nsub][nseg] (Σ p², Σ p)
     f2 *R = reinterpret_cast<f2 *>(smem + lo.R);                   // [PB + l − 1][PB] row-pass outputs of the L pixels
     uint8_t *patch = smem + lo.patch;                              // their input pixels
-    __shared__ int s_sum[NW], s_v[NW], s_cv[NW], s_ci[NW], s_cellbest, s_kept;
+    __shared__ int s_sum[NW], s_pmax[NW], s_pmin[NW], s_cv[NW], s_ci[NW], s_cellbest, s_kept, s_nstr;
     __shared__ double s_emax;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -94,125 +124,250 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
     const uint8_t *__restrict__ frame = g.frames + (long long)fidx * g.frame_stride;
     const int ti0 = g1 - g.r1 - 1 - hw, wj0 = g2 - g.r2 - 1 - hw; // frame row / column of the tile's first pixel
     const tap_ptr trow = as_taps(taps_row), tcol = as_taps(taps_col);
+    const uint32_t fill4 = (uint32_t)g.fill * 0x01010101u;
 
+    const int ncols = g.nthin ? g.thin_x0 : g.n2; // window columns the strips cover
+    const int ws = min(TW, ncols);
+    auto slot_cols = [&](int sl, int &c0, int &c1) { // the tile columns a slot's outputs read
+        const bool strip = sl < g.nstrips;
+        c0 = strip ? ((ncols >= TW) ? min(sl * TW, ncols - TW) : 0) : g.thin_x0 + (sl - g.nstrips);
+        c1 = c0 + (strip ? ws + L - 1 : L);
+    };
+    auto seg_id = [&](int c) {
+        int id = 0;
+        for (int sl = 0; sl < g.nslots; ++sl) {
+            int c0, c1;
+            slot_cols(sl, c0, c1);
+            id += (c0 <= c) + (c1 <= c);
+        }
+        return id;
+    };
+    // One dword of the tile at frame row gi, frame column gj: the bytes inside the frame (`in`: pw_mask(gj, 0, fw) in a row of
+    // the frame, else 0), 0 elsewhere.  Every address read lies in a row of the frame at a column of the frame: a dword that
+    // hangs over the frame's edge is read byte by byte.
+    auto row_in = [&](int gi) { return gi >= 0 && gi < g.fh; };
+    auto tile_word = [&](int gi, int gj, uint32_t in) -> uint32_t {
+        uint32_t w = 0;
+        if (in == 0xffffffffu) {
+            __builtin_memcpy(&w, frame + (long long)gi * g.row_stride + gj, 4);
+        } else if (in) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if ((in >> (8 * i)) & 1u) w |= (uint32_t)frame[(long long)gi * g.row_stride + gj + i] << (8 * i);
+        }
+        return w;
+    };
+
+    if (tid == 0) { s_kept = 0; s_nstr = 0; }
+    for (int i = tid; i < nsub * nseg * 2; i += NT) S[i] = 0;
     // ---- the window's DC level: the strips' samples and rounding ----
     int dc;
     {
         int sum = wave_sum(dc_sample_sum(g, frame, ti0, wj0, L, tid, NT));
         if (lane == 0) s_sum[wave] = sum;
-        if (tid == 0) s_kept = 0;
         __syncthreads();
         int tot = 0;
         for (int w = 0; w < NW; ++w) tot += s_sum[w];
         dc = dc_from_sum(tot, g.fill);
     }
-
-    // ---- energies: one item = the 8 rows of a band × one dword of columns; the items of the whole tile are dealt out to the
-    // threads in order (consecutive lanes read consecutive dwords of a row: coalesced; 99 % of the lanes have work, where a
-    // lane per dword of ONE row left 17 of 64 busy in the second pass over a 321-byte row).  An item adds its Σ v to its
-    // 8 × 8 cell and its column energies to every slot that reads those columns, with LDS atomics (integers: exact in any
-    // order).  Products through the 24-bit multiplier: |v| ≤ 255, and the full 32-bit multiply runs at a quarter of its rate ----
-    const int ncols = g.nthin ? g.thin_x0 : g.n2; // window columns the strips cover
-    const int ws = min(TW, ncols);
-    for (int i = tid; i < nsub * ncx + g.nslots * nsub; i += NT) cell[i] = 0; // (E follows cell in the layout)
+    for (int d = tid; d < TQ2; d += NT) {
+        int sd = -1;
+        if (4 * d < TWin) {
+            const int first = seg_id(4 * d), last = seg_id(min(4 * d + 3, TWin - 1));
+            if (first == last) sd = first;
+            else strd[atomicAdd(&s_nstr, 1)] = (unsigned short)d;
+        }
+        segd[d] = (short)sd;
+    }
     __syncthreads();
-    int vmax = 0;
-    for (int it = tid; it < nsub * TQ; it += NT) {
-        const int band = it / TQ, d = it - band * TQ;
-        unsigned e[4] = {0u, 0u, 0u, 0u};
-        int s = 0;
-        const int gj = wj0 + 4 * d;
-        const bool cols_in = gj >= 0 && gj + 4 <= g.fw && 4 * d + 4 <= TWin;
+
+    // ---- energy pass (above).  Per dword: a load, the two substituted words, two dots, four ands, four packed min / max ----
+    PwAcc ext = pw_init(); // (its extremes only: the thread's pixels of all its items)
+    {
+        int band = tid / ncx, cx = tid - band * ncx;
+        const int bstep = NT / ncx, cstep = NT - bstep * ncx;
+        for (int it = tid; it < nsub * ncx; it += NT) {
+            const int col0 = 8 * cx, gj = wj0 + col0, a0 = band * CH, gi0 = ti0 + a0, nr = min(CH, NA - a0);
+            const uint32_t cnt_a = pw_mask(col0, 0, TWin), cnt_b = pw_mask(col0 + 4, 0, TWin);
+            uint32_t s2a = 0, s1a = 0, s2b = 0, s1b = 0; // the moments of the cell's two dwords
+            if (nr == CH && gi0 >= 0 && gi0 + CH <= g.fh && gj >= 0 && gj + 8 <= g.fw) { // the cell inside the frame
+                const uint8_t *src = frame + (long long)gi0 * g.row_stride + gj;
 #pragma unroll
-        for (int r = 0; r < CH; ++r) {
-            const int a = band * CH + r, gi = ti0 + a;
-            if (a >= NA) continue; // (rows past the tile are read by no output)
-            int p[4];
-            if (cols_in && gi >= 0 && gi < g.fh) {
-                uint32_t w;
-                __builtin_memcpy(&w, frame + (long long)gi * g.row_stride + gj, 4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) p[i] = (int)((w >> (8 * i)) & 0xffu);
+                for (int r = 0; r < CH; ++r) {
+                    uint32_t w[2];
+                    __builtin_memcpy(w, src + (long long)r * g.row_stride, 8);
+                    const PwWords xa = pw_words(w[0], 0xffffffffu, cnt_a, fill4), xb = pw_words(w[1], 0xffffffffu, cnt_b, fill4);
+                    pw_moments(s2a, s1a, xa.wz);
+                    pw_extremes(ext, xa);
+                    pw_moments(s2b, s1b, xb.wz);
+                    pw_extremes(ext, xb);
+                }
             } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int gjj = gj + i;
-                    p[i] = 4 * d + i >= TWin ? dc // (columns past the tile: v = 0)
-                           : (gi >= 0 && gi < g.fh && gjj >= 0 && gjj < g.fw) ? (int)frame[(long long)gi * g.row_stride + gjj] : g.fill;
+                const uint32_t in_a = pw_mask(gj, 0, g.fw), in_b = pw_mask(gj + 4, 0, g.fw);
+                if ((in_a | in_b) == 0u || gi0 >= g.fh || gi0 + nr <= 0) { // the cell outside the frame: nr rows of fill
+                    const PwWords xa = pw_words(0u, 0u, cnt_a, fill4), xb = pw_words(0u, 0u, cnt_b, fill4);
+                    pw_moments(s2a, s1a, xa.wz);
+                    pw_moments(s2b, s1b, xb.wz);
+                    s2a *= (uint32_t)nr; s1a *= (uint32_t)nr; s2b *= (uint32_t)nr; s1b *= (uint32_t)nr;
+                    pw_extremes(ext, xa);
+                    pw_extremes(ext, xb);
+                } else {
+                    for (int r = 0; r < nr; ++r) { // (rows at or past NA are read by no output)
+                        const bool rin = row_in(gi0 + r);
+                        const uint32_t ia = rin ? in_a : 0u, ib = rin ? in_b : 0u;
+                        const PwWords xa = pw_words(tile_word(gi0 + r, gj, ia), ia, cnt_a, fill4), xb = pw_words(tile_word(gi0 + r, gj + 4, ib), ib, cnt_b, fill4);
+                        pw_moments(s2a, s1a, xa.wz);
+                        pw_extremes(ext, xa);
+                        pw_moments(s2b, s1b, xb.wz);
+                        pw_extremes(ext, xb);
+                    }
                 }
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int v = p[i] - dc;
-                e[i] += (unsigned)__mul24(v, v);
-                s += v;
-                vmax = max(vmax, abs(v));
+            cell[band * ncx + cx] = pw_sum(s1a + s1b, nr * min(TWin - col0, 8), dc);
+            const int sda = segd[2 * cx], sdb = segd[2 * cx + 1];
+            unsigned *Sb = S + 2 * band * nseg;
+            if (sda == sdb) {
+                if (sda >= 0) { atomicAdd(Sb + 2 * sda, s2a + s2b); atomicAdd(Sb + 2 * sda + 1, s1a + s1b); }
+            } else {
+                if (sda >= 0) { atomicAdd(Sb + 2 * sda, s2a); atomicAdd(Sb + 2 * sda + 1, s1a); }
+                if (sdb >= 0) { atomicAdd(Sb + 2 * sdb, s2b); atomicAdd(Sb + 2 * sdb + 1, s1b); }
             }
-        }
-        atomicAdd(&cell[band * ncx + (d >> 1)], s); // two dwords = one 8-column cell
-        for (int sl = 0; sl < g.nslots; ++sl) {
-            const bool strip = sl < g.nstrips;
-            const int c0 = strip ? ((ncols >= TW) ? min(sl * TW, ncols - TW) : 0) : g.thin_x0 + (sl - g.nstrips);
-            const int lo = c0 - 4 * d, hi = lo + (strip ? ws + L - 1 : L); // the slot's columns, counted from this dword's first
-            unsigned sum = 0; // (a slot's band total is at most 8 · 212 · 255² < 2³¹)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i >= lo && i < hi) sum += e[i];
-            if (sum) atomicAdd(&E[sl * nsub + band], sum);
+            cx += cstep;
+            band += bstep;
+            if (cx >= ncx) { cx -= ncx; ++band; }
         }
     }
-    vmax = wave_reduce_bits(vmax, [](int a, int c) { return a > c ? a : c; });
-    if (lane == 0) s_v[wave] = vmax;
+    {
+        const int pmax = wave_reduce_bits(pw_pmax(ext), [](int a, int c) { return a > c ? a : c; });
+        const int pmin = wave_min(pw_pmin(ext));
+        if (lane == 0) { s_pmax[wave] = pmax; s_pmin[wave] = pmin; }
+    }
     __syncthreads();
 
-    // ---- where to take L: the cell whose direction-signed 3 × 3-cell sum is largest ----
-    {
-        int bv = -0x7fffffff, bi = 0;
-        for (int c = tid; c < nsub * ncx; c += NT) {
-            const int cy = c / ncx, cx = c - cy * ncx;
-            int s = 0;
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int yy = cy + dy, xx = cx + dx;
-                    if (yy >= 0 && yy < nsub && xx >= 0 && xx < ncx) s += cell[yy * ncx + xx];
-                }
-            if (pg.darker) s = -s;
-            if (s > bv) { bv = s; bi = c; }
+    // ---- the dwords that straddle a cut, a column per task: the same words, masked to the one byte ----
+    for (int j = 0, nstr = s_nstr; j < nstr; ++j) {
+        const int d = strd[j], gj = wj0 + 4 * d;
+        const uint32_t in_cols = pw_mask(gj, 0, g.fw);
+        for (int t = tid; t < 4 * nsub; t += NT) {
+            const int band = t >> 2, col = 4 * d + (t & 3), a0 = band * CH, nr = min(CH, NA - a0);
+            if (col >= TWin) continue;
+            const uint32_t counted = pw_mask(4 * d, col, col + 1);
+            uint32_t s2 = 0, s1 = 0;
+            for (int r = 0; r < nr; ++r) {
+                const int gi = ti0 + a0 + r;
+                const uint32_t in = row_in(gi) ? in_cols & counted : 0u;
+                pw_moments(s2, s1, pw_words(tile_word(gi, gj, in), in, counted, fill4).wz);
+            }
+            unsigned *Sb = S + 2 * (band * nseg + seg_id(col));
+            atomicAdd(Sb, s2);
+            atomicAdd(Sb + 1, s1);
         }
+    }
+
+    // ---- where to take L: the cell whose direction-signed 3 × 3-cell sum is largest, the first such cell in row-major
+    // order.  Separably: a thread walks a run of one cell column downwards, three reads per cell for the three-sum along x
+    // and the three-sum along y sliding in registers ----
+    {
+        int bv = -0x7fffffff, bi = 0x7fffffff;
+        const int nrun = ncx >= NT ? 1 : NT / ncx, rlen = (nsub + nrun - 1) / nrun;
+        const int run = ncx >= NT ? 0 : tid / ncx;
+        if (run < nrun)
+            for (int cx = tid - run * ncx; cx < ncx; cx += NT) {
+                const bool left = cx > 0, right = cx + 1 < ncx;
+                auto h3 = [&](int y) {
+                    if (y < 0 || y >= nsub) return 0;
+                    const int *c = cell + y * ncx + cx;
+                    return c[0] + (left ? c[-1] : 0) + (right ? c[1] : 0);
+                };
+                const int y0 = run * rlen, y1 = min(nsub, y0 + rlen);
+                int above = h3(y0 - 1), here = h3(y0);
+                for (int y = y0; y < y1; ++y) {
+                    const int below = h3(y + 1);
+                    int s = above + here + below;
+                    if (pg.darker) s = -s;
+                    const int c = y * ncx + cx;
+                    if (s > bv || (s == bv && c < bi)) { bv = s; bi = c; }
+                    above = here;
+                    here = below;
+                }
+            }
         const int m = wave_reduce_bits(bv, [](int a, int c) { return a > c ? a : c; });
         const int mi = wave_min(bv == m ? bi : 0x7fffffff);
         if (lane == 0) { s_cv[wave] = m; s_ci[wave] = mi; }
-        __syncthreads();
-        if (tid == 0) {
-            int wv = s_cv[0], wi = s_ci[0];
-            for (int w = 1; w < NW; ++w)
-                if (s_cv[w] > wv || (s_cv[w] == wv && s_ci[w] < wi)) { wv = s_cv[w]; wi = s_ci[w]; }
-            s_cellbest = wi;
-        }
-        __syncthreads();
     }
-    int V = 0;
-    for (int w = 0; w < NW; ++w) V = max(V, s_v[w]);
+    __syncthreads();
+    if (tid == 0) {
+        int wv = s_cv[0], wi = s_ci[0];
+        for (int w = 1; w < NW; ++w)
+            if (s_cv[w] > wv || (s_cv[w] == wv && s_ci[w] < wi)) { wv = s_cv[w]; wi = s_ci[w]; }
+        s_cellbest = wi;
+    }
+    // ---- E[slot][band] from the slot's segments: n is geometry, the band's rows × the slot's columns ----
+    for (int sl = wave; sl < g.nslots; sl += NW) {
+        int c0, c1;
+        slot_cols(sl, c0, c1);
+        const int sa = seg_id(c0), sb = seg_id(c1); // (c0 and c1 are cuts: exactly the columns [c0, c1) lie in segments sa … sb − 1)
+        for (int band = lane; band < nsub; band += 64) {
+            uint32_t s2 = 0, s1 = 0;
+            for (int sg = sa; sg < sb; ++sg) { s2 += S[2 * (band * nseg + sg)]; s1 += S[2 * (band * nseg + sg) + 1]; }
+            E[sl * nsub + band] = pw_energy(s2, s1, min(CH, NA - band * CH) * (c1 - c0), dc);
+        }
+    }
+    int V;
+    {
+        int pmax = 0, pmin = 255;
+        for (int w = 0; w < NW; ++w) { pmax = max(pmax, s_pmax[w]); pmin = min(pmin, s_pmin[w]); }
+        V = pw_V(pmax, pmin, dc);
+    }
+    __syncthreads(); // (the segment sums are dead from here: R and the patch take their place)
     const int cy = s_cellbest / ncx, cx = s_cellbest - cy * ncx;
     // the cell's centre is tile pixel (8cy + 4, 8cx + 4) = the centre input of output (8cy + 4 − l÷2, 8cx + 4 − l÷2)
     const int ny = min(PB, g.n1), nx = min(PB, g.n2);
     const int oy = min(max(CH * cy + 4 - hw - PB / 2, 0), g.n1 - ny), ox = min(max(8 * cx + 4 - hw - PB / 2, 0), g.n2 - nx);
-    const int PH = ny + L - 1, PW = nx + L - 1, PP = (PB + L - 1 + 3) / 4 * 4;
-    for (int e = tid; e < PH * PW; e += NT) {
-        const int a = e / PW, c = e - a * PW;
-        const int gi = ti0 + oy + a, gj = wj0 + ox + c;
-        patch[a * PP + c] = (gi >= 0 && gi < g.fh && gj >= 0 && gj < g.fw) ? frame[(long long)gi * g.row_stride + gj] : (uint8_t)g.fill;
+    const int PH = ny + L - 1, PW = nx + L - 1, PP = (PB + L - 1 + 3) / 4 * 4, PQ = (PW + 3) / 4;
+    {
+        // the patch in dwords, fill substituted (the bytes of a row's last dword past PW are read and never used)
+        uint32_t *pw32 = reinterpret_cast<uint32_t *>(patch);
+        int a = tid / PQ, q = tid - a * PQ;
+        const int astep = NT / PQ, qstep = NT - astep * PQ;
+        for (int e = tid; e < PH * PQ; e += NT) {
+            const int gi = ti0 + oy + a, gj = wj0 + ox + 4 * q;
+            const uint32_t in = row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u;
+            pw32[a * (PP / 4) + q] = pw_words(tile_word(gi, gj, in), in, 0xffffffffu, fill4).wz;
+            q += qstep;
+            a += astep;
+            if (q >= PQ) { q -= PQ; ++a; }
+        }
     }
     __syncthreads();
-    // row pass in the strips' order: pairs k ascending, centre last
-    const float fdc = (float)dc;
-    for (int task = tid; task < PH * nx; task += NT) {
-        const int a = task / nx, xo = task - a * nx;
-        const uint8_t *p = patch + a * PP + xo;
-        f2 acc = f2{0.f, 0.f};
-        for (int k = 0; k < H; ++k) acc = fma_bcast(((float)p[k] - fdc) + ((float)p[L - 1 - k] - fdc), trow[k], acc);
-        acc = fma_bcast((float)p[H] - fdc, trow[H], acc);
-        R[a * PB + xo] = acc;
+    // Row pass in the strips' order: pairs k ascending, centre last.  A thread is (input row, output column xo); the pixels
+    // of four pairs come as two unaligned dwords (v_alignbyte_b32 over two aligned LDS dwords each): p[xo + 4i … + 3] and
+    // p[xo + l − 4 − 4i … + 3], the second read from its last byte down.  A pair's input is the integer
+    // p[k] + p[l−1−k] − 2·dc converted once: bit-equal to ((float)p[k] − fdc) + ((float)p[l−1−k] − fdc), because every term
+    // there is an exact integer of at most ten bits (and a zero sum is +0 either way).
+    {
+        const uint32_t *pw32 = reinterpret_cast<const uint32_t *>(patch);
+        const int xo = tid & (PB - 1), twodc = 2 * dc;
+        const unsigned sh_up = xo & 3, sh_dn = (xo + L) & 3; // (l − 4 − 4i ≡ l mod 4)
+        if (xo < nx)
+            for (int a = tid / PB; a < PH; a += NT / PB) {
+                const uint32_t *up = pw32 + a * (PP / 4) + (xo >> 2), *dn = pw32 + a * (PP / 4) + ((xo + L - 4) >> 2);
+                f2 acc = f2{0.f, 0.f};
+                int k0 = 0;
+                for (; k0 + 4 <= H; k0 += 4, ++up, --dn) { // (whole groups without a test per pair: their four taps come as one scalar load)
+                    const uint32_t u = __builtin_amdgcn_alignbyte(up[1], up[0], sh_up), v = __builtin_amdgcn_alignbyte(dn[1], dn[0], sh_dn);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        acc = fma_bcast((float)((int)((u >> (8 * i)) & 0xffu) + (int)((v >> (24 - 8 * i)) & 0xffu) - twodc), trow[k0 + i], acc);
+                }
+                if (k0 < H) { // l ÷ 2 mod 4 pairs more
+                    const uint32_t u = __builtin_amdgcn_alignbyte(up[1], up[0], sh_up), v = __builtin_amdgcn_alignbyte(dn[1], dn[0], sh_dn);
+                    for (int i = 0; k0 + i < H; ++i)
+                        acc = fma_bcast((float)((int)((u >> (8 * i)) & 0xffu) + (int)((v >> (24 - 8 * i)) & 0xffu) - twodc), trow[k0 + i], acc);
+                }
+                acc = fma_bcast((float)((int)patch[a * PP + xo + H] - dc), trow[H], acc);
+                R[a * PB + xo] = acc;
+            }
     }
     __syncthreads();
     if (wave == 0) {
@@ -260,7 +415,8 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         __hip_atomic_fetch_add(pg.stat, (unsigned long long)s_kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_add(pg.stat + 1, (unsigned long long)(g.nslots * nsub), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // the last workgroup of the batch publishes both counts where the host sees them without a copy or a wait (the way
-        // dog_finish_kernel publishes its flagged count): one plain store per batch
+        // dog_finish_kernel publishes its flagged count): one plain store per batch.  (Tried: arrival and kept pairs in ONE
+        // atomic per workgroup instead of three on neighbouring words: the kernel's time did not move.)
         const unsigned long long arrived = __hip_atomic_fetch_add(pg.stat + 2, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         if (arrived == (unsigned long long)gridDim.x - 1) {
             __hip_atomic_store(pg.stat + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,0 +1,128 @@
+// dog_prune_words.hpp — the pre-pass's arithmetic on one dword of four pixels (dog_prune.hpp), free of HIP so that a host
+// program can hold it against the direct sums (tests/prune_words_main.cpp).
+//
+// The energy of a set of n pixels about the window's DC level comes from the raw pixels' moments, exactly, in integers:
+//     Σ (p − dc)² = Σ p² − 2·dc·Σ p + n·dc²,          Σ (p − dc) = Σ p − n·dc,
+// and V = max |p − dc| = max(pmax − dc, dc − pmin).  Per dword the device forms Σ p² and Σ p with one v_dot4_u32_u8 each
+// and the four bytes' maxima and minima as two packed 16-bit halves each (the even bytes in place, the odd bytes left in
+// the high byte of their half: a common factor of 256 does not change an order, so no shift is needed).
+//
+// A dword is counted through two substituted words (pw_words):
+//     wz — what the sums and the maximum see: the frame's byte where the pixel lies inside the frame, the fill where it lies
+//          outside the frame but inside the tile, 0 where the pixel is not counted at all (a column at or past the tile's width
+//          or outside the column range asked for, a row at or past the tile's height);
+//     wo — what the minimum sees: the same, with 0xff for the bytes that are not counted, so that they never are the minimum
+//          (a zeroed byte on a bright window would give a wrong V).
+// n is geometry (rows × columns counted), never counted at run time.
+//
+// RANGE.  The widest slot, at l = 149, is 8 rows × 212 columns: Σ p² ≤ 1696·255² ≈ 1.11e8, n·dc² likewise, 2·dc·Σ p ≤ 2.21e8;
+// a dword's 8-row sums are far smaller.  pw_energy adds before it subtracts: every intermediate lies in [0, 2.21e8] < 2³².
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PW_HD __host__ __device__ inline
+#else
+#define PW_HD inline
+#endif
+
+namespace pdog {
+
+// 0xff in byte i iff column col0 + i lies in [lo, hi)
+PW_HD uint32_t pw_low_bytes(int n) { return n >= 4 ? 0xffffffffu : n <= 0 ? 0u : (1u << (8 * n)) - 1u; } // 0xff in the bytes below n
+PW_HD uint32_t pw_mask(int col0, int lo, int hi) { return pw_low_bytes(hi - col0) & ~pw_low_bytes(lo - col0); }
+
+// The substituted words of one loaded dword.  in_frame: the bytes whose pixel lies inside the frame (w is read there only);
+// counted: the bytes that are counted at all.
+struct PwWords { uint32_t wz, wo; };
+PW_HD PwWords pw_words(uint32_t w, uint32_t in_frame, uint32_t counted, uint32_t fill4)
+{
+    const uint32_t keep = in_frame & counted;
+    const uint32_t z = (w & keep) | (fill4 & counted & ~keep);
+    return PwWords{z, z | ~counted};
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned short pw_us2 __attribute__((ext_vector_type(2)));
+PW_HD uint32_t pw_dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
+PW_HD uint32_t pw_pk_max(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(pw_us2, a), __builtin_bit_cast(pw_us2, b)));
+}
+PW_HD uint32_t pw_pk_min(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(pw_us2, a), __builtin_bit_cast(pw_us2, b)));
+}
+#else
+PW_HD uint32_t pw_dot4(uint32_t a, uint32_t b, uint32_t c)
+{
+    for (int i = 0; i < 4; ++i) c += ((a >> (8 * i)) & 0xffu) * ((b >> (8 * i)) & 0xffu);
+    return c;
+}
+PW_HD uint32_t pw_pk_max(uint32_t a, uint32_t b)
+{
+    const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
+    return (al > bl ? al : bl) | ((ah > bh ? ah : bh) << 16);
+}
+PW_HD uint32_t pw_pk_min(uint32_t a, uint32_t b)
+{
+    const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
+    return (al < bl ? al : bl) | ((ah < bh ? ah : bh) << 16);
+}
+#endif
+
+constexpr uint32_t PW_EVEN = 0x00ff00ffu, PW_ODD = 0xff00ff00u;
+
+// Σ p², Σ p and the packed extremes of the pixels counted so far
+struct PwAcc {
+    uint32_t s2, s1;
+    uint32_t max_e, max_o, min_e, min_o; // even / odd bytes, two 16-bit halves each
+};
+PW_HD PwAcc pw_init() { return PwAcc{0u, 0u, 0u, 0u, PW_EVEN, PW_ODD}; }
+
+// the sums of one dword: two dot instructions
+PW_HD void pw_moments(uint32_t &s2, uint32_t &s1, uint32_t wz)
+{
+    s2 = pw_dot4(wz, wz, s2);
+    s1 = pw_dot4(wz, 0x01010101u, s1);
+}
+// the extremes of one dword: two ands and two packed min / max per word
+PW_HD void pw_extremes(PwAcc &a, PwWords x)
+{
+    a.max_e = pw_pk_max(a.max_e, x.wz & PW_EVEN);
+    a.max_o = pw_pk_max(a.max_o, x.wz & PW_ODD);
+    a.min_e = pw_pk_min(a.min_e, x.wo & PW_EVEN);
+    a.min_o = pw_pk_min(a.min_o, x.wo & PW_ODD);
+}
+PW_HD void pw_update(PwAcc &a, PwWords x)
+{
+    pw_moments(a.s2, a.s1, x.wz);
+    pw_extremes(a, x);
+}
+
+// the largest / smallest counted pixel (0 / 255 when nothing was counted)
+PW_HD int pw_pmax(const PwAcc &a)
+{
+    const uint32_t e = (a.max_e & 0xffffu) > (a.max_e >> 16) ? (a.max_e & 0xffffu) : (a.max_e >> 16);
+    const uint32_t o = (a.max_o & 0xffffu) > (a.max_o >> 16) ? (a.max_o & 0xffffu) : (a.max_o >> 16);
+    return (int)(e > (o >> 8) ? e : (o >> 8));
+}
+PW_HD int pw_pmin(const PwAcc &a)
+{
+    const uint32_t e = (a.min_e & 0xffffu) < (a.min_e >> 16) ? (a.min_e & 0xffffu) : (a.min_e >> 16);
+    const uint32_t o = (a.min_o & 0xffffu) < (a.min_o >> 16) ? (a.min_o & 0xffffu) : (a.min_o >> 16);
+    return (int)(e < (o >> 8) ? e : (o >> 8));
+}
+
+// Σ (p − dc)² of n pixels from their moments (RANGE above)
+PW_HD uint32_t pw_energy(uint32_t s2, uint32_t s1, int n, int dc) { return (s2 + (uint32_t)n * (uint32_t)(dc * dc)) - 2u * (uint32_t)dc * s1; }
+// Σ (p − dc)
+PW_HD int pw_sum(uint32_t s1, int n, int dc) { return (int)s1 - n * dc; }
+// max |p − dc| from the extremes (0 when nothing was counted)
+PW_HD int pw_V(int pmax, int pmin, int dc)
+{
+    const int up = pmax - dc, dn = dc - pmin, v = up > dn ? up : dn;
+    return v > 0 ? v : 0;
+}
+
+} // namespace pdog

@@ -346,6 +346,23 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     const int tj0 = wj0 + x0;
     const int NA = g.n1 + L - 1;
 
+    // ---- kept range (dog_prune.hpp), read ahead of everything else: a slot with an empty range leaves an initialised partial
+    // and mask 0 at once, without taking its share of the window's DC samples from the frame ----
+    int prune_ba = 0, prune_bb = 0;
+    if constexpr (PRUNE) {
+        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + s];
+        prune_ba = __builtin_amdgcn_readfirstlane((int)(unsigned)rng);
+        prune_bb = __builtin_amdgcn_readfirstlane((int)(unsigned)(rng >> 32));
+        if (prune_bb <= prune_ba) {
+            Peak pk;
+            peak_init(pk);
+            peak_wave_reduce(pk);
+            peak_out = pk;
+            mask_out = 0ull;
+            return;
+        }
+    }
+
     // ---- per-window DC level (see dog_kernels.hpp): same samples in every strip ----
     int dc;
     {
@@ -434,11 +451,9 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     static_assert(!PRUNE || (!RESP && ABL == 0 && EPI < 0), "kept ranges: the plain instances only");
     int sc_lo = 0, sc_hi = nsub, y_lo = 0;
     if constexpr (PRUNE) {
-        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + s];
-        const int ba = __builtin_amdgcn_readfirstlane((int)(unsigned)rng), bb = __builtin_amdgcn_readfirstlane((int)(unsigned)(rng >> 32));
-        sc_lo = ba;
-        sc_hi = prune_sc_hi(ba, bb, L, nsub);
-        y_lo = ba * CH;
+        sc_lo = prune_ba; // (read above, ahead of the DC level)
+        sc_hi = prune_sc_hi(prune_ba, prune_bb, L, nsub);
+        y_lo = prune_ba * CH;
     }
     uint32_t pre[SB / 4];
     load16(sc_lo * CH + srow, pre);
@@ -835,6 +850,27 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
     __shared__ int ssum[NW];
     __shared__ float sval[NW], ssec[NW];
     __shared__ int sidx[NW];
+    // ---- kept range (dog_prune.hpp), read ahead of the DC level: output rows [y_lo, y_hi) and the input rows [a_lo, a_hi)
+    // they read; an empty range (the same for the whole workgroup) leaves an initialised Peak at once ----
+    int a_lo = 0, a_hi = NA, y_lo = 0, y_hi = g.n1;
+    if (!RESP && g.prune) {
+        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + g.nstrips + rc];
+        const int ba = (int)(unsigned)rng, bb = (int)(unsigned)(rng >> 32);
+        if (bb <= ba) {
+            if (tid == 0) {
+                Peak pk;
+                peak_init(pk);
+                g.part_val[b * g.nslots + g.nstrips + rc] = pk.best;
+                g.part_idx[b * g.nslots + g.nstrips + rc] = pk.idx;
+                g.part_sec[b * g.nslots + g.nstrips + rc] = pk.second;
+            }
+            return;
+        }
+        y_lo = ba * ROLL_CH;
+        y_hi = min(g.n1, bb * ROLL_CH);
+        a_lo = y_lo;
+        a_hi = y_hi + L - 1;
+    }
     int dc;
     {
         int sum = dc_sample_sum(g, frame, ti0, wj0, L, tid, NT);
@@ -846,17 +882,6 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
         dc = dc_from_sum(tot, g.fill);
     }
     const float fdc = (float)dc;
-    // ---- kept range (dog_prune.hpp): output rows [y_lo, y_hi) and the input rows [a_lo, a_hi) they read; an empty range
-    // leaves an initialised Peak ----
-    int a_lo = 0, a_hi = NA, y_lo = 0, y_hi = g.n1;
-    if (!RESP && g.prune) {
-        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + g.nstrips + rc];
-        const int ba = (int)(unsigned)rng, bb = (int)(unsigned)(rng >> 32);
-        y_lo = ba * ROLL_CH;
-        y_hi = bb > ba ? min(g.n1, bb * ROLL_CH) : y_lo;
-        a_lo = y_lo;
-        a_hi = bb > ba ? y_hi + L - 1 : a_lo;
-    }
     const int na = a_hi - a_lo; // input rows to stage
 
     // ---- the column's input patch, NA rows × l pixels, → LDS bytes: a dword per item, loaded unconditionally at an

@@ -1119,6 +1119,9 @@ int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticke
 // bench.py (profiles/prune_profile_this.txt, profiles/prune_profile_parent.txt): dog_prune_kernel takes 0.474 ms beside the
 // dense roll kernel's 1.314 ms, 36 % of it (kPrunePrePct), so a batch that keeps more than 64 % of its (slot, sub-chunk) pairs
 // (kPruneBreakEvenPct) is better off dense.  Noise-only windows and heavy texture are such batches (nothing can be excluded).
+// (Since the pre-pass forms its energies from raw-pixel moments it takes 0.331 ms, 25 % of the dense roll kernel:
+// profiles/prepass_profile_this.txt.  The constant has not followed yet: bench data at ±40 levels keeps 76 % of its pairs,
+// right at the share that ratio would give, and whether pruning pays there is unmeasured — profiles/prepass_ab.txt.)
 // The pre-pass publishes its cumulative kept / total counts through host-coherent memory, as the finishing kernel publishes
 // its flagged count; when the pairs counted since the last look kept more than the break-even share, the next
 // kPruneProbeEvery batches run dense, then one batch probes again.  Nothing here waits for the GPU.
