@@ -61,6 +61,22 @@ def host_i32(v, name, n):
     return a
 
 
+def peaks_args(k, min_distance, name="k"):
+    """The picks per window (1 ... 32, PDOG_PEAKS_MAX_K) and the least distance between two picks (None: the library's
+    default, ceil(target_width), passed on as 0; otherwise a positive integer) as pdog_detect_peaks takes them."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer, not {type(k).__name__}")
+    if not 1 <= k <= 32:
+        raise ValueError(f"{name}: {k} lies outside 1 ... 32")
+    if min_distance is None:
+        return int(k), 0
+    if isinstance(min_distance, bool) or not isinstance(min_distance, (int, np.integer)):
+        raise TypeError(f"min_distance must be None or an integer, not {type(min_distance).__name__}")
+    if not 1 <= min_distance < 2**31:
+        raise ValueError(f"min_distance: {min_distance} is not a positive number of pixels")
+    return int(k), int(min_distance)
+
+
 def host_table(v, name):
     """A frame table — a sequence of rows, a numpy array or a tensor of integers [n_clips, n_steps] — as a contiguous host int32
     array.  Its entries are the library's to judge (it validates them before it launches anything)."""

@@ -116,6 +116,15 @@ OVERLAY_PROTOTYPES = {
 }
 OVERLAY_SYMBOLS = tuple(OVERLAY_PROTOTYPES)
 DIAG_MAX_TARGETS = 1024      # PDOG_DIAG_MAX_TARGETS
+
+# the same for include/pawsome_peaks.h, a header of its own that includes pawsome_dog.h: the K best separated peaks of a
+# window (tests/test_peaks_cpu.py holds this table against that header)
+PEAKS_PROTOTYPES = {
+    "pdog_detect_peaks": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "pdog_get_peaks_counts": (_i, [_p, _pu64]),
+}
+PEAKS_SYMBOLS = tuple(PEAKS_PROTOTYPES)
+PEAKS_MAX_K = 32             # PDOG_PEAKS_MAX_K
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -160,7 +169,7 @@ def lib():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -241,6 +250,12 @@ class TrackerHandle(Handle):
         """(kept, total) (strip, sub-chunk) pairs of the batches that ran the bounding pre-pass — pdog_get_prune_counts."""
         out = (C.c_uint64 * 2)()
         check(lib().pdog_get_prune_counts(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def peaks_counts(self):
+        """(windows detect_peaks served, those among them whose candidate list overflowed) — pdog_get_peaks_counts."""
+        out = (C.c_uint64 * 2)()
+        check(lib().pdog_get_peaks_counts(self._h, out))
         return int(out[0]), int(out[1])
 
     def batch_maxima(self, n):

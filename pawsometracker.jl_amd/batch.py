@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, frame_index_ptr, host_i32, host_table
+from ._args import device_array, device_frames, frame_index_ptr, host_i32, host_table, peaks_args
 
 
 class BatchTracker(_lib.TrackerHandle):
@@ -50,6 +50,33 @@ class BatchTracker(_lib.TrackerHandle):
             C.c_void_p(guesses.data_ptr()), n, C.c_void_p(out.data_ptr()),
             C.c_void_p(resp.data_ptr()) if want_resp else None))
         return (out, resp) if want_resp else out
+
+    def detect_peaks(self, frames, guesses, k, min_distance=None, frame_index=None, want_resp=False):
+        """The k best, mutually separated peaks of every window (pdog_detect_peaks; this library's addition, the rule is
+        stated in include/pawsome_peaks.h): frames, guesses and frame_index as for detect.  Pick 1 is detect's position; picks
+        2 ... k are the local maxima of the window's FP32 response inside the frame, taken greedily by value, none closer
+        than min_distance pixels (None: ceil(target_width)) to an earlier pick.  Returns (ij int32 cuda [n, k, 2], peak
+        float32 cuda [n, k], count int32 cuda [n]): count picks per window in pick order, the rest (0, 0) and -inf — and the
+        maps, float32 [n, win_w, win_h] as detect hands them out, when want_resp.  Without want_resp the maps live in scratch
+        of the tracker's (PDOG_MAP_MB) and large batches go in chunks."""
+        import torch
+        self.use_torch_stream()
+        device_frames(frames, "frames", 3, self._hw)
+        n = device_array(guesses, "guesses", torch.int32, (None, 2)).shape[0]
+        fi = frame_index_ptr(frame_index, n)
+        k, md = peaks_args(k, min_distance)
+        ij = torch.empty((n, k, 2), dtype=torch.int32, device=frames.device)
+        peak = torch.empty((n, k), dtype=torch.float32, device=frames.device)
+        count = torch.empty((n,), dtype=torch.int32, device=frames.device)
+        resp = None
+        if want_resp:
+            info = self.info()
+            resp = torch.empty((n, info.win_w, info.win_h), dtype=torch.float32, device=frames.device)
+        _lib.check(_lib.lib().pdog_detect_peaks(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
+            C.c_void_p(guesses.data_ptr()), n, k, md, C.c_void_p(ij.data_ptr()), C.c_void_p(peak.data_ptr()),
+            C.c_void_p(count.data_ptr()), C.c_void_p(resp.data_ptr()) if want_resp else None))
+        return (ij, peak, count, resp) if want_resp else (ij, peak, count)
 
     def detect_host(self, frames, guesses, frame_index=None):
         """The same n applications on frames in HOST memory (numpy uint8 [nf, h, w], the layout

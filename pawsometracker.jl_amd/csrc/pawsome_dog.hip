@@ -347,6 +347,7 @@ struct pdog_tracker {
     PinnedBuffer<int32_t> h_ingest_out;
     hipStream_t h2d_stream = nullptr;
     hipEvent_t ev_h2d[kIngestSlots] = {nullptr, nullptr, nullptr}, ev_used[kIngestSlots] = {nullptr, nullptr, nullptr};
+    pdog::PeaksState peaks; // pdog_detect_peaks (pawsome_peaks.hip): its scratch, switch and counters
 
     // Drains and destroys the streams and events; the buffers free themselves after that.
     ~pdog_tracker()
@@ -363,6 +364,13 @@ struct pdog_tracker {
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
 };
+
+pdog::PeaksState *pdog::peaks_state(pdog_tracker *t)
+{
+    t->peaks.device = t->device;
+    t->peaks.map_cap = t->sw.map_cap;
+    return &t->peaks;
+}
 
 namespace {
 
@@ -1583,6 +1591,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "no_prune") t->sw.no_prune = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
+    else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h
     else if (k == "no_fused_c") {
         t->sw.no_fused_c = on;
         t->fused_resident = 0;

@@ -6,8 +6,8 @@
 // raise_lds_limit is keyed on a kernel's address: a second translation unit that included one of those headers would get
 // private copies whose LDS limit was never raised.  So every include of a dog_*.hpp header of the tracker, every launch of
 // its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
-// this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip and pawsome_group.hip launch their own
-// kernels, dog_diag.hpp's and group_compact_kernel, which no other unit names.)  The one exception is dog_step.hpp, which
+// this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip and pawsome_peaks.hip launch
+// their own kernels, dog_diag.hpp's, group_compact_kernel and dog_peaks.hpp's, which no other unit names.)  The one exception is dog_step.hpp, which
 // pawsome_dog.hip and pawsome_clips.hip both include: its kernel uses no dynamic LDS, so no limit is ever raised for it and
 // a private copy per unit is harmless.
 #pragma once
@@ -164,6 +164,19 @@ private:
     hipEvent_t ev_ = nullptr;
     bool pending_ = false;
 };
+
+// What pdog_detect_peaks (pawsome_peaks.hip, a unit of its own with its own kernel) keeps on a tracker.  It is a member of
+// pdog_tracker, so it goes after the tracker's destructor has drained the stream; peaks_state (pawsome_dog.hip) hands it out
+// with the tracker's device and PDOG_MAP_MB filled in.
+struct PeaksState {
+    bool no_list = false;                   // pdog_set_tuning "peaks_no_list": the selection rounds scan the map (dog_peaks.hpp)
+    int device = 0;
+    size_t map_cap = 0;                     // PDOG_MAP_MB, bytes
+    DeviceBuffer<float> d_map;              // the chunk's response maps when the caller gives no buffer
+    DeviceBuffer<int32_t> d_ij1;            // [n][2] the detect kernels' positions: pick 1
+    DeviceBuffer<unsigned long long> d_stat; // [0] windows served, [1] windows whose candidate list overflowed
+};
+PeaksState *peaks_state(pdog_tracker *t);
 
 } // namespace pdog
 #pragma GCC visibility pop

@@ -377,7 +377,8 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
-                darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256):
+                darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
+                min_distance=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -394,10 +395,24 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     diagnostic(k0, overlays): overlays uint8 cuda [<= diagnostic_chunk, 360, 640], overlays[i] belonging to step k0 + i of
     ts and indices.  The buffer is reused once the sink returns: the sink consumes it with torch work on the current
     stream, or copies it.  ALL targets are drawn onto the same overlay, each with its own dot and trace — this library's
-    addition: the reference has one target per video.  ts, indices and sub are what they are without the keyword."""
+    addition: the reference has one target per video.  ts, indices and sub are what they are without the keyword.
+    `n_targets` = K (1 ... 32, with start_locations None) FINDS the targets instead: the K starts are the K best, mutually
+    separated peaks (BatchTracker.detect_peaks; none closer than `min_distance` pixels to another, None: ceil(target_width))
+    of the reference's bootstrap window — sz .÷ 4 around the frame centre on the first selected frame (:99-107) —, in pick
+    order: target 0 starts where the reference's own bootstrap puts its one target.  ValueError when fewer than K picks
+    have a positive response, or when n_targets comes with start_locations.  Everything after the starts is what a list of
+    K start locations gets."""
     import torch
+    from ._args import peaks_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
+    if n_targets is not None:
+        if start_locations is not None:
+            raise ValueError("n_targets finds the targets itself: give it, or start_locations, not both")
+        n_targets, md = peaks_args(n_targets, min_distance, "n_targets")
+        start_locations = [None] * n_targets
+    elif min_distance is not None:
+        raise ValueError("min_distance belongs to n_targets")
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3):
         raise TypeError("frames must be a uint8 cuda tensor [n_frames, h, w]")
     n, h, w = (int(v) for v in frames.shape)
@@ -422,7 +437,19 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             on_f0 = torch.full((nt,), f0, dtype=torch.int32, device=dev)
             starts = bt.detect(frames, guesses, on_f0)                                                    # :95
             auto = torch.tensor([loc is None for loc in locs], device=dev)
-            if bool(auto.any()):
+            if n_targets is not None:
+                bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, fill, device=dev.index)   # :102-103
+                try:
+                    ij, peak, _ = bt4.detect_peaks(frames, guesses[:1], n_targets, md or None, on_f0[:1])         # :104, and K - 1 more
+                    bt4.sync()
+                finally:
+                    bt4.close()
+                found = int((peak[0] > 0).sum())         # (pick order is value order: the positive ones come first)
+                if found < n_targets:
+                    raise ValueError(f"n_targets = {n_targets}, but the bootstrap window holds only {found} separated peak(s) "
+                                     "with a positive response")
+                starts = ij[0].contiguous()
+            elif bool(auto.any()):
                 bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, fill, device=dev.index)   # :102-103
                 try:
                     starts = torch.where(auto[:, None], bt4.detect(frames, guesses, on_f0), starts).contiguous()  # :104
