@@ -908,9 +908,9 @@ static __global__ __launch_bounds__(REFINE_NT) void dog_finish_kernel(const Fini
     // batches of hard windows to the response-map path (pawsome_dog.hip).  One plain store per batch — a system-scope
     // atomic per workgroup with flagged windows cost cfg5, where every window is flagged, 0.7 ms of PCIe atomics.
     if (blockIdx.x == 0 && tid == 0 && g.ex.range_err) {
-        __hip_atomic_store(g.ex.range_err + 1, (int)__hip_atomic_load(g.ex.stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED,
+        __hip_atomic_store(&g.ex.range_err->flagged, (uint32_t)__hip_atomic_load(g.ex.stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(g.ex.range_err + 2, fg.seq_windows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // … out of how many windows
+        __hip_atomic_store(&g.ex.range_err->finished, (uint32_t)fg.seq_windows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // … out of how many windows
     }
     // the windows of this workgroup that need the refinement (rare), one after the other, all threads on each
     constexpr int SLOT_CAP = 128;

@@ -24,6 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pdog_mailbox.hpp"
 
 namespace pdog {
 
@@ -124,7 +125,7 @@ __device__ __forceinline__ void peak_wave_reduce(Peak &p, int width = 64)
 // by a Float64 re-evaluation of its near-maximal pixels.
 struct ExactCtl {
     unsigned long long *stat; // [4] since the tracker was created: windows refined, column blocks rescanned, candidates, sequential chains run (diagnostics)
-    int *range_err;           // host-coherent words: [0] set when a guess lies where the reference raises BoundsError (:45-46) (2: a device-side wait gave up); [1] windows flagged for refinement by the finishing kernel, cumulative
+    KernelWords *range_err;   // the host-coherent words kernels raise and publish (pdog_mailbox.hpp), or null
     float T;                  // 2δ_main: the launched kernel family's own error bound (pawsome_dog.hip, exact_factors) for |pixel − dc| ≤ 255
     float T_rescan;           // δ_main + δ_rescan: the refinement's recomputed FP32 values (plain chains) against the main kernel's maximum
 };
@@ -146,7 +147,7 @@ __device__ __forceinline__ bool wait_counter(const unsigned *ctr, unsigned targe
             if (abort && __hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false; // a peer gave up
             if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_TICKS) {
                 if (abort) __hip_atomic_store(abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (x.range_err) __hip_atomic_store(x.range_err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (x.range_err) __hip_atomic_store(&x.range_err->raised, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 return false;
             }
         }
@@ -157,7 +158,7 @@ __device__ __forceinline__ bool wait_counter(const unsigned *ctr, unsigned targe
 __device__ __forceinline__ void range_check(const ExactCtl &x, int g1, int g2, int hw, int fh, int fw)
 {
     if (x.range_err && (g1 < -hw || g1 > fh + hw + 1 || g2 < -hw || g2 > fw + hw + 1))
-        __hip_atomic_store(x.range_err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&x.range_err->raised, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 struct LaunchGeo {

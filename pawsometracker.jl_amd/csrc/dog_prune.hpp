@@ -52,7 +52,7 @@ struct PruneGeo {
     float tmax;               // T_max (header comment)
     int darker;               // sign of the cell sums that point at a target
     unsigned long long *stat; // [0] kept, [1] total (slot, sub-chunk) pairs since the tracker was created, [2] arrivals of the batch in flight
-    unsigned long long *host; // one host-coherent word: the low halves of [0] and ([1] << 32) as the last workgroup of a batch saw them
+    uint64_t *host;           // Mailbox::prune_pub, one host-coherent word: the low halves of [0] and ([1] << 32) as the last workgroup of a batch saw them
 };
 
 constexpr int PRUNE_NT = 256;

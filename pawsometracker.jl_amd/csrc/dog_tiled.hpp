@@ -120,7 +120,7 @@ __global__ __launch_bounds__(FUSED_NT) void dog_tiled_kernel(const std::conditio
                 if (__hip_atomic_load(tg.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return 1;
                 if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_TICKS) {
                     __hip_atomic_store(tg.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (g.ex.range_err) __hip_atomic_store(g.ex.range_err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if (g.ex.range_err) __hip_atomic_store(&g.ex.range_err->raised, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     return 1;
                 }
             }

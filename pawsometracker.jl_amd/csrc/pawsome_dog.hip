@@ -6,6 +6,8 @@
 // device; the functor (:55-62) becomes kernel launches on a HIP stream.
 // There is NO CPU fallback: without a gfx950 device pdog_create fails.
 #include "pdog_host.hpp"
+#include "pdog_mailbox.hpp"
+#include "pdog_policy.hpp"
 #include "dog_kernels.hpp"
 #include "dog_roll.hpp"
 #include "dog_prune.hpp"
@@ -253,6 +255,43 @@ const Variant *find_variant(int id)
     return nullptr;
 }
 
+// ---- what make_plan derives per kernel family, and what a family keeps between launches ----
+// what the fused and tiled kernels share: the instance and, for the tile one workgroup works on, pitches and task sizes (plan_tile)
+struct TilePlan {
+    bool c = false; // the compile-time-l instance (lat_lengths.def) and its wider tile layout
+    int pitchA = 0, pitchV = 0, pr = 0, pc = 0, cshift = 0;
+};
+// fused kernel (dog_fused.hpp): one workgroup per window, the whole tile in LDS
+struct FusedPlan : TilePlan {
+    bool ok = false;               // the window's tile fits in LDS: the fused kernel takes small batches and short chains
+    int resident = 0;              // workgroups the device keeps resident (the grid is capped there: a workgroup walks several windows); 0: launch_fused asks
+    size_t lds = 0;                // dynamic LDS: the tile + RT, or the scratch of the refinement it may run in the same memory
+    int ref_cbw = 1, ref_rows = 8; // refinement geometry inside the kernel (its scratch is the kernel's own LDS)
+};
+// tiled kernel (dog_tiled.hpp): one large window cut into sub-windows, a workgroup each, one launch per batch / clip
+struct TiledPlan : TilePlan {
+    bool ok = false;
+    int sn1 = 0, sn2 = 0, ns1 = 0, ns2 = 0;
+    int ref_cbw = 1, ref_rows = 8, resident = 0; // refinement scratch geometry; workgroups the device keeps resident
+    size_t lds = 0;
+};
+struct TiledRun {
+    DeviceBuffer<int> d_ctl; // [cap][4]: current guess (2), partial arrivals, frame flag; then the abort word
+    int ctl_cap() const { return (int)(d_ctl.capacity() / 4); }
+    DeviceBuffer<unsigned long long> d_slots; // [clips][3][nsub][2] tagged partials of the tiled kernel's clips (dog_tiled.hpp): two sets by frame parity + the V set
+    unsigned tag = 0;        // advanced by chain_len + 1 per clip launch: a frame's tag never repeats
+};
+// host-batch ingest (pdog_detect_batch_host): rotating pinned staging / device tile slots, created at the first call
+struct Ingest {
+    static constexpr int kSlots = 3;
+    PinnedBuffer<uint8_t> h_stage[kSlots];
+    DeviceBuffer<uint8_t> d_tiles[kSlots];
+    DeviceBuffer<int32_t> d_guess, d_out;
+    PinnedBuffer<int32_t> h_out;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_h2d[kSlots] = {nullptr, nullptr, nullptr}, ev_used[kSlots] = {nullptr, nullptr, nullptr};
+};
+
 } // namespace
 
 struct pdog_tracker {
@@ -266,38 +305,26 @@ struct pdog_tracker {
     int nthin = 0, thin_x0 = 0; // window columns handled by the thin-remainder kernel
     bool forced_variant = false;   // pdog_set_variant pinned the kernel: no batch-size switching
     bool small_twopass = false;    // two-pass kernels are set up and may take over small batches
-    bool fused_ok = false;         // the window's tile fits in LDS: the fused kernel takes small batches and short chains
-    int fused_resident = 0;        // workgroups of the fused kernel the device keeps resident (its grid is capped there: a workgroup walks several windows)
-    bool fused_c = false;          // … through its compile-time-l instance (dog_fused.hpp: l = 65, the default tracker's), whose tile layout is wider
+    FusedPlan fused;
     int hp_rows = HP_ROWS;         // RT rows (window columns) per column-pass workgroup: 16 (P = 13) or 8 (P = 7)
     DeviceBuffer<int32_t> d_chain_tmp; // [2][n_clips][2]: current guesses / step results of multi-clip chains
     // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it
     StagedUpload<int32_t> table;
     std::vector<int32_t> table_len;    // steps per clip of the table being served
     int tp_ph1 = 13, tp_php = 7;   // outputs per task of the two-pass row / column pass (pick_twopass_p)
-    // tiled kernel (dog_tiled.hpp): one large window cut into sub-windows, a workgroup each, one launch per batch / clip
-    bool tiled_ok = false;
-    int tiled_sn1 = 0, tiled_sn2 = 0, tiled_ns1 = 0, tiled_ns2 = 0, tiled_pr = 0, tiled_pc = 0, tiled_cshift = 0;
-    int tiled_ref_cbw = 1, tiled_ref_rows = 8, tiled_resident = 0; // refinement scratch geometry; workgroups the device keeps resident
-    size_t tiled_lds = 0;
-    bool tiled_c = false;          // the tiled kernel's compile-time-l instance (l = 65) and tile layout
-    DeviceBuffer<int> d_tiled_ctl; // [cap][4]: current guess (2), partial arrivals, frame flag; then the abort word
-    int tiled_ctl_cap() const { return (int)(d_tiled_ctl.capacity() / 4); }
-    DeviceBuffer<unsigned long long> d_tiled_slots; // [clips][3][nsub][2] tagged partials of the tiled kernel's clips (dog_tiled.hpp): two sets by frame parity + the V set
-    unsigned tiled_tag = 0;        // advanced by chain_len + 1 per clip launch: a frame's tag never repeats
+    TiledPlan tiled;
+    TiledRun tiled_run;
     // two-pass path scratch
     DeviceBuffer<f2> d_V;
-    // exact mode on the batch kernels of short kernels (roll / ring): windows flagged per batch as the finishing kernel reports
-    // them (h_pinned[6], cumulative); batches of HARD windows (noise only, ±1-level targets: every window flagged) switch to
-    // the response-map refinement like the two-pass path — 81–206 ms per 4096 windows of 257×257 without it
-    unsigned flag_last = 0, win_last = 0, win_launched = 0; // flagged / finished windows last seen (h_pinned[6], [7]); windows handed to finishing kernels so far
-    int flag_calm = 0;
-    bool roll_map = false;
-    // kept ranges on the roll family's batch path (dog_prune.hpp; launch_strips, "pruning policy")
+    // exact mode on the batch kernels of short kernels (roll / ring): batches of HARD windows (noise only, ±1-level targets:
+    // every window flagged) switch to the response-map refinement like the two-pass path — 81–206 ms per 4096 windows of
+    // 257×257 without it (pdog_policy.hpp)
+    MapPolicy map_policy;
+    unsigned win_launched = 0;               // windows handed to finishing kernels so far
+    // kept ranges on the roll family's batch path (dog_prune.hpp; pdog_policy.hpp)
+    PrunePolicy prune_policy;
     double K_norm = 0;                       // ‖K‖₂ of the dense kernel, rounded up (dog_kernel_norm_up)
     DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] arrivals of the pre-pass in flight
-    unsigned prune_kept_last = 0, prune_total_last = 0; // the published counts last seen (h_pinned[8], [9])
-    int prune_sleep = 0;                     // batches left to run dense before the next probe
     int last_n = 0, last_nslots = 0;         // windows and partial slots per window of the last launch_strips batch (pdog_get_batch_maxima)
     DeviceBuffer<float> d_map; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
     DeviceBuffer<int> d_dc;    // [cap] DC levels, then [cap] the windows' own V (exact mode)
@@ -328,25 +355,14 @@ struct pdog_tracker {
     double exact_T64 = 0.0;           // 2δ64: separable Float64 against the reference's dense Float64
     DeviceBuffer<unsigned long long> d_ref_stat;
     int ref_cbw = 1, ref_rows = 8;    // refinement: window columns per block; rows of the block's pixel tile resident in LDS at a time
-    int fused_ref_cbw = 1, fused_ref_rows = 8; // the same inside the fused kernel (its scratch is that kernel's LDS)
     // host-path staging (pdog_detect_host / chain seed)
     DeviceBuffer<uint8_t> d_frame;
     DeviceBuffer<int32_t> d_small; // [0..1] guess, [2..3] result
-    // pinned, host-coherent, device-mapped mailbox: [0..1] guess, [2..3] result, [4] completion ticket of the functor,
-    // [5] raised by kernels (drain_and_check), [6] / [7] flagged / finished windows (launch_strips), [8] / [9] kept / total
-    // (slot, sub-chunk) pairs of the pre-pass (one 64-bit word: dog_prune.hpp)
-    PinnedBuffer<int32_t> h_pinned{hipHostMallocMapped | hipHostMallocCoherent};
+    PinnedBuffer<Mailbox> h_pinned{hipHostMallocMapped | hipHostMallocCoherent}; // one element (pdog_mailbox.hpp)
     int32_t ticket = 0;
     DeviceBuffer<float> d_resp;
     PinnedBuffer<uint8_t> h_tile{hipHostMallocMapped}; // the functor's window tile when the kernels read it in place
-    // host-batch ingest (pdog_detect_batch_host): rotating pinned staging / device tile slots
-    static constexpr int kIngestSlots = 3;
-    PinnedBuffer<uint8_t> h_stage[kIngestSlots];
-    DeviceBuffer<uint8_t> d_tiles[kIngestSlots];
-    DeviceBuffer<int32_t> d_ingest_guess, d_ingest_out;
-    PinnedBuffer<int32_t> h_ingest_out;
-    hipStream_t h2d_stream = nullptr;
-    hipEvent_t ev_h2d[kIngestSlots] = {nullptr, nullptr, nullptr}, ev_used[kIngestSlots] = {nullptr, nullptr, nullptr};
+    Ingest ingest;
     pdog::PeaksState peaks; // pdog_detect_peaks (pawsome_peaks.hip): its scratch, switch and counters
 
     // Drains and destroys the streams and events; the buffers free themselves after that.
@@ -354,10 +370,10 @@ struct pdog_tracker {
     {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (hipStream_t s : {h2d_stream, aux_stream})
+        for (hipStream_t s : {ingest.stream, aux_stream})
             if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-        for (int k = 0; k < kIngestSlots; ++k)
-            for (hipEvent_t e : {ev_h2d[k], ev_used[k]})
+        for (int k = 0; k < Ingest::kSlots; ++k)
+            for (hipEvent_t e : {ingest.ev_h2d[k], ingest.ev_used[k]})
                 if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {ev_fork, ev_join, ev_switch})
             if (e) (void)hipEventDestroy(e);
@@ -399,8 +415,8 @@ const LatInstances &lat_instances(int L, bool compile_time)
         if (row.L == L) return row;
     return runtime_length;
 }
-const LatInstances &fused_instances(const pdog_tracker *t) { return lat_instances(t->L, t->fused_c); }
-const LatInstances &tiled_instances(const pdog_tracker *t) { return lat_instances(t->L, t->tiled_c); }
+const LatInstances &fused_instances(const pdog_tracker *t) { return lat_instances(t->L, t->fused.c); }
+const LatInstances &tiled_instances(const pdog_tracker *t) { return lat_instances(t->L, t->tiled.c); }
 int raise_lds_limits(const void *const (&fns)[3], size_t bytes)
 {
     for (const void *fn : fns)
@@ -488,39 +504,10 @@ int pick_hpass_outputs(int nout)
     auto fill = [&](int p) { return (double)nout / (double)(round_up(nout, 32 * p)); };
     return fill(9) > fill(7) + 0.05 ? 9 : 7;
 }
-// Exact mode's refinement (dog_exact.hpp) works on blocks of `cbw` window columns whose row-pass result (two doubles
-// per element in the Float64 stage) fits ≈24 KB of LDS; the block's pixels go through an LDS tile — all n1 + l − 1 rows
-// resident when that fits 100 KB in total (l ≲ 150: a candidate's exact chain then reads LDS), otherwise ≈24 KB slices.
 int refine_slice_rows(int NA, int L, int cbw, size_t budget)
 {
     return (int)std::max<size_t>(8, std::min<size_t>((size_t)NA, budget / (size_t)refine_tile_pitch(cbw, L)));
 }
-size_t fused_tile_lds(const pdog_tracker *t)
-{
-    return t->fused_c ? fusedc_lds_bytes(t->n1, t->n2, t->L) : fused_lds_bytes(t->n1, t->n2, t->L);
-}
-void setup_refine_geometry(pdog_tracker *t)
-{
-    const int NA = t->n1 + t->L - 1;
-    t->ref_cbw = std::max(1, std::min({8, t->n2, (int)(24576 / ((size_t)NA * 16))}));
-    t->ref_rows = refine_lds_bytes(t->n1, t->L, t->ref_cbw, NA) <= 100 * 1024 ? NA : refine_slice_rows(NA, t->L, t->ref_cbw, 24576);
-    // inside the fused kernel the scratch is that kernel's own LDS (tile + RT, free by then): the widest block that fits
-    // it with the whole pixel tile resident (a window whose tile fits as floats has room for it as bytes)
-    t->fused_ref_cbw = 1;
-    t->fused_ref_rows = NA;
-    t->fused_c = fused_has_instance(t->L) && fusedc_lds_bytes(t->n1, t->n2, t->L) <= kMaxLds - 1024;
-    if (t->sw.no_fused_c) t->fused_c = false;
-    const size_t have = fused_tile_lds(t);
-    for (int cbw = std::min(8, t->n2); cbw >= 1; --cbw)
-        if (refine_lds_bytes(t->n1, t->L, cbw, NA) <= have) { t->fused_ref_cbw = cbw; break; }
-    if (refine_lds_bytes(t->n1, t->L, 1, NA) > kMaxLds - 1024) t->fused_ref_rows = refine_slice_rows(NA, t->L, 1, 24576);
-}
-// dynamic LDS of the fused kernel: its tile + RT, or the scratch of the refinement it may run in the same memory
-size_t fused_total_lds(const pdog_tracker *t)
-{
-    return std::max(fused_tile_lds(t), refine_lds_bytes(t->n1, t->L, t->fused_ref_cbw, t->fused_ref_rows));
-}
-
 int ensure_capacity(pdog_tracker *t, int n);
 enum KernelFamily : int { kFamRoll, kFamRing, kFamFused, kFamTwoPass8, kFamTwoPass16 };
 ExactCtl exact_ctl(const pdog_tracker *t, KernelFamily fam);
@@ -536,6 +523,38 @@ int pick_outputs_per_task(int lines, int nout, std::initializer_list<int> ps, do
         if (!best || cost < best_cost) { best = p; best_cost = cost; }
     }
     return best;
+}
+
+// Pitches and task sizes of a tile of n1 × n2 outputs (the window, or a sub-window of it) under the instance p.c names.
+void plan_tile(TilePlan &p, int n1, int n2, int L)
+{
+    p.pitchA = p.c ? fusedc_pitch_a(n2, L) : fused_pitch_a(n2, L);
+    p.pitchV = fused_pitch_v(n1, L);
+    for (p.cshift = 0; (1 << p.cshift) < (n2 + L - 1 + 3) / 4;) ++p.cshift;
+    p.pr = p.c ? fusedc_row_outputs(n1 + L - 1, n2) : pick_outputs_per_task(n1 + L - 1, n2, {3, 4, 5, 6, 8}, 2.0);
+    p.pc = pick_outputs_per_task(n2, n1, {2, 3, 4, 6, 8}, 1.5);
+}
+
+// The fused kernel for this geometry: its instance, its LDS and the refinement's share of it, whether it fits (the one place
+// that decides), and what a launch copies into FusedGeo.  `resident` is left for make_plan.
+FusedPlan plan_fused(const pdog_tracker *t)
+{
+    const int NA = t->n1 + t->L - 1, TWin = t->n2 + t->L - 1;
+    FusedPlan f;
+    f.c = fused_has_instance(t->L) && fusedc_lds_bytes(t->n1, t->n2, t->L) <= kMaxLds - 1024 && !t->sw.no_fused_c;
+    // inside the fused kernel the refinement's scratch is that kernel's own LDS (tile + RT, free by then): the widest block that
+    // fits it with the whole pixel tile resident (a window whose tile fits as floats has room for it as bytes)
+    const size_t tile = f.c ? fusedc_lds_bytes(t->n1, t->n2, t->L) : fused_lds_bytes(t->n1, t->n2, t->L);
+    f.ref_cbw = 1;
+    f.ref_rows = NA;
+    for (int cbw = std::min(8, t->n2); cbw >= 1; --cbw)
+        if (refine_lds_bytes(t->n1, t->L, cbw, NA) <= tile) { f.ref_cbw = cbw; break; }
+    if (refine_lds_bytes(t->n1, t->L, 1, NA) > kMaxLds - 1024) f.ref_rows = refine_slice_rows(NA, t->L, 1, 24576);
+    f.lds = std::max(tile, refine_lds_bytes(t->n1, t->L, f.ref_cbw, f.ref_rows));
+    f.ok = f.lds <= kMaxLds - 1024 && TWin <= 4 * FUSED_NT && t->fw >= 4;
+    plan_tile(f, t->n1, t->n2, t->L);
+    if (t->sw.fused_pr) { f.pr = t->sw.fused_pr; f.pc = t->sw.fused_pc; } // tuning switch PDOG_FUSED_P
+    return f;
 }
 
 // Tiled kernel (dog_tiled.hpp): windows too large for the fused kernel, cut into sub-windows of ≈48 rows/columns (a
@@ -557,14 +576,14 @@ void fit_refine_scratch(const pdog_tracker *t, size_t base, int *ref_cbw, int *r
         return;
     }
 }
-int setup_tiled(pdog_tracker *t)
+int plan_tiled(pdog_tracker *t)
 {
-    t->tiled_ok = false;
+    TiledPlan &p = t->tiled = TiledPlan();
     // partial slots per window: the most over all variants, so that a later pdog_set_variant never reallocates …
     t->part_slots = (t->n2 + 7) / 8;
     for (int i = 0; i < kNumVariants; ++i)
         if (!kVariants[i].fused) t->part_slots = std::max(t->part_slots, (t->n2 + kVariants[i].tw() - 1) / kVariants[i].tw() + kThinMax);
-    if ((t->fused_ok && !t->sw.tiled_force) || t->sw.no_tiled || t->fw < 4) return PDOG_OK;
+    if ((t->fused.ok && !t->sw.tiled_force) || t->sw.no_tiled || t->fw < 4) return PDOG_OK;
     // Sub-window edge: ≈32 measured best for a 257×257 window (81 workgroups: 13.9 µs per frame; 48: 15.3), but beyond
     // ≈128 workgroups the partial exchange costs more than smaller tiles save (513×513: 121 workgroups of 47 → 17.8 µs,
     // 169 of 40 → 21.9); long kernels need smaller sub-windows for their halo to fit LDS.
@@ -572,7 +591,7 @@ int setup_tiled(pdog_tracker *t)
     size_t need = 0;
     bool found = false;
     const int user = t->sw.tiled_sub;
-    t->tiled_c = fused_has_instance(t->L) && !t->sw.no_fused_c;
+    p.c = fused_has_instance(t->L) && !t->sw.no_fused_c;
     // (round 3, with the one-round-trip exchange: 129×129 at 24 → 36 workgroups 8.6–8.8 µs against 9.2–9.7 at 32 → 25; 257×257 at 20 / 24 /
     // 32: 9.8–10.1 / 10.2 / 10.2–10.5 — kept at 32 so that three clips stay resident; 513×513 at 36 → 225 workgroups 12.2–12.6 against 13.0 at 48)
     bool small_first = true;
@@ -586,7 +605,7 @@ int setup_tiled(pdog_tracker *t)
         sn2 = (t->n2 + ns2 - 1) / ns2;
         ns1 = (t->n1 + sn1 - 1) / sn1;
         ns2 = (t->n2 + sn2 - 1) / sn2;
-        need = t->tiled_c ? fusedc_lds_bytes(sn1, sn2, t->L) : fused_lds_bytes(sn1, sn2, t->L);
+        need = p.c ? fusedc_lds_bytes(sn1, sn2, t->L) : fused_lds_bytes(sn1, sn2, t->L);
         const bool fits = need <= kMaxLds - 1024 && sn2 + t->L - 1 <= 4 * FUSED_NT && (long long)t->n1 * t->n2 < (1 << 24) && // (a partial's index shares a word with 8 tag bits)
                           (long long)ns1 * ns2 <= (target >= 32 && !user ? 128 : TILED_SLOT_CAP);
         if (fits && !(probe24 && !user && (long long)ns1 * ns2 > 48)) { found = true; break; }
@@ -596,22 +615,18 @@ int setup_tiled(pdog_tracker *t)
     // the refinement's scratch is the kernel's own LDS: at least its smallest form must fit; then the widest block that does
     const size_t base = std::max(need, refine_lds_bytes(t->n1, t->L, 1, 8));
     if (base > kMaxLds - 1024) return PDOG_OK;
-    fit_refine_scratch(t, base, &t->tiled_ref_cbw, &t->tiled_ref_rows);
-    t->tiled_sn1 = sn1; t->tiled_sn2 = sn2; t->tiled_ns1 = ns1; t->tiled_ns2 = ns2;
-    t->tiled_lds = base;
-    t->tiled_cshift = 0;
-    while ((1 << t->tiled_cshift) < (sn2 + t->L - 1 + 3) / 4) ++t->tiled_cshift;
-    t->tiled_pr = t->tiled_c ? fusedc_row_outputs(sn1 + t->L - 1, sn2) : pick_outputs_per_task(sn1 + t->L - 1, sn2, {3, 4, 5, 6, 8}, 2.0);
-    t->tiled_pc = pick_outputs_per_task(sn2, sn1, {2, 3, 4, 6, 8}, 1.5);
+    fit_refine_scratch(t, base, &p.ref_cbw, &p.ref_rows);
+    p.sn1 = sn1; p.sn2 = sn2; p.ns1 = ns1; p.ns2 = ns2;
+    p.lds = base;
+    plan_tile(p, sn1, sn2, t->L);
     if (int rc = raise_lds_limits(tiled_instances(t).tiled, base)) return rc;
-    int per_cu = 0, cus = 0, coop = 0;
-    t->tiled_resident = 0; // chains need every workgroup of a clip resident at once: a cooperative launch, if the device has them
+    int per_cu = 0, cus = 0, coop = 0; // chains need every workgroup of a clip resident at once: a cooperative launch, if the device has them
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, t->device) == hipSuccess && coop &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tiled_instances(t).tiled[kLatPlain], FUSED_NT, base) == hipSuccess && per_cu >= 1 &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess)
-        t->tiled_resident = per_cu * cus;
+        p.resident = per_cu * cus;
     t->part_slots = std::max(t->part_slots, 2 * ns1 * ns2); // … and the tiled kernel's partials: two sets per window
-    t->tiled_ok = true;
+    p.ok = true;
     return PDOG_OK;
 }
 
@@ -662,7 +677,7 @@ void use_partials(const pdog_tracker *t, LaunchGeo &g)
 // What launch_tiled takes: n windows, or n clips of chain_len > 1 frames with every sub-window's workgroup resident at once.
 bool tiled_serves(const pdog_tracker *t, int n, int chain_len)
 {
-    return t->tiled_ok && n >= 1 && (chain_len <= 1 || (long long)n * t->tiled_ns1 * t->tiled_ns2 <= t->tiled_resident);
+    return t->tiled.ok && n >= 1 && (chain_len <= 1 || (long long)n * t->tiled.ns1 * t->tiled.ns2 <= t->tiled.resident);
 }
 
 // req.n windows (chain_len = 1: independent; ordinary launch) or req.n clips of chain_len frames (cooperative launch: the
@@ -672,10 +687,12 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
     *launched = false;
     const int n = req.n, chain_len = req.chain_len;
     if (!tiled_serves(t, n, chain_len)) return PDOG_OK;
-    const int nsub = t->tiled_ns1 * t->tiled_ns2;
+    const TiledPlan &p = t->tiled;
+    TiledRun &run = t->tiled_run;
+    const int nsub = p.ns1 * p.ns2;
     if (int rc = ensure_capacity(t, n)) return rc;
     // the kernel leaves its counters at zero; the last word is the abort word
-    if (int rc = t->d_tiled_ctl.reserve(4 * (size_t)n + 1, &t->stream, true)) return rc;
+    if (int rc = run.d_ctl.reserve(4 * (size_t)n + 1, &t->stream, true)) return rc;
     TiledTableGeo tg; // (an ordinary launch takes its TiledGeo part)
     std::memset(&tg, 0, sizeof tg);
     LaunchGeo &g = tg.g;
@@ -685,60 +702,65 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
     g.nstrips = nsub; g.nslots = nsub; g.nblocks = n * nsub;
     tg.NA = t->n1 + t->L - 1;
     tg.TWin = t->n2 + t->L - 1;
-    tg.sn1 = t->tiled_sn1; tg.sn2 = t->tiled_sn2; tg.ns1 = t->tiled_ns1; tg.ns2 = t->tiled_ns2;
-    tg.pitchA = t->tiled_c ? fusedc_pitch_a(t->tiled_sn2, t->L) : fused_pitch_a(t->tiled_sn2, t->L);
-    tg.pitchV = fused_pitch_v(t->tiled_sn1, t->L);
-    tg.cshift = t->tiled_cshift;
-    tg.pr = t->tiled_pr;
-    tg.pc = t->tiled_pc;
+    tg.sn1 = p.sn1; tg.sn2 = p.sn2; tg.ns1 = p.ns1; tg.ns2 = p.ns2;
+    tg.pitchA = p.pitchA;
+    tg.pitchV = p.pitchV;
+    tg.cshift = p.cshift;
+    tg.pr = p.pr;
+    tg.pc = p.pc;
     tg.chain_len = chain_len;
     tg.out_ij = req.out_ij;
     tg.done_flag = req.done_flag;
     tg.done_value = req.done_value;
     tg.progress = req.progress ? 1 : 0;
     tg.rp = t->exact ? t->d_rp.get() : nullptr;
-    tg.ref_cbw = t->tiled_ref_cbw;
-    tg.ref_rows = t->tiled_ref_rows;
+    tg.ref_cbw = p.ref_cbw;
+    tg.ref_rows = p.ref_rows;
     tg.dc_host = req.dc_host;
-    tg.cur = t->d_tiled_ctl.get();
-    tg.sync = reinterpret_cast<unsigned *>(t->d_tiled_ctl.get() + 2 * (size_t)t->tiled_ctl_cap());
-    tg.abort = reinterpret_cast<unsigned *>(t->d_tiled_ctl.get() + 4 * (size_t)t->tiled_ctl_cap());
+    tg.cur = run.d_ctl.get();
+    tg.sync = reinterpret_cast<unsigned *>(run.d_ctl.get() + 2 * (size_t)run.ctl_cap());
+    tg.abort = reinterpret_cast<unsigned *>(run.d_ctl.get() + 4 * (size_t)run.ctl_cap());
     tg.fault_inject = t->sw.fault_inject ? 1 : 0;
     tg.tab = req.table;
     tg.slots = nullptr;
     tg.tag_base = 0;
     if (chain_len > 1) {
-        if (int rc = t->d_tiled_slots.reserve((size_t)n * 3 * nsub * 2, &t->stream, true)) return rc; // zeroed: tag 0 is never a frame's
-        tg.slots = t->d_tiled_slots.get();
-        tg.tag_base = t->tiled_tag;
-        t->tiled_tag += (unsigned)chain_len + 1u;
+        if (int rc = run.d_slots.reserve((size_t)n * 3 * nsub * 2, &t->stream, true)) return rc; // zeroed: tag 0 is never a frame's
+        tg.slots = run.d_slots.get();
+        tg.tag_base = run.tag;
+        run.tag += (unsigned)chain_len + 1u;
     }
     const void *fn = tiled_instances(t).tiled[req.table.index ? kLatTable : req.out_resp ? kLatResp : kLatPlain];
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
     if (chain_len > 1) {
         void *args[] = {(void *)&tg, (void *)&tr, (void *)&tc};
-        const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(n * nsub), dim3(FUSED_NT), args, (unsigned)t->tiled_lds, t->stream);
+        const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(n * nsub), dim3(FUSED_NT), args, (unsigned)p.lds, t->stream);
         if (e != hipSuccess) { (void)hipGetLastError(); return PDOG_OK; } // refused: the caller's other paths
     } else {
-        hipLaunchKernelGGL((tiled_fn_t)fn, dim3(n * nsub), dim3(FUSED_NT), t->tiled_lds, t->stream, static_cast<const TiledGeo &>(tg), tr, tc);
+        hipLaunchKernelGGL((tiled_fn_t)fn, dim3(n * nsub), dim3(FUSED_NT), p.lds, t->stream, static_cast<const TiledGeo &>(tg), tr, tc);
         HIP_TRY(hipGetLastError());
     }
     *launched = true;
     return PDOG_OK;
 }
 
+// Everything the tracker derives from its geometry, its switches and the pinned variant id (`forced`, or -1): the batch kernel
+// and its strips, the refinement's geometry, the fused and tiled kernels' plans, the two-pass task sizes, part_slots — and the
+// LDS limits of every kernel those may launch, which only ever rise.  pdog_create, pdog_set_variant and the pdog_set_tuning
+// keys that change an input call this and nothing else; no caller patches a derived field.  A variant that does not fit is
+// refused before anything changes.
 // Kernel lengths with a roll instance: l = 17 … 149 (dog_roll.hpp, roll_lengths.def; l = 101 … 149 at two waves per SIMD,
 // without spills); longer kernels take the two-pass path.
-
-int choose_variant(pdog_tracker *t, int forced)
+int make_plan(pdog_tracker *t, int forced)
 {
+    FusedPlan fused = plan_fused(t);
     const Variant *best = nullptr;
     double best_cost = 0;
     for (int i = 0; i < kNumVariants; ++i) {
         const Variant &v = kVariants[i];
         if (forced >= 0 && v.id != forced) continue;
         if (v.fused) { // never the tracker's batch kernel unless forced; small batches and chains reach it below
-            if (forced == v.id && fused_total_lds(t) <= kMaxLds - 1024 && t->n2 + t->L - 1 <= 4 * FUSED_NT && t->fw >= 4) best = &v;
+            if (forced == v.id && fused.ok) best = &v;
             continue;
         }
         if (v.LT != 0 && v.LT != t->L) continue;
@@ -772,10 +794,18 @@ int choose_variant(pdog_tracker *t, int forced)
     t->thin_x0 = 0;
     t->forced_variant = forced >= 0;
     t->small_twopass = false;
-    t->fused_ok = fused_total_lds(t) <= kMaxLds - 1024 && t->n2 + t->L - 1 <= 4 * FUSED_NT && t->fw >= 4;
-    if (t->fused_ok)
-        if (int rc = raise_lds_limits(fused_instances(t).fused, fused_total_lds(t))) return rc;
-    if (int rc = setup_tiled(t)) return rc;
+    // Exact mode's refinement (dog_exact.hpp) works on blocks of `cbw` window columns whose row-pass result (two doubles
+    // per element in the Float64 stage) fits ≈24 KB of LDS; the block's pixels go through an LDS tile — all n1 + l − 1 rows
+    // resident when that fits 100 KB in total (l ≲ 150: a candidate's exact chain then reads LDS), otherwise ≈24 KB slices.
+    const int NA = t->n1 + t->L - 1;
+    t->ref_cbw = std::max(1, std::min({8, t->n2, (int)(24576 / ((size_t)NA * 16))}));
+    t->ref_rows = refine_lds_bytes(t->n1, t->L, t->ref_cbw, NA) <= 100 * 1024 ? NA : refine_slice_rows(NA, t->L, t->ref_cbw, 24576);
+    // (the count of resident workgroups stands while the instance and its LDS do; launch_fused asks again otherwise)
+    if (fused.c == t->fused.c && fused.lds == t->fused.lds) fused.resident = t->fused.resident;
+    t->fused = fused;
+    if (fused.ok)
+        if (int rc = raise_lds_limits(fused_instances(t).fused, fused.lds)) return rc;
+    if (int rc = plan_tiled(t)) return rc;
     if (best->fused) { t->nstrips = 1; return PDOG_OK; }
     {
         // The two-pass kernels spread one window over dozens of workgroups, so they win whenever the batch
@@ -849,9 +879,9 @@ int path_for_batch(const pdog_tracker *t, int n)
     // (… and since a workgroup of the fused kernel walks several windows — dispatch, prologue and first tap loads once per workgroup — 45×45 windows:
     // 1024 / 2048 / 4096 per batch 44.5 / 83 / 155 µs against the roll kernel's 79 / 103 / 163: windows below 3000 pixels stay on it at any batch size)
     const bool few = v.twopass ? n <= 256 : ((long long)n * (t->nstrips + (t->nthin ? 1 : 0)) < 1200 || (long long)t->n1 * t->n2 < 3000);
-    if (t->sw.tiled_force && t->tiled_ok && n <= t->sw.tiled_batch) return kPathTiled; // experiment switch
-    if (few && t->fused_ok) return kPathFused;
-    if (t->tiled_ok && n <= t->sw.tiled_batch) return kPathTiled; // one or two windows too large for the fused kernel: one launch (dog_tiled.hpp)
+    if (t->sw.tiled_force && t->tiled.ok && n <= t->sw.tiled_batch) return kPathTiled; // experiment switch
+    if (few && t->fused.ok) return kPathFused;
+    if (t->tiled.ok && n <= t->sw.tiled_batch) return kPathTiled; // one or two windows too large for the fused kernel: one launch (dog_tiled.hpp)
     if (v.twopass || (few && t->small_twopass)) return kPathTwoPass;
     return v.id;
 }
@@ -888,7 +918,7 @@ ExactCtl exact_ctl(const pdog_tracker *t, KernelFamily fam)
 {
     ExactCtl x;
     x.stat = t->d_ref_stat.get();
-    x.range_err = t->h_pinned.device() ? t->h_pinned.device() + 5 : nullptr;
+    x.range_err = t->h_pinned.device() ? &t->h_pinned.device()->kernel : nullptr;
     const double F = fam == kFamRoll ? t->F_sym_int : fam == kFamRing ? t->F_ring : fam == kFamFused ? t->F_sym_sep : twopass_factor(t, fam == kFamTwoPass8);
     const double u = std::ldexp(1.0, -24);
     x.T = t->exact_all ? __builtin_huge_valf() : std::nextafter((float)(2.0 * u * F * 1.02 + 2e-9), 1.0f);
@@ -947,6 +977,7 @@ int launch_finish(pdog_tracker *t, const LaunchGeo &g, const Finish &f)
 int launch_fused(pdog_tracker *t, const Request &req)
 {
     const int n = req.n, chain_len = req.chain_len;
+    FusedPlan &p = t->fused;
     FusedTableGeo fg; // (a launch without a table takes its FusedGeo part)
     fg.tab = req.table;
     fg.g = base_geo(t, req);
@@ -954,29 +985,27 @@ int launch_fused(pdog_tracker *t, const Request &req)
     g.nstrips = 1; g.nslots = 1; g.nblocks = n;
     fg.NA = t->n1 + t->L - 1;
     fg.TWin = t->n2 + t->L - 1;
-    fg.pitchA = t->fused_c ? fusedc_pitch_a(t->n2, t->L) : fused_pitch_a(t->n2, t->L);
-    fg.pitchV = fused_pitch_v(t->n1, t->L);
-    fg.cshift = 0;
-    while ((1 << fg.cshift) < (fg.TWin + 3) / 4) ++fg.cshift;
-    fg.pr = t->fused_c ? fusedc_row_outputs(fg.NA, t->n2) : pick_outputs_per_task(fg.NA, t->n2, {3, 4, 5, 6, 8}, 2.0);
-    fg.pc = pick_outputs_per_task(t->n2, t->n1, {2, 3, 4, 6, 8}, 1.5);
-    if (t->sw.fused_pr) { fg.pr = t->sw.fused_pr; fg.pc = t->sw.fused_pc; } // tuning switch PDOG_FUSED_P
+    fg.pitchA = p.pitchA;
+    fg.pitchV = p.pitchV;
+    fg.cshift = p.cshift;
+    fg.pr = p.pr;
+    fg.pc = p.pc;
     fg.chain_len = chain_len;
     fg.out_ij = req.out_ij;
     fg.done_flag = req.done_flag;
     fg.done_value = req.done_value;
     fg.progress = req.progress ? 1 : 0;
     fg.rp = t->exact ? t->d_rp.get() : nullptr;
-    fg.ref_cbw = t->fused_ref_cbw;
-    fg.ref_rows = t->fused_ref_rows;
+    fg.ref_cbw = p.ref_cbw;
+    fg.ref_rows = p.ref_rows;
     fg.dc_host = req.dc_host;
     g.ex = exact_ctl(t, kFamFused);
-    const size_t lds = fused_total_lds(t);
+    const size_t lds = p.lds;
     fused_fn_t fn = (fused_fn_t)fused_instances(t).fused[req.out_resp ? kLatResp : kLatPlain];
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
 #ifdef PDOG_ABLATIONS
     if (req.out_resp && t->sw.fused_diag) { // phase stamps instead of the response (tools/fused_phases.py)
-        fn = (t->fused_c && t->L == 65) ? (fused_fn_t)dog_fused_kernel<true, 1, 65> : (fused_fn_t)dog_fused_kernel<true, 1>;
+        fn = (p.c && t->L == 65) ? (fused_fn_t)dog_fused_kernel<true, 1, 65> : (fused_fn_t)dog_fused_kernel<true, 1>;
         if (int rc = raise_lds_limit((const void *)fn, lds)) return rc;
     }
     if (!req.out_resp && t->sw.fused_diag && chain_len > 8) { // a chain's steady state: stamps of every frame, the median printed per phase
@@ -984,7 +1013,7 @@ int launch_fused(pdog_tracker *t, const Request &req)
         std::vector<float> st(16 * (size_t)chain_len + 64);
         if (int rc = d_st.reserve(st.size(), nullptr)) return rc;
         fg.g.resp = d_st.get();
-        fn = (t->fused_c && t->L == 65) ? (fused_fn_t)dog_fused_kernel<true, 1, 65> : (fused_fn_t)dog_fused_kernel<true, 1>;
+        fn = (p.c && t->L == 65) ? (fused_fn_t)dog_fused_kernel<true, 1, 65> : (fused_fn_t)dog_fused_kernel<true, 1>;
         if (int rc = raise_lds_limit((const void *)fn, lds)) return rc;
         hipLaunchKernelGGL(fn, dim3(n), dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
         HIP_TRY(hipStreamSynchronize(t->stream));
@@ -1010,13 +1039,13 @@ int launch_fused(pdog_tracker *t, const Request &req)
         return PDOG_OK;
     }
 #endif
-    if (t->fused_resident <= 0) { // once per tracker
+    if (p.resident <= 0) { // once per plan
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, FUSED_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus < 1) cus = 256;
-        t->fused_resident = per_cu * cus;
+        p.resident = per_cu * cus;
     }
-    const dim3 grid(std::min(n, t->fused_resident));
+    const dim3 grid(std::min(n, p.resident));
     if (req.table.index) hipLaunchKernelGGL((fused_table_fn_t)fused_instances(t).fused[kLatTable], grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
     else hipLaunchKernelGGL(fn, grid, dim3(FUSED_NT), lds, t->stream, static_cast<const FusedGeo &>(fg), tr, tc);
     HIP_TRY(hipGetLastError());
@@ -1122,35 +1151,14 @@ int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticke
     return launch_finish(t, g, fin);
 }
 
-// ---- pruning policy (dog_prune.hpp) ----
-// The pre-pass pays where it lets the strips skip more than it costs.  Measured on the flagship batch, kernel trace of
-// bench.py (profiles/prune_profile_this.txt, profiles/prune_profile_parent.txt): dog_prune_kernel takes 0.474 ms beside the
-// dense roll kernel's 1.314 ms, 36 % of it (kPrunePrePct), so a batch that keeps more than 64 % of its (slot, sub-chunk) pairs
-// (kPruneBreakEvenPct) is better off dense.  Noise-only windows and heavy texture are such batches (nothing can be excluded).
-// (Since the pre-pass forms its energies from raw-pixel moments it takes 0.331 ms, 25 % of the dense roll kernel:
-// profiles/prepass_profile_this.txt.  The constant has not followed yet: bench data at ±40 levels keeps 76 % of its pairs,
-// right at the share that ratio would give, and whether pruning pays there is unmeasured — profiles/prepass_ab.txt.)
-// The pre-pass publishes its cumulative kept / total counts through host-coherent memory, as the finishing kernel publishes
-// its flagged count; when the pairs counted since the last look kept more than the break-even share, the next
-// kPruneProbeEvery batches run dense, then one batch probes again.  Nothing here waits for the GPU.
-constexpr int kPrunePrePct = 36;
-constexpr int kPruneBreakEvenPct = 100 - kPrunePrePct;
-constexpr int kPruneProbeEvery = 64;
+// ---- pruning policy (dog_prune.hpp; PrunePolicy, pdog_policy.hpp) ----
 constexpr size_t kPruneMaxLds = 64 * 1024; // (the pre-pass's dynamic LDS without raising the kernel's limit; larger windows stay dense)
 bool use_pruning(pdog_tracker *t, const Variant &v, bool want_resp, int nslots)
 {
     // dense: the response-writing instances, pdog_set_exact(t, 2) (infinite thresholds), "no_prune", every other kernel family
+    // (ahead of the policy: a launch that cannot prune is no observation)
     if (!v.roll || !v.fn_prune || want_resp || t->exact_all || t->sw.no_prune || prune_lds(t->n1, t->n2, t->L, nslots).total > kPruneMaxLds) return false;
-    const unsigned long long pub = __atomic_load_n(reinterpret_cast<const unsigned long long *>(t->h_pinned.get() + 8), __ATOMIC_ACQUIRE);
-    const unsigned kept = (unsigned)pub, total = (unsigned)(pub >> 32); // (low halves of cumulative counts: differences wrap correctly)
-    const long long dk = (long long)(unsigned)(kept - t->prune_kept_last), dt = (long long)(unsigned)(total - t->prune_total_last);
-    if (dt > 0) {
-        t->prune_kept_last = kept;
-        t->prune_total_last = total;
-        t->prune_sleep = dk * 100 > dt * kPruneBreakEvenPct ? kPruneProbeEvery : 0;
-    }
-    if (t->prune_sleep > 0) { --t->prune_sleep; return false; }
-    return true;
+    return t->prune_policy.decide(__atomic_load_n(&t->h_pinned.get()->prune_pub, __ATOMIC_ACQUIRE));
 }
 
 // The tracker's batch kernel: one wave (roll) or workgroup (ring) per strip of every window, the thin remainder columns beside
@@ -1160,24 +1168,14 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     const Variant &v = *t->var;
     const int n = req.n;
     const int grid = round_up(g.nblocks, 8);
-    // Exact mode: a batch whose predecessors flagged more than 8 % of their windows writes its responses (the kernels'
-    // RESP instances: +15 % on the strips) and the finishing kernel reads the candidates off that map instead of recomputing
-    // them per window; back to the plain instances after eight observations below 2 %.  The finishing kernels publish the
-    // flagged count TOGETHER with the number of windows it came from, through host-coherent memory: nothing here waits for
-    // the GPU, and the rate is right however many batches are in flight (round 2 compared the count's increase with ONE
-    // batch's size: with three batches in flight 0.9 % looked like 2.7 % and one step in four paid for a map it did not need).
+    // Exact mode: batches whose predecessors flagged many of their windows write their responses, and the finishing kernel
+    // reads its candidates off that map (MapPolicy, pdog_policy.hpp).  The counts come through host-coherent memory: nothing
+    // here waits for the GPU.
     if (t->exact && !t->exact_all) {
-        const unsigned cur = (unsigned)__atomic_load_n(&t->h_pinned.get()[6], __ATOMIC_ACQUIRE); // (the low 32 bits of a cumulative count: differences wrap correctly)
-        const unsigned curw = (unsigned)__atomic_load_n(&t->h_pinned.get()[7], __ATOMIC_ACQUIRE);
-        const long long delta = (long long)(unsigned)(cur - t->flag_last), dwin = (long long)(unsigned)(curw - t->win_last);
-        if (dwin > 0) {
-            t->flag_last = cur;
-            t->win_last = curw;
-            if (delta * 12 > dwin) { t->roll_map = true; t->flag_calm = 0; }
-            else if (delta * 50 < dwin) { if (++t->flag_calm >= 8) t->roll_map = false; }
-            else t->flag_calm = 0;
-        }
-        if (!g.resp && t->roll_map && !t->sw.no_roll_map)
+        const KernelWords &kw = t->h_pinned.get()->kernel;
+        const uint32_t flagged = __atomic_load_n(&kw.flagged, __ATOMIC_ACQUIRE);
+        t->map_policy.observe(flagged, __atomic_load_n(&kw.finished, __ATOMIC_ACQUIRE));
+        if (!g.resp && t->map_policy.on() && !t->sw.no_roll_map)
             if (int rc = reserve_response_map(t, g)) return rc;
     }
     const bool want_resp = g.resp != nullptr;
@@ -1202,7 +1200,7 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         pg.tmax = std::max(g.ex.T, g.ex.T_rescan);
         pg.darker = t->darker;
         pg.stat = t->d_prune_stat.get();
-        pg.host = reinterpret_cast<unsigned long long *>(t->h_pinned.device() + 8);
+        pg.host = &t->h_pinned.device()->prune_pub;
         hipLaunchKernelGGL(dog_prune_kernel, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
         HIP_TRY(hipGetLastError());
         g.prune = 1;
@@ -1378,8 +1376,7 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
     t->fill = fill;                                // :47
     if ((long long)t->n1 * t->n2 > 0x3fffffffLL) return fail(PDOG_E_ARG, "pdog_create: window too large");
 
-    setup_refine_geometry(t);
-    if (int rc = choose_variant(t, -1)) return rc;
+    if (int rc = make_plan(t, -1)) return rc;
 
     // taps: Float64 on the host, one rounding to f32
     std::vector<double> gp(t->L), gm(t->L);
@@ -1418,7 +1415,7 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
         if (int rc = upload(t->d_taps_roll, tab)) return rc;
     }
     if (int rc = t->d_small.reserve(4, nullptr)) return rc;
-    if (int rc = t->h_pinned.reserve(10, nullptr, true)) return rc;
+    if (int rc = t->h_pinned.reserve(1, nullptr, true)) return rc;
     {
         // exact mode (dog_exact.hpp): the reference's dense kernel in Float64, built exactly as :41-43 builds it
         // (K = dir·(g₊⊗g₊ − g₋⊗g₋), column-major), and the decision threshold T = 2δ, δ = u·(6l + 4) for |pixel − dc| ≤ 255
@@ -1535,7 +1532,7 @@ int pdog_set_variant(pdog_tracker *t, int variant)
     if (!t) return fail(PDOG_E_ARG, "pdog_set_variant: null tracker");
     if (variant >= 0 && !find_variant(variant)) return fail(PDOG_E_ARG, "pdog_set_variant: unknown variant id");
     HIP_TRY(hipSetDevice(t->device));
-    return choose_variant(t, variant);
+    return make_plan(t, variant);
 }
 
 // Drain the tracker's stream and report what its kernels raised while they ran: every entry point that waits for the
@@ -1544,10 +1541,10 @@ static int drain_and_check(pdog_tracker *t, const char *who)
 {
     HIP_TRY(hipSetDevice(t->device)); // (group mode: the current device is whichever rank was touched last)
     HIP_TRY(hipStreamSynchronize(t->stream));
-    if (const int32_t raised = __atomic_load_n(&t->h_pinned.get()[5], __ATOMIC_ACQUIRE)) { // raised by a kernel
-        __atomic_store_n(&t->h_pinned.get()[5], 0, __ATOMIC_RELEASE);
+    if (const int32_t raised = __atomic_load_n(&t->h_pinned.get()->kernel.raised, __ATOMIC_ACQUIRE)) { // raised by a kernel
+        __atomic_store_n(&t->h_pinned.get()->kernel.raised, 0, __ATOMIC_RELEASE);
         if (raised == 2) { // a wait between resident workgroups gave up (wait_counter): the positions of that work are not valid
-            if (t->d_tiled_ctl.get()) (void)hipMemset(t->d_tiled_ctl.get(), 0, sizeof(int) * t->d_tiled_ctl.capacity()); // counters, flags and the abort word
+            if (t->tiled_run.d_ctl.get()) (void)hipMemset(t->tiled_run.d_ctl.get(), 0, sizeof(int) * t->tiled_run.d_ctl.capacity()); // counters, flags and the abort word
             return fail(PDOG_E_HIP, std::string(who) + ": a kernel gave up waiting for its other workgroups (device-side watchdog); the results of the work just finished are not valid");
         }
         // a device-resident guess was out of range
@@ -1592,16 +1589,9 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h
-    else if (k == "no_fused_c") {
-        t->sw.no_fused_c = on;
-        t->fused_resident = 0;
-        setup_refine_geometry(t); // the tile layout, and with it the refinement's share of the kernel's LDS
-        if (t->fused_ok)
-            if (int rc = raise_lds_limits(fused_instances(t).fused, fused_total_lds(t))) return rc;
-        if (int rc = setup_tiled(t)) return rc;
-    } else if (k == "no_tiled") {
-        t->sw.no_tiled = on;
-        if (int rc = setup_tiled(t)) return rc; // the tiled kernel's geometry is decided per tracker
+    else if (k == "no_fused_c" || k == "no_tiled") { // inputs of the plan: the latency kernels' instances and tile layouts
+        (k == "no_tiled" ? t->sw.no_tiled : t->sw.no_fused_c) = on;
+        return make_plan(t, t->forced_variant ? t->var->id : -1);
     } else return fail(PDOG_E_ARG, "pdog_set_tuning: unknown key '" + k + "'");
     return PDOG_OK;
 }
@@ -1750,13 +1740,13 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         // queued next.  With a response copy, a pinned batch kernel that publishes no ticket, or a ticket that does
         // not show up in time (a failed launch), the stream is synchronised as usual.
         if (int rc = t->h_tile.reserve(tile.bytes(), nullptr)) return rc;
-        int32_t *mail = t->h_pinned.get(), *d_mail = t->h_pinned.device();
+        Mailbox *mail = t->h_pinned.get(), *d_mail = t->h_pinned.device();
         const bool trace = t->sw.host_trace; // diagnostic: where a call's wall time goes
         const auto t0 = std::chrono::steady_clock::now();
         // cached stores: the functor's kernel reads this tile in place right away (non-temporal stores measured equal here)
         pack_tile_geo(h_frame, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2, guess[0], guess[1], t->h_tile.get(), tile.pitch, false);
-        mail[0] = tile.centre[0];   // the guess is the tile's centre
-        mail[1] = tile.centre[1];
+        mail->guess[0] = tile.centre[0];   // the guess is the tile's centre
+        mail->guess[1] = tile.centre[1];
         const auto t1 = std::chrono::steady_clock::now();
         if (int rc = ensure_capacity(t, 1)) return rc;
         const int32_t ticket = t->ticket = t->ticket % 0x7fffffff + 1;   // 1 … 2^31 − 1, never the mailbox's initial 0
@@ -1773,10 +1763,10 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         }
         Request req;
         req.frames = t->h_tile.device(); req.frame_stride = (int64_t)tile.bytes(); req.row_stride = tile.pitch;
-        req.guesses = d_mail; req.n = 1;
-        req.out_ij = d_mail + 2; req.out_resp = h_resp ? t->d_resp.get() : nullptr;
+        req.guesses = d_mail->guess; req.n = 1;
+        req.out_ij = d_mail->result; req.out_resp = h_resp ? t->d_resp.get() : nullptr;
         req.fh = tile.th; req.fw = tile.tw;
-        req.done_flag = d_mail + 4; req.done_value = ticket;
+        req.done_flag = &d_mail->ticket; req.done_value = ticket;
         req.dc_host = t->sw.no_host_dc ? -1 : dc_host;
         if (int rc = launch_detect(t, req, &armed)) return rc;
         if (h_resp) HIP_TRY(hipMemcpyAsync(h_resp, t->d_resp.get(), sizeof(float) * (size_t)t->n1 * t->n2, hipMemcpyDeviceToHost, t->stream));
@@ -1785,7 +1775,7 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
         if (armed && !h_resp && !t->sw.host_sync) {
             const auto deadline = t2 + std::chrono::microseconds(500);
             for (int spin = 0;; ++spin) {
-                if (__atomic_load_n(&mail[4], __ATOMIC_ACQUIRE) == ticket) { done = true; break; }
+                if (__atomic_load_n(&mail->ticket, __ATOMIC_ACQUIRE) == ticket) { done = true; break; }
                 if ((spin & 63) == 63 && std::chrono::steady_clock::now() > deadline) break;
                 __builtin_ia32_pause();
             }
@@ -1796,12 +1786,13 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
             auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
             std::fprintf(stderr, "pdog functor: pack %.1f us, launch %.1f us, sync %.1f us\n", us(t0, t1), us(t1, t2), us(t2, t3));
         }
-        tile.to_frame(t, guess, mail + 2, out_ij);
+        tile.to_frame(t, guess, mail->result, out_ij);
         return PDOG_OK;
     }
     if (int rc = t->d_frame.reserve((size_t)t->fh * t->fw, nullptr)) return rc;
     if (int rc = ensure_capacity(t, 1)) return rc;
-    int32_t *mail = t->h_pinned.get(), *d_small = t->d_small.get();
+    Mailbox *mail = t->h_pinned.get();
+    int32_t *d_small = t->d_small.get();
     {
         // Only the window's padded tile is read by the kernels (anything else they touch feeds masked
         // lanes), so only that rectangle of the frame crosses PCIe: 109×109 B instead of 2 MB for the
@@ -1812,19 +1803,19 @@ int pdog_detect_host(pdog_tracker *t, const uint8_t *h_frame, int64_t row_stride
             HIP_TRY(hipMemcpy2DAsync(t->d_frame.get() + (size_t)r_lo * t->fw + c_lo, t->fw, h_frame + (size_t)r_lo * row_stride + c_lo,
                                      row_stride, (size_t)(c_hi - c_lo), (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, t->stream));
     }
-    mail[0] = guess[0];
-    mail[1] = guess[1];
-    HIP_TRY(hipMemcpyAsync(d_small, mail, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
+    mail->guess[0] = guess[0];
+    mail->guess[1] = guess[1];
+    HIP_TRY(hipMemcpyAsync(d_small, mail->guess, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
     Request req;
     req.frames = t->d_frame.get(); req.frame_stride = (int64_t)t->fh * t->fw; req.row_stride = t->fw;
     req.guesses = d_small; req.n = 1;
     req.out_ij = d_small + 2; req.out_resp = h_resp ? t->d_resp.get() : nullptr;
     if (int rc = launch_detect(t, req)) return rc;
-    HIP_TRY(hipMemcpyAsync(mail + 2, d_small + 2, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(mail->result, d_small + 2, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, t->stream));
     if (h_resp) HIP_TRY(hipMemcpyAsync(h_resp, t->d_resp.get(), sizeof(float) * (size_t)t->n1 * t->n2, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
-    out_ij[0] = mail[2];
-    out_ij[1] = mail[3];
+    out_ij[0] = mail->result[0];
+    out_ij[1] = mail->result[1];
     return PDOG_OK;
 }
 
@@ -1870,29 +1861,30 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
     int chunk = (int)std::max<size_t>(64, ((size_t)32 << 20) / tile_bytes);
     if (t->sw.ingest_chunk) chunk = t->sw.ingest_chunk;
     chunk = std::min(chunk, n);
-    constexpr int NS = pdog_tracker::kIngestSlots;
-    if (!t->h2d_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t->h2d_stream, hipStreamNonBlocking));
+    constexpr int NS = Ingest::kSlots;
+    Ingest &in = t->ingest;
+    if (!in.stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&in.stream, hipStreamNonBlocking));
         for (int k = 0; k < NS; ++k) {
-            HIP_TRY(hipEventCreateWithFlags(&t->ev_h2d[k], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&t->ev_used[k], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&in.ev_h2d[k], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&in.ev_used[k], hipEventDisableTiming));
         }
     }
     const size_t slot_bytes = tile_bytes * chunk;
     for (int k = 0; k < NS; ++k) {
-        if (std::min(t->h_stage[k].capacity(), t->d_tiles[k].capacity()) < slot_bytes)
-            HIP_TRY(hipStreamSynchronize(t->h2d_stream)); // copies queued into the old slot (reserve drains the tracker's stream)
-        if (int rc = t->h_stage[k].reserve(slot_bytes, &t->stream)) return rc;
-        if (int rc = t->d_tiles[k].reserve(slot_bytes, &t->stream)) return rc;
+        if (std::min(in.h_stage[k].capacity(), in.d_tiles[k].capacity()) < slot_bytes)
+            HIP_TRY(hipStreamSynchronize(in.stream)); // copies queued into the old slot (reserve drains the tracker's stream)
+        if (int rc = in.h_stage[k].reserve(slot_bytes, &t->stream)) return rc;
+        if (int rc = in.d_tiles[k].reserve(slot_bytes, &t->stream)) return rc;
     }
-    if (t->d_ingest_guess.capacity() < 2 * (size_t)chunk) { // every tile's guess is its centre
-        if (int rc = t->d_ingest_guess.reserve(2 * (size_t)chunk, &t->stream)) return rc;
+    if (in.d_guess.capacity() < 2 * (size_t)chunk) { // every tile's guess is its centre
+        if (int rc = in.d_guess.reserve(2 * (size_t)chunk, &t->stream)) return rc;
         std::vector<int32_t> centre(2 * (size_t)chunk);
         for (int b = 0; b < chunk; ++b) { centre[2 * b] = tile.centre[0]; centre[2 * b + 1] = tile.centre[1]; }
-        HIP_TRY(hipMemcpy(t->d_ingest_guess.get(), centre.data(), sizeof(int32_t) * centre.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(in.d_guess.get(), centre.data(), sizeof(int32_t) * centre.size(), hipMemcpyHostToDevice));
     }
-    if (int rc = t->d_ingest_out.reserve(2 * (size_t)n, &t->stream)) return rc;
-    if (int rc = t->h_ingest_out.reserve(2 * (size_t)n, &t->stream)) return rc;
+    if (int rc = in.d_out.reserve(2 * (size_t)n, &t->stream)) return rc;
+    if (int rc = in.h_out.reserve(2 * (size_t)n, &t->stream)) return rc;
     if (int rc = ensure_capacity(t, chunk)) return rc;
 
     const int nchunks = (n + chunk - 1) / chunk;
@@ -1912,13 +1904,13 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
                     if (failed.load()) return;
                     std::this_thread::yield();
                 }
-                if (hipEventSynchronize(t->ev_h2d[c % NS]) != hipSuccess) { failed.store(1); return; }
+                if (hipEventSynchronize(in.ev_h2d[c % NS]) != hipSuccess) { failed.store(1); return; }
                 waited_for = c;
             }
             const int f = h_frame_index ? h_frame_index[b] : b;
             const bool nt_stores = !t->sw.ingest_no_nt;
             pack_tile_geo(h_frames + (int64_t)f * frame_stride, t->fh, t->fw, row_stride, t->fill, t->L, t->r1, t->r2,
-                          h_guesses[2 * b], h_guesses[2 * b + 1], t->h_stage[c % NS].get() + (size_t)(b - c * chunk) * tile_bytes, tile.pitch, nt_stores);
+                          h_guesses[2 * b], h_guesses[2 * b + 1], in.h_stage[c % NS].get() + (size_t)(b - c * chunk) * tile_bytes, tile.pitch, nt_stores);
             packed[c].fetch_add(1, std::memory_order_release);
         }
     };
@@ -1936,26 +1928,26 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
         wait_pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
         if (failed.load()) { rc = fail(PDOG_E_HIP, "pdog_detect_batch_host: event wait failed in a packing thread"); break; }
         hipError_t e = hipSuccess;
-        if (c >= NS) e = hipStreamWaitEvent(t->h2d_stream, t->ev_used[slot], 0); // kernels of chunk c - NS are done with the device slot
-        if (e == hipSuccess) e = hipMemcpyAsync(t->d_tiles[slot].get(), t->h_stage[slot].get(), tile_bytes * nw, hipMemcpyHostToDevice, t->h2d_stream);
-        if (e == hipSuccess) e = hipEventRecord(t->ev_h2d[slot], t->h2d_stream);
+        if (c >= NS) e = hipStreamWaitEvent(in.stream, in.ev_used[slot], 0); // kernels of chunk c - NS are done with the device slot
+        if (e == hipSuccess) e = hipMemcpyAsync(in.d_tiles[slot].get(), in.h_stage[slot].get(), tile_bytes * nw, hipMemcpyHostToDevice, in.stream);
+        if (e == hipSuccess) e = hipEventRecord(in.ev_h2d[slot], in.stream);
         submitted.store(c + 1, std::memory_order_release);
-        if (e == hipSuccess) e = hipStreamWaitEvent(t->stream, t->ev_h2d[slot], 0);
+        if (e == hipSuccess) e = hipStreamWaitEvent(t->stream, in.ev_h2d[slot], 0);
         if (e != hipSuccess) { rc = fail(PDOG_E_HIP, std::string("pdog_detect_batch_host: ") + hipGetErrorString(e)); break; }
         Request req;
-        req.frames = t->d_tiles[slot].get(); req.frame_stride = (int64_t)tile_bytes; req.row_stride = tile.pitch;
-        req.guesses = t->d_ingest_guess.get(); req.n = nw;
-        req.out_ij = t->d_ingest_out.get() + 2 * (size_t)w0;
+        req.frames = in.d_tiles[slot].get(); req.frame_stride = (int64_t)tile_bytes; req.row_stride = tile.pitch;
+        req.guesses = in.d_guess.get(); req.n = nw;
+        req.out_ij = in.d_out.get() + 2 * (size_t)w0;
         req.fh = tile.th; req.fw = tile.tw;
         rc = launch_detect(t, req);
-        if (rc == PDOG_OK && hipEventRecord(t->ev_used[slot], t->stream) != hipSuccess)
+        if (rc == PDOG_OK && hipEventRecord(in.ev_used[slot], t->stream) != hipSuccess)
             rc = fail(PDOG_E_HIP, "pdog_detect_batch_host: hipEventRecord failed");
     }
     if (rc != PDOG_OK) { failed.store(1); submitted.store(nchunks + NS); }
     for (auto &th_ : pool) th_.join();
-    if (rc != PDOG_OK) { (void)hipStreamSynchronize(t->h2d_stream); (void)hipStreamSynchronize(t->stream); return rc; }
+    if (rc != PDOG_OK) { (void)hipStreamSynchronize(in.stream); (void)hipStreamSynchronize(t->stream); return rc; }
     const auto t_submitted = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(t->h_ingest_out.get(), t->d_ingest_out.get(), sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(in.h_out.get(), in.d_out.get(), sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     if (trace) {
         const auto t_end = std::chrono::steady_clock::now();
@@ -1963,7 +1955,7 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
                      n, nchunks, chunk, nthreads, std::chrono::duration<double, std::milli>(t_submitted - t_begin).count(), wait_pack_ms,
                      std::chrono::duration<double, std::milli>(t_end - t_submitted).count());
     }
-    for (int b = 0; b < n; ++b) tile.to_frame(t, h_guesses + 2 * b, t->h_ingest_out.get() + 2 * b, h_out_ij + 2 * b);
+    for (int b = 0; b < n; ++b) tile.to_frame(t, h_guesses + 2 * b, in.h_out.get() + 2 * b, h_out_ij + 2 * b);
     return PDOG_OK;
 }
 
@@ -2042,10 +2034,10 @@ ChainPath chain_path(const pdog_tracker *t, int n_clips, int n_steps, bool table
     // (round 3: the fused kernel's compile-time-l instances walk 256 … 4096 clips of 45×45 windows at 27–30 M frames/s, the persistent
     // roll chain 19–28 M; at 63×63 the chain wins from ≈1400 clips: 23.5 against 18.0 M frames/s at 2048)
     const long long strip_waves = (long long)n_clips * chain_strips(t);
-    const bool fused_wins = t->fused_ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || strip_waves < 1400);
+    const bool fused_wins = t->fused.ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || strip_waves < 1400);
     const bool persistent = !progress && v.roll && v.chain && chain_strips(t) <= 8 && !fused_wins && // (the chain kernel publishes no progress)
                             (t->forced_variant || !t->small_twopass || strip_waves >= 1000);
-    if (v.fused || (!persistent && !t->forced_variant && t->fused_ok)) return ChainPath::Fused; // one launch: a workgroup per clip loops over its frames
+    if (v.fused || (!persistent && !t->forced_variant && t->fused.ok)) return ChainPath::Fused; // one launch: a workgroup per clip loops over its frames
     if (persistent) return ChainPath::Persistent;
     // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that
     // allows); with progress its combining workgroup publishes k + 1 after every frame

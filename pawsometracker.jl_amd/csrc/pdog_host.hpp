@@ -1,6 +1,9 @@
 // pdog_host.hpp — what the host side of the C ABI shares between its translation units (pawsome_dog.hip,
 // pawsome_group.hip, pawsome_diag.hip, pdog_math.cpp): the thread's error text, the reference's Float64 host arithmetic
 // (pdog_math.cpp, plain C++) and, for the units that hipcc compiles, the HIP-error macro and the owning buffer type.
+// Two more headers are plain C++ and carry no HIP either: pdog_mailbox.hpp, the layout of the tracker's host-coherent mailbox,
+// which the kernel headers and pawsome_dog.hip both include, and pdog_policy.hpp, the two adaptive policies of the roll batch
+// path, which pawsome_dog.hip includes alone; the host compiler tests both (tests/policy_main.cpp).
 //
 // WHERE KERNELS LIVE.  The kernels of the tracker (dog_*.hpp) are templates or `static __global__` functions in headers, and
 // raise_lds_limit is keyed on a kernel's address: a second translation unit that included one of those headers would get
