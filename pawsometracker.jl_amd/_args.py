@@ -77,6 +77,20 @@ def peaks_args(k, min_distance, name="k"):
     return int(k), int(min_distance)
 
 
+def exclusive_args(n_targets, k, min_distance, min_ratio):
+    """What the exclusive step takes beside its arrays: targets per group 1 ... 32 (PDOG_EXCLUSIVE_MAX_TARGETS), k and
+    min_distance as peaks_args judges them — k None: the library's default, min(32, 2 * n_targets), passed on as 0 —, and the
+    ratio, a real number in [0, 1].  Returns (k, min_distance, min_ratio) as the library takes them."""
+    if not 1 <= n_targets <= 32:
+        raise ValueError(f"n_targets: {n_targets} lies outside 1 ... 32")
+    k, md = (0, peaks_args(1, min_distance)[1]) if k is None else peaks_args(k, min_distance)
+    if isinstance(min_ratio, bool) or not isinstance(min_ratio, (int, float, np.integer, np.floating)):
+        raise TypeError(f"min_ratio must be a real number, not {type(min_ratio).__name__}")
+    if not 0.0 <= float(min_ratio) <= 1.0:          # (a NaN fails both comparisons)
+        raise ValueError(f"min_ratio: {min_ratio} lies outside [0, 1]")
+    return k, md, float(min_ratio)
+
+
 def host_table(v, name):
     """A frame table — a sequence of rows, a numpy array or a tensor of integers [n_clips, n_steps] — as a contiguous host int32
     array.  Its entries are the library's to judge (it validates them before it launches anything)."""

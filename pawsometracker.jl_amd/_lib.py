@@ -125,6 +125,17 @@ PEAKS_PROTOTYPES = {
 }
 PEAKS_SYMBOLS = tuple(PEAKS_PROTOTYPES)
 PEAKS_MAX_K = 32             # PDOG_PEAKS_MAX_K
+
+# the same for include/pawsome_exclusive.h, which includes pawsome_peaks.h: several targets of one video kept apart
+# (tests/test_exclusive_cpu.py holds this table against that header)
+EXCLUSIVE_PROTOTYPES = {
+    "pdog_assign_exclusive": (_i, [_p, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p]),
+    "pdog_assign_exclusive_host": (_i, [_i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p]),
+    "pdog_detect_chains_exclusive": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p]),
+    "pdog_get_exclusive_counts": (_i, [_p, _pu64]),
+}
+EXCLUSIVE_SYMBOLS = tuple(EXCLUSIVE_PROTOTYPES)
+EXCLUSIVE_MAX_TARGETS = 32   # PDOG_EXCLUSIVE_MAX_TARGETS
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -169,7 +180,8 @@ def lib():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
+                                      **EXCLUSIVE_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -256,6 +268,12 @@ class TrackerHandle(Handle):
         """(windows detect_peaks served, those among them whose candidate list overflowed) — pdog_get_peaks_counts."""
         out = (C.c_uint64 * 2)()
         check(lib().pdog_get_peaks_counts(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def exclusive_counts(self):
+        """(joint steps enqueued, times a workspace of the exclusive calls grew) — pdog_get_exclusive_counts."""
+        out = (C.c_uint64 * 2)()
+        check(lib().pdog_get_exclusive_counts(self._h, out))
         return int(out[0]), int(out[1])
 
     def batch_maxima(self, n):

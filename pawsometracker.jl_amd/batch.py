@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, frame_index_ptr, host_i32, host_table, peaks_args
+from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, peaks_args
 
 
 class BatchTracker(_lib.TrackerHandle):
@@ -165,6 +165,61 @@ class BatchTracker(_lib.TrackerHandle):
             self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
             C.c_void_p(table.ctypes.data), ns, nc, int(first), C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
+
+    def assign_exclusive(self, prev, ij, peak, count, min_distance=None, min_ratio=0.5):
+        """The exclusive step alone (pdog_assign_exclusive; this library's addition, the rule is stated in
+        include/pawsome_exclusive.h): per group the targets share out the peaks of their windows so that no two take the same
+        blob.  prev int32 cuda [n_groups, n_targets, 2], the positions the windows were centred on; ij int32 cuda
+        [n_groups, n_targets, k, 2], peak float32 cuda [n_groups, n_targets, k] and count int32 cuda [n_groups, n_targets]:
+        what detect_peaks returned for the n_groups * n_targets windows, reshaped.  Returns (positions int32 cuda
+        [n_groups, n_targets, 2], state int32 cuda [n_groups, n_targets]): state is the number of the pick a target was
+        assigned, 1 ... k, or -1 where it found no blob of its own and is held at prev."""
+        import torch
+        self.use_torch_stream()
+        if not isinstance(prev, torch.Tensor) or prev.dim() != 3 or not isinstance(ij, torch.Tensor) or ij.dim() != 4:
+            raise TypeError("prev must be an int32 cuda tensor [n_groups, n_targets, 2], ij one [n_groups, n_targets, k, 2]")
+        ng, nt, k = int(ij.shape[0]), int(ij.shape[1]), int(ij.shape[2])
+        if ng < 1:
+            raise ValueError("ij: no group")
+        k, md, rho = exclusive_args(nt, k, min_distance, min_ratio)
+        device_array(prev, "prev", torch.int32, (ng, nt, 2))
+        device_array(ij, "ij", torch.int32, (ng, nt, k, 2))
+        device_array(peak, "peak", torch.float32, (ng, nt, k))
+        device_array(count, "count", torch.int32, (ng, nt))
+        out = torch.empty((ng, nt, 2), dtype=torch.int32, device=ij.device)
+        state = torch.empty((ng, nt), dtype=torch.int32, device=ij.device)
+        _lib.check(_lib.lib().pdog_assign_exclusive(
+            self._h, ng, nt, k, md, rho, C.c_void_p(prev.data_ptr()), C.c_void_p(ij.data_ptr()), C.c_void_p(peak.data_ptr()),
+            C.c_void_p(count.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr())))
+        return out, state
+
+    def detect_chains_exclusive(self, frames, frame_table, starts, k=None, min_distance=None, min_ratio=0.5, first=0):
+        """The exclusive walk over a frame table (pdog_detect_chains_exclusive): frames uint8 cuda [n_frames, h, w] is one stack;
+        frame_table [n_groups, n_steps], host side, names each step's frame for a GROUP — the targets of one video, which
+        share its row — as for detect_chains_indexed; starts int32 cuda [n_groups, n_targets, 2].  Per step every target's
+        window yields its k best peaks (k None: min(32, 2 * n_targets); min_distance None: ceil(target_width)) and the
+        group's targets share them out as assign_exclusive states; first as for detect_chains_indexed (first = 1 files the
+        starts as given, with state 0).  Returns (indices int32 cuda [n_groups, n_targets, n_steps, 2], state int32 cuda
+        [n_groups, n_targets, n_steps]); steps at and beyond a group's end are not written (both are zeroed)."""
+        import torch
+        self.use_torch_stream()
+        device_frames(frames, "frames", 3, self._hw)
+        table = host_table(frame_table, "frame_table")
+        ng, ns = table.shape
+        if not isinstance(starts, torch.Tensor) or starts.dim() != 3:
+            raise TypeError("starts must be an int32 cuda tensor [n_groups, n_targets, 2]")
+        nt = int(starts.shape[1])
+        k, md, rho = exclusive_args(nt, k, min_distance, min_ratio)
+        if isinstance(first, bool) or first not in (0, 1):
+            raise ValueError(f"first: {first!r} is neither 0 nor 1")
+        device_array(starts, "starts", torch.int32, (ng, nt, 2))
+        out = torch.zeros((ng, nt, ns, 2), dtype=torch.int32, device=frames.device)
+        state = torch.zeros((ng, nt, ns), dtype=torch.int32, device=frames.device)
+        _lib.check(_lib.lib().pdog_detect_chains_exclusive(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
+            C.c_void_p(table.ctypes.data), ns, ng, nt, int(first), k, md, rho, C.c_void_p(starts.data_ptr()),
+            C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr())))
+        return out, state
 
     def measure(self, frames, ij, frame_index=None, want_resp=False):
         """Sub-pixel positions (and peak responses) at tracked points (pdog_measure).  frames: uint8 cuda tensor

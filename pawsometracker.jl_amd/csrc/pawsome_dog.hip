@@ -364,6 +364,7 @@ struct pdog_tracker {
     PinnedBuffer<uint8_t> h_tile{hipHostMallocMapped}; // the functor's window tile when the kernels read it in place
     Ingest ingest;
     pdog::PeaksState peaks; // pdog_detect_peaks (pawsome_peaks.hip): its scratch, switch and counters
+    pdog::ExclusiveState exclusive; // the exclusive step and walk (pawsome_exclusive.hip): their scratch and counters
 
     // Drains and destroys the streams and events; the buffers free themselves after that.
     ~pdog_tracker()
@@ -386,6 +387,12 @@ pdog::PeaksState *pdog::peaks_state(pdog_tracker *t)
     t->peaks.device = t->device;
     t->peaks.map_cap = t->sw.map_cap;
     return &t->peaks;
+}
+
+pdog::ExclusiveState *pdog::exclusive_state(pdog_tracker *t)
+{
+    t->exclusive.device = t->device;
+    return &t->exclusive;
 }
 
 namespace {

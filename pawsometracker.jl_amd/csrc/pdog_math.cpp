@@ -2,6 +2,8 @@
 // reference's Float64 kernel arithmetic (src/PawsomeTracker.jl:30, :41-43), mode(_img) (:47) and the window
 // tile packer.  Plain C++: no HIP, no kernel header (pdog_host.hpp says why), so tools/asan_host.sh sanitises it alone.
 #include "pdog_host.hpp"
+#include "pdog_exclusive.hpp"
+#include "../../include/pawsome_exclusive.h"
 
 #include <algorithm>
 #include <cmath>
@@ -18,6 +20,16 @@ int fail(int code, const std::string &msg)
 {
     g_err = msg;
     return code;
+}
+
+// What the exclusive step's three entry points refuse alike (include/pawsome_exclusive.h); PDOG_E_ARG in `who`'s name.
+int check_exclusive(const char *who, int n_groups, int n_targets, int k, double min_ratio)
+{
+    if (n_groups < 1 || (long long)n_groups * n_targets > 0x7fffffffLL) return fail(PDOG_E_ARG, std::string(who) + ": bad number of groups");
+    if (n_targets < 1 || n_targets > exclusive::kMaxTargets) return fail(PDOG_E_ARG, std::string(who) + ": n_targets = " + std::to_string(n_targets) + " lies outside 1 ... 32");
+    if (k < 1 || k > PDOG_PEAKS_MAX_K) return fail(PDOG_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " lies outside 1 ... 32");
+    if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) return fail(PDOG_E_ARG, std::string(who) + ": min_ratio lies outside [0, 1]");
+    return PDOG_OK;
 }
 
 double sigma_of(double tw) { return tw / (2.0 * std::sqrt(2.0 * std::log(2.0))); } // :30
@@ -307,6 +319,56 @@ int pdog_fps_table(double rate, int n_frames, double start, double stop, double 
         }
     }
     *out_n = count;
+    return PDOG_OK;
+}
+
+// ---- the exclusive step on the host (include/pawsome_exclusive.h): the rule round by round, as the header states it ----
+int pdog_assign_exclusive_host(int n_groups, int n_targets, int k, int min_distance, double min_ratio, const int32_t *prev,
+                               const int32_t *ij, const float *peak, const int32_t *count, int32_t *out_ij, int32_t *out_state)
+{
+    using namespace pdog::exclusive;
+    if (!prev || !ij || !peak || !count || !out_ij || !out_state) return fail(PDOG_E_ARG, "pdog_assign_exclusive_host: null pointer");
+    if (int rc = check_exclusive("pdog_assign_exclusive_host", n_groups, n_targets, k, min_ratio)) return rc;
+    if (min_distance < 1) return fail(PDOG_E_ARG, "pdog_assign_exclusive_host: min_distance must be given (>= 1)");
+    const int T = n_targets;
+    const long long d = min_distance;
+    const float rho = (float)min_ratio;
+    for (int g = 0; g < n_groups; ++g) {
+        const size_t w0 = (size_t)g * T;
+        bool assigned[kMaxTargets] = {};
+        int32_t *oij = out_ij + 2 * w0, *ost = out_state + w0;
+        for (int t = 0; t < T; ++t) { // held until a round says otherwise
+            oij[2 * t] = prev[2 * (w0 + t)];
+            oij[2 * t + 1] = prev[2 * (w0 + t) + 1];
+            ost[t] = -1;
+        }
+        for (int round = 0; round < T; ++round) {
+            uint64_t best = 0;
+            int best_q = 0;
+            for (int t = 0; t < T; ++t) {
+                if (assigned[t]) continue;
+                const int32_t *pij = ij + 2 * (w0 + t) * k;
+                const float *pk = peak + (w0 + t) * k;
+                for (int q = 0; q < k; ++q) { // the head: the first entry that is admissible and not blocked
+                    if (!admissible(q, count[w0 + t], pk[q], pk[0], rho)) continue;
+                    bool blocked = false;
+                    for (int u = 0; u < T && !blocked; ++u)
+                        blocked = assigned[u] && blocks(pij[2 * q], pij[2 * q + 1], oij[2 * u], oij[2 * u + 1], d);
+                    if (blocked) continue;
+                    const uint64_t key = head_key(pk[q], t);
+                    if (key > best) { best = key; best_q = q; }
+                    break;
+                }
+            }
+            if (!best) break;
+            const int t = key_target(best);
+            const int32_t *pij = ij + 2 * (w0 + t) * k;
+            assigned[t] = true;
+            oij[2 * t] = pij[2 * best_q];
+            oij[2 * t + 1] = pij[2 * best_q + 1];
+            ost[t] = best_q + 1;
+        }
+    }
     return PDOG_OK;
 }
 

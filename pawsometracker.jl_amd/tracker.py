@@ -378,7 +378,7 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None):
+                min_distance=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -401,9 +401,17 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     of the reference's bootstrap window — sz .÷ 4 around the frame centre on the first selected frame (:99-107) —, in pick
     order: target 0 starts where the reference's own bootstrap puts its one target.  ValueError when fewer than K picks
     have a positive response, or when n_targets comes with start_locations.  Everything after the starts is what a list of
-    K start locations gets."""
+    K start locations gets.
+    `exclusive` = True keeps the targets apart (this library's addition; include/pawsome_exclusive.h states the rule): the
+    loop from the second selected frame on is BatchTracker.detect_chains_exclusive over all targets as one group — per step
+    every target's window yields its best separated peaks and the targets share them out, so that no two take the same blob;
+    a target that finds none of its own waits where it is.  `min_ratio` (None: 0.5) is the least share of a window's best
+    response a second or later peak must reach to be taken, and `min_distance` (None: ceil(target_width)) the least distance
+    between two peaks; at most 32 targets.  The result then gains a trailing `state`, int32 cuda [n_targets, m]: 0 for the
+    bootstrap, the number of the pick a target was assigned (1: the functor's own answer), -1 where it was held.  Bootstrap,
+    subpixel, diagnostic and n_targets work on the positions as before.  ValueError for min_ratio without exclusive."""
     import torch
-    from ._args import peaks_args
+    from ._args import exclusive_args, peaks_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
     if n_targets is not None:
@@ -411,8 +419,15 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             raise ValueError("n_targets finds the targets itself: give it, or start_locations, not both")
         n_targets, md = peaks_args(n_targets, min_distance, "n_targets")
         start_locations = [None] * n_targets
-    elif min_distance is not None:
-        raise ValueError("min_distance belongs to n_targets")
+    elif min_distance is not None and not exclusive:
+        raise ValueError("min_distance belongs to n_targets and exclusive")
+    if not isinstance(exclusive, bool):
+        raise TypeError("exclusive must be True or False")
+    if min_ratio is not None and not exclusive:
+        raise ValueError("min_ratio belongs to exclusive")
+    if exclusive:
+        n_locs = len(start_locations) if isinstance(start_locations, list) else 1
+        excl = exclusive_args(max(n_locs, 1), None, min_distance, 0.5 if min_ratio is None else min_ratio)
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3):
         raise TypeError("frames must be a uint8 cuda tensor [n_frames, h, w]")
     n, h, w = (int(v) for v in frames.shape)
@@ -457,7 +472,13 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 finally:
                     bt4.close()
             # the loop from the second selected frame on, :161-167: every target over the same table
-            out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
+            state = None
+            if exclusive:
+                out, state = bt.detect_chains_exclusive(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None,
+                                                        excl[2], first=1)
+                out, state = out[0], state[0]
+            else:
+                out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
             sub = None
             if subpixel:
                 fi = torch.from_numpy(np.tile(table, nt)).to(dev)
@@ -468,6 +489,7 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 with Diagnose(darker_target, dev.index) as dia:
                     dia.set_targets(nt)
                     _render_steps(dia, frames, table, out, chunk, diagnostic)
-            return (ts, out, sub) if subpixel else (ts, out)
+            res = (ts, out, sub) if subpixel else (ts, out)
+            return res + (state,) if exclusive else res
         finally:
             bt.close()
