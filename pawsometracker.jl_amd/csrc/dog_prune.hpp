@@ -57,6 +57,7 @@ struct PruneGeo {
 
 constexpr int PRUNE_NT = 256;
 constexpr int PRUNE_B = 8; // the L pixels: PRUNE_B × PRUNE_B outputs
+constexpr int PRUNE_PHASES = 9; // phase stamps of the diagnostic build: stat[4 … 4 + PRUNE_PHASES), then the workgroups that stamped
 // The segment sums (S) are dead once the energies are formed and the L block's buffers (R, patch) live only after that: they
 // share one region.  The patch carries 8 bytes of slack: its row pass reads whole dwords, up to 3 bytes past a row's last pixel.
 struct PruneLds { size_t cell, E, segd, strd, S, R, patch, total; };
@@ -98,6 +99,12 @@ __host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots)
 //   * A dword that straddles a cut (strips shifted to ncols − 64, remainder columns) adds nothing to the segments in the main
 //     pass; the few such dwords are listed and a second, byte-masked pass adds them column by column.
 // (Tried: 80 SGPRs at most, for eight resident workgroups per CU instead of six at 106: 35 SGPR spills, the kernel no faster.)
+// REGISTERS.  The next cell's loads in flight cost sixteen VGPRs: 79, six waves per SIMD by the compiler's count.  (Tried:
+// amdgpu_waves_per_eu(7) — 72 VGPRs, five spilled, scratch loads in the cell loop: slower in every run,
+// profiles/prepass_latency_ab.txt.  A second cell in flight would be sixteen more.)
+// NARROW: the instance for frames narrower than one clamped load (below), which keeps the byte path; every other frame runs
+// the instance without it.
+template <bool NARROW>
 static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneGeo pg, const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
     constexpr int NT = PRUNE_NT, NW = NT / 64, CH = ROLL_CH, TW = ROLL_TW, PB = PRUNE_B;
@@ -125,6 +132,14 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
     const int ti0 = g1 - g.r1 - 1 - hw, wj0 = g2 - g.r2 - 1 - hw; // frame row / column of the tile's first pixel
     const tap_ptr trow = as_taps(taps_row), tcol = as_taps(taps_col);
     const uint32_t fill4 = (uint32_t)g.fill * 0x01010101u;
+#ifdef PDOG_ABLATIONS
+    // Phase stamps (diagnostic build; tools/prune_phases.py): thread 0 of every workgroup adds the cycles since its last stamp
+    // to stat[4 + phase] with an ordinary atomic, and counts itself in stat[4 + PRUNE_PHASES].
+    unsigned long long stamp_prev = __builtin_readcyclecounter();
+#define PRUNE_STAMP(i) do { if (tid == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); atomicAdd(pg.stat + 4 + (i), now_ - stamp_prev); stamp_prev = now_; } } while (0)
+#else
+#define PRUNE_STAMP(i) do { } while (0)
+#endif
 
     const int ncols = g.nthin ? g.thin_x0 : g.n2; // window columns the strips cover
     const int ws = min(TW, ncols);
@@ -142,10 +157,19 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         }
         return id;
     };
-    // One dword of the tile at frame row gi, frame column gj: the bytes inside the frame (`in`: pw_mask(gj, 0, fw) in a row of
-    // the frame, else 0), 0 elsewhere.  Every address read lies in a row of the frame at a column of the frame: a dword that
-    // hangs over the frame's edge is read byte by byte.
+    // HOW THE FRAME IS READ.  Every address read lies in a row of the frame at a column of the frame, and no load stands behind
+    // a branch that another load decides: a word of the tile is loaded at its row and start column CLAMPED into the frame, all
+    // loads of an item are requested together, and the tile's word is rebuilt afterwards by a shift of the clamp distance
+    // (dog_prune_words.hpp, "clamped loads"); the in-frame masks select the fill as before.  (Before: a cell on the frame's
+    // edge read row by row, dword by dword and, over the left or right edge, byte by byte, each load behind its own wait —
+    // 16 to 64 memory round trips where an interior cell takes one, and one such lane holds its whole wave.)  A frame
+    // narrower than one load (fw < 8 for the cells, < 4 for single dwords) keeps the byte path, tile_word: that case is cold.
     auto row_in = [&](int gi) { return gi >= 0 && gi < g.fh; };
+    const bool narrow8 = NARROW && g.fw < 8, narrow4 = NARROW && g.fw < 4;
+    const unsigned rs = (unsigned)g.row_stride; // (at most PDOG_MAX_ROW_STRIDE: an offset inside a frame is a 32 × 32-bit product)
+    auto frame_at = [&](int gi, int gjc) { return frame + ((unsigned long long)(unsigned)pw_clamp_row(gi, g.fh) * rs + (unsigned)gjc); };
+    // One dword of the tile at frame row gi, frame column gj, byte by byte: the bytes inside the frame (`in`: pw_mask(gj, 0, fw)
+    // in a row of the frame, else 0), 0 elsewhere.
     auto tile_word = [&](int gi, int gj, uint32_t in) -> uint32_t {
         uint32_t w = 0;
         if (in == 0xffffffffu) {
@@ -158,12 +182,55 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         return w;
     };
 
+    // ---- the energy pass's items and their loads (the pass itself: below) ----
+    const int nitems = nsub * ncx;
+    // the cell's sixteen dwords, row r in w[2r], w[2r + 1]: as loaded at the clamped address (narrow frame: the tile's words)
+    auto cell_load = [&](int band, int cx, uint32_t (&w)[2 * CH]) {
+        const int gj = wj0 + 8 * cx, gi0 = ti0 + band * CH;
+        if (!narrow8) {
+            const uint8_t *src = frame_at(gi0, pw_clamp_col(gj, g.fw, 8));
+#pragma unroll
+            for (int r = 0; r < CH; ++r) { // (the clamped row moves on from row gi0 + r iff 0 ≤ gi0 + r < fh − 1)
+                __builtin_memcpy(&w[2 * r], src, 8);
+                src += (unsigned)(gi0 + r) < (unsigned)(g.fh - 1) ? rs : 0u;
+            }
+        } else {
+            const uint32_t in_a = pw_mask(gj, 0, g.fw), in_b = pw_mask(gj + 4, 0, g.fw);
+            for (int r = 0; r < CH; ++r) {
+                const bool rin = row_in(gi0 + r);
+                w[2 * r] = tile_word(gi0 + r, gj, rin ? in_a : 0u);
+                w[2 * r + 1] = tile_word(gi0 + r, gj + 4, rin ? in_b : 0u);
+            }
+        }
+    };
+
     if (tid == 0) { s_kept = 0; s_nstr = 0; }
-    for (int i = tid; i < nsub * nseg * 2; i += NT) S[i] = 0;
-    // ---- the window's DC level: the strips' samples and rounding ----
+    // ---- the window's DC level: the strips' samples (dc_sample_sum's grid) and rounding.  A thread's samples are requested
+    // together at clamped addresses and the fill is selected afterwards; the first cell's loads follow them at once — a
+    // cell's moments do not depend on dc — so both are in flight while the segment sums are zeroed and the samples reduced ----
     int dc;
+    uint32_t cur[2 * CH];
     {
-        int sum = wave_sum(dc_sample_sum(g, frame, ti0, wj0, L, tid, NT));
+        constexpr int DCN = 1024 / NT;
+        const int tH = NA, tW = TWin;
+        int sv[DCN];
+        bool sin[DCN];
+#pragma unroll
+        for (int j = 0; j < DCN; ++j) {
+            const int k = tid + j * NT;
+            const int gi = ti0 + (int)(((long long)(k >> 5) * tH) >> 5), gj = wj0 + (int)(((long long)(k & 31) * tW) >> 5);
+            sin[j] = row_in(gi) && gj >= 0 && gj < g.fw;
+            sv[j] = *frame_at(gi, min(max(gj, 0), g.fw - 1));
+        }
+        {
+            const int it0 = min(tid, nitems - 1), band0 = it0 / ncx; // (a thread without an item loads the last one, and drops it)
+            cell_load(band0, it0 - band0 * ncx, cur);
+        }
+        for (int i = tid; i < nsub * nseg * 2; i += NT) S[i] = 0;
+        int sum = 0;
+#pragma unroll
+        for (int j = 0; j < DCN; ++j) sum += sin[j] ? sv[j] : g.fill;
+        sum = wave_sum(sum);
         if (lane == 0) s_sum[wave] = sum;
         __syncthreads();
         int tot = 0;
@@ -180,62 +247,74 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         segd[d] = (short)sd;
     }
     __syncthreads();
+    PRUNE_STAMP(0); // DC level, segment table
 
-    // ---- energy pass (above).  Per dword: a load, the two substituted words, two dots, four ands, four packed min / max ----
+    // ---- energy pass (above).  Per dword: the two substituted words, two dots, four ands, four packed min / max.  The loads
+    // of the thread's next cell are requested before the sums of this one (sixteen registers each) ----
     PwAcc ext = pw_init(); // (its extremes only: the thread's pixels of all its items)
-    {
-        int band = tid / ncx, cx = tid - band * ncx;
-        const int bstep = NT / ncx, cstep = NT - bstep * ncx;
-        for (int it = tid; it < nsub * ncx; it += NT) {
-            const int col0 = 8 * cx, gj = wj0 + col0, a0 = band * CH, gi0 = ti0 + a0, nr = min(CH, NA - a0);
-            const uint32_t cnt_a = pw_mask(col0, 0, TWin), cnt_b = pw_mask(col0 + 4, 0, TWin);
-            uint32_t s2a = 0, s1a = 0, s2b = 0, s1b = 0; // the moments of the cell's two dwords
-            if (nr == CH && gi0 >= 0 && gi0 + CH <= g.fh && gj >= 0 && gj + 8 <= g.fw) { // the cell inside the frame
-                const uint8_t *src = frame + (long long)gi0 * g.row_stride + gj;
+    auto cell_sums = [&](int band, int cx, const uint32_t (&w)[2 * CH]) {
+        const int col0 = 8 * cx, gj = wj0 + col0, a0 = band * CH, gi0 = ti0 + a0, nr = min(CH, NA - a0);
+        const uint32_t cnt_a = pw_mask(col0, 0, TWin), cnt_b = pw_mask(col0 + 4, 0, TWin);
+        uint32_t s2a = 0, s1a = 0, s2b = 0, s1b = 0; // the moments of the cell's two dwords
+        if (nr == CH && gi0 >= 0 && gi0 + CH <= g.fh && gj >= 0 && gj + 8 <= g.fw) { // the cell inside the frame: nothing was clamped
+#pragma unroll
+            for (int r = 0; r < CH; ++r) {
+                const PwWords xa = pw_words(w[2 * r], 0xffffffffu, cnt_a, fill4), xb = pw_words(w[2 * r + 1], 0xffffffffu, cnt_b, fill4);
+                pw_moments(s2a, s1a, xa.wz);
+                pw_extremes(ext, xa);
+                pw_moments(s2b, s1b, xb.wz);
+                pw_extremes(ext, xb);
+            }
+        } else {
+            const uint32_t in_a = pw_mask(gj, 0, g.fw), in_b = pw_mask(gj + 4, 0, g.fw);
+            if ((in_a | in_b) == 0u || gi0 >= g.fh || gi0 + nr <= 0) { // the cell outside the frame: nr rows of fill
+                const PwWords xa = pw_words(0u, 0u, cnt_a, fill4), xb = pw_words(0u, 0u, cnt_b, fill4);
+                pw_moments(s2a, s1a, xa.wz);
+                pw_moments(s2b, s1b, xb.wz);
+                s2a *= (uint32_t)nr; s1a *= (uint32_t)nr; s2b *= (uint32_t)nr; s1b *= (uint32_t)nr;
+                pw_extremes(ext, xa);
+                pw_extremes(ext, xb);
+            } else { // the cell on the frame's edge: the words rebuilt, a row outside the frame all fill, a row at or past NA not counted
+                const PwShift sh = narrow8 ? PwShift{0u, 0u} : pw_shift(pw_clamp_col(gj, g.fw, 8) - gj, 8);
 #pragma unroll
                 for (int r = 0; r < CH; ++r) {
-                    uint32_t w[2];
-                    __builtin_memcpy(w, src + (long long)r * g.row_stride, 8);
-                    const PwWords xa = pw_words(w[0], 0xffffffffu, cnt_a, fill4), xb = pw_words(w[1], 0xffffffffu, cnt_b, fill4);
+                    const bool rin = row_in(gi0 + r), rc = r < nr;
+                    const uint64_t v = pw_rebuild64((uint64_t)w[2 * r] | ((uint64_t)w[2 * r + 1] << 32), sh);
+                    const PwWords xa = pw_words((uint32_t)v, rin ? in_a : 0u, rc ? cnt_a : 0u, fill4);
+                    const PwWords xb = pw_words((uint32_t)(v >> 32), rin ? in_b : 0u, rc ? cnt_b : 0u, fill4);
                     pw_moments(s2a, s1a, xa.wz);
                     pw_extremes(ext, xa);
                     pw_moments(s2b, s1b, xb.wz);
                     pw_extremes(ext, xb);
                 }
-            } else {
-                const uint32_t in_a = pw_mask(gj, 0, g.fw), in_b = pw_mask(gj + 4, 0, g.fw);
-                if ((in_a | in_b) == 0u || gi0 >= g.fh || gi0 + nr <= 0) { // the cell outside the frame: nr rows of fill
-                    const PwWords xa = pw_words(0u, 0u, cnt_a, fill4), xb = pw_words(0u, 0u, cnt_b, fill4);
-                    pw_moments(s2a, s1a, xa.wz);
-                    pw_moments(s2b, s1b, xb.wz);
-                    s2a *= (uint32_t)nr; s1a *= (uint32_t)nr; s2b *= (uint32_t)nr; s1b *= (uint32_t)nr;
-                    pw_extremes(ext, xa);
-                    pw_extremes(ext, xb);
-                } else {
-                    for (int r = 0; r < nr; ++r) { // (rows at or past NA are read by no output)
-                        const bool rin = row_in(gi0 + r);
-                        const uint32_t ia = rin ? in_a : 0u, ib = rin ? in_b : 0u;
-                        const PwWords xa = pw_words(tile_word(gi0 + r, gj, ia), ia, cnt_a, fill4), xb = pw_words(tile_word(gi0 + r, gj + 4, ib), ib, cnt_b, fill4);
-                        pw_moments(s2a, s1a, xa.wz);
-                        pw_extremes(ext, xa);
-                        pw_moments(s2b, s1b, xb.wz);
-                        pw_extremes(ext, xb);
-                    }
-                }
             }
-            cell[band * ncx + cx] = pw_sum(s1a + s1b, nr * min(TWin - col0, 8), dc);
-            const int sda = segd[2 * cx], sdb = segd[2 * cx + 1];
-            unsigned *Sb = S + 2 * band * nseg;
-            if (sda == sdb) {
-                if (sda >= 0) { atomicAdd(Sb + 2 * sda, s2a + s2b); atomicAdd(Sb + 2 * sda + 1, s1a + s1b); }
-            } else {
-                if (sda >= 0) { atomicAdd(Sb + 2 * sda, s2a); atomicAdd(Sb + 2 * sda + 1, s1a); }
-                if (sdb >= 0) { atomicAdd(Sb + 2 * sdb, s2b); atomicAdd(Sb + 2 * sdb + 1, s1b); }
-            }
-            cx += cstep;
-            band += bstep;
-            if (cx >= ncx) { cx -= ncx; ++band; }
         }
+        cell[band * ncx + cx] = pw_sum(s1a + s1b, nr * min(TWin - col0, 8), dc);
+        const int sda = segd[2 * cx], sdb = segd[2 * cx + 1];
+        unsigned *Sb = S + 2 * band * nseg;
+        if (sda == sdb) {
+            if (sda >= 0) { atomicAdd(Sb + 2 * sda, s2a + s2b); atomicAdd(Sb + 2 * sda + 1, s1a + s1b); }
+        } else {
+            if (sda >= 0) { atomicAdd(Sb + 2 * sda, s2a); atomicAdd(Sb + 2 * sda + 1, s1a); }
+            if (sdb >= 0) { atomicAdd(Sb + 2 * sdb, s2b); atomicAdd(Sb + 2 * sdb + 1, s1b); }
+        }
+    };
+    if (tid < nitems) {
+        // the cells of the whole tile dealt out in order: (band, cell) advance by the constant (NT ÷ ncx, NT mod ncx)
+        int band = tid / ncx, cx = tid - band * ncx;
+        const int bstep = NT / ncx, cstep = NT - bstep * ncx;
+        for (int it = tid + NT; it < nitems; it += NT) {
+            int nband = band + bstep, ncell = cx + cstep;
+            if (ncell >= ncx) { ncell -= ncx; ++nband; }
+            uint32_t nxt[2 * CH];
+            cell_load(nband, ncell, nxt);
+            cell_sums(band, cx, cur);
+#pragma unroll
+            for (int i = 0; i < 2 * CH; ++i) cur[i] = nxt[i];
+            band = nband;
+            cx = ncell;
+        }
+        cell_sums(band, cx, cur); // the thread's last cell: nothing more to request
     }
     {
         const int pmax = wave_reduce_bits(pw_pmax(ext), [](int a, int c) { return a > c ? a : c; });
@@ -243,26 +322,37 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         if (lane == 0) { s_pmax[wave] = pmax; s_pmin[wave] = pmin; }
     }
     __syncthreads();
+    PRUNE_STAMP(1); // energy pass
 
     // ---- the dwords that straddle a cut, a column per task: the same words, masked to the one byte ----
     for (int j = 0, nstr = s_nstr; j < nstr; ++j) {
         const int d = strd[j], gj = wj0 + 4 * d;
         const uint32_t in_cols = pw_mask(gj, 0, g.fw);
+        const int gjc = narrow4 ? 0 : pw_clamp_col(gj, g.fw, 4);
+        const PwShift sh = narrow4 ? PwShift{0u, 0u} : pw_shift(gjc - gj, 4);
         for (int t = tid; t < 4 * nsub; t += NT) {
             const int band = t >> 2, col = 4 * d + (t & 3), a0 = band * CH, nr = min(CH, NA - a0);
             if (col >= TWin) continue;
             const uint32_t counted = pw_mask(4 * d, col, col + 1);
+            uint32_t w[CH]; // the band's eight rows of the dword, requested together
+            if (!narrow4) {
+#pragma unroll
+                for (int r = 0; r < CH; ++r) __builtin_memcpy(&w[r], frame_at(ti0 + a0 + r, gjc), 4);
+            } else {
+                for (int r = 0; r < CH; ++r) w[r] = tile_word(ti0 + a0 + r, gj, row_in(ti0 + a0 + r) ? in_cols & counted : 0u);
+            }
             uint32_t s2 = 0, s1 = 0;
-            for (int r = 0; r < nr; ++r) {
-                const int gi = ti0 + a0 + r;
-                const uint32_t in = row_in(gi) ? in_cols & counted : 0u;
-                pw_moments(s2, s1, pw_words(tile_word(gi, gj, in), in, counted, fill4).wz);
+#pragma unroll
+            for (int r = 0; r < CH; ++r) { // (a row at or past NA is not counted)
+                const uint32_t in = row_in(ti0 + a0 + r) ? in_cols & counted : 0u;
+                pw_moments(s2, s1, pw_words(pw_rebuild32(w[r], sh), in, r < nr ? counted : 0u, fill4).wz);
             }
             unsigned *Sb = S + 2 * (band * nseg + seg_id(col));
             atomicAdd(Sb, s2);
             atomicAdd(Sb + 1, s1);
         }
     }
+    PRUNE_STAMP(2); // straddle pass
 
     // ---- where to take L: the cell whose direction-signed 3 × 3-cell sum is largest, the first such cell in row-major
     // order.  Separably: a thread walks a run of one cell column downwards, three reads per cell for the three-sum along x
@@ -320,6 +410,9 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         V = pw_V(pmax, pmin, dc);
     }
     __syncthreads(); // (the segment sums are dead from here: R and the patch take their place)
+    PRUNE_STAMP(3); // cell choice and E
+    int *hull = cell; // [nslots] (first kept block, one past the last): the cell sums are dead from here too
+    for (int sl = tid; sl < g.nslots; sl += NT) { hull[2 * sl] = 0x7fffffff; hull[2 * sl + 1] = 0; }
     const int cy = s_cellbest / ncx, cx = s_cellbest - cy * ncx;
     // the cell's centre is tile pixel (8cy + 4, 8cx + 4) = the centre input of output (8cy + 4 − l÷2, 8cx + 4 − l÷2)
     const int ny = min(PB, g.n1), nx = min(PB, g.n2);
@@ -327,19 +420,43 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
     const int PH = ny + L - 1, PW = nx + L - 1, PP = (PB + L - 1 + 3) / 4 * 4, PQ = (PW + 3) / 4;
     {
         // the patch in dwords, fill substituted (the bytes of a row's last dword past PW are read and never used)
+        // A thread's dwords are requested PU at a time (all six of l = 65 at once) before the first is stored; an element past
+        // the patch's end lies in a row past PH, is loaded like any other at its clamped address and is not stored.
+        constexpr int PU = 6;
         uint32_t *pw32 = reinterpret_cast<uint32_t *>(patch);
         int a = tid / PQ, q = tid - a * PQ;
         const int astep = NT / PQ, qstep = NT - astep * PQ;
-        for (int e = tid; e < PH * PQ; e += NT) {
-            const int gi = ti0 + oy + a, gj = wj0 + ox + 4 * q;
-            const uint32_t in = row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u;
-            pw32[a * (PP / 4) + q] = pw_words(tile_word(gi, gj, in), in, 0xffffffffu, fill4).wz;
-            q += qstep;
-            a += astep;
-            if (q >= PQ) { q -= PQ; ++a; }
+        for (int e0 = tid; e0 < PH * PQ; e0 += PU * NT) {
+            int pa[PU], pq[PU];
+            uint32_t w[PU];
+#pragma unroll
+            for (int j = 0; j < PU; ++j) {
+                pa[j] = a;
+                pq[j] = q;
+                q += qstep;
+                a += astep;
+                if (q >= PQ) { q -= PQ; ++a; }
+            }
+            if (!narrow4) {
+#pragma unroll
+                for (int j = 0; j < PU; ++j) __builtin_memcpy(&w[j], frame_at(ti0 + oy + pa[j], pw_clamp_col(wj0 + ox + 4 * pq[j], g.fw, 4)), 4);
+            } else {
+                for (int j = 0; j < PU; ++j) {
+                    const int gi = ti0 + oy + pa[j], gj = wj0 + ox + 4 * pq[j];
+                    w[j] = tile_word(gi, gj, row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < PU; ++j) {
+                const int gi = ti0 + oy + pa[j], gj = wj0 + ox + 4 * pq[j];
+                const uint32_t in = row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u;
+                const PwShift sh = narrow4 ? PwShift{0u, 0u} : pw_shift(pw_clamp_col(gj, g.fw, 4) - gj, 4);
+                if (e0 + j * NT < PH * PQ) pw32[pa[j] * (PP / 4) + pq[j]] = pw_words(pw_rebuild32(w[j], sh), in, 0xffffffffu, fill4).wz;
+            }
         }
     }
     __syncthreads();
+    PRUNE_STAMP(4); // patch
     // Row pass in the strips' order: pairs k ascending, centre last.  A thread is (input row, output column xo); the pixels
     // of four pairs come as two unaligned dwords (v_alignbyte_b32 over two aligned LDS dwords each): p[xo + 4i … + 3] and
     // p[xo + l − 4 − 4i … + 3], the second read from its last byte down.  A pair's input is the integer
@@ -370,6 +487,7 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
             }
     }
     __syncthreads();
+    PRUNE_STAMP(5); // row pass of L
     if (wave == 0) {
         // column pass in the strips' order: taps ascending, the g₊ term then the g₋ term into one f32
         const int yo = lane & (PB - 1), xo = lane / PB;
@@ -393,24 +511,32 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         }
     }
     __syncthreads();
+    PRUNE_STAMP(6); // column pass of L, threshold
 
-    // ---- per slot: the hull of the blocks that cannot be excluded ----
+    // ---- per slot: the hull of the blocks that cannot be excluded.  A lane per (slot, block): the block's sub-chunks summed
+    // in exact integers (any order gives the same sum), the first and one past the last kept block of a slot met by LDS
+    // minimum / maximum.  (Before: a thread per slot slid the sum down the blocks, 33 dependent steps in 5 threads.) ----
     const int nblk = (g.n1 + CH - 1) / CH, NS = prune_span(L);
-    for (int sl = tid; sl < g.nslots; sl += NT) {
-        const unsigned *Es = E + sl * nsub;
-        unsigned long long sum = 0;
-        for (int sc = 0; sc < min(NS, nsub); ++sc) sum += Es[sc];
-        int ba = -1, bb = 0;
-        for (int j = 0; j < nblk; ++j) {
-            if ((double)sum >= s_emax) { if (ba < 0) ba = j; bb = j + 1; }
-            sum -= Es[j];
-            if (j + NS < nsub) sum += Es[j + NS];
+    {
+        const double emax = s_emax;
+        for (int t = tid; t < g.nslots * nblk; t += NT) {
+            const int sl = t / nblk, j = t - sl * nblk;
+            const unsigned *Es = E + sl * nsub + j;
+            unsigned long long sum = 0;
+            for (int k = 0, n = min(NS, nsub - j); k < n; ++k) sum += Es[k];
+            if ((double)sum >= emax) { atomicMin(&hull[2 * sl], j); atomicMax(&hull[2 * sl + 1], j + 1); }
         }
-        if (ba < 0) ba = bb = 0;
+    }
+    __syncthreads();
+    for (int sl = tid; sl < g.nslots; sl += NT) {
+        int ba = hull[2 * sl];
+        const int bb = hull[2 * sl + 1];
+        if (bb == 0) ba = 0;
         g.part_mask[(long long)b * g.nslots + sl] = (unsigned long long)(unsigned)ba | ((unsigned long long)(unsigned)bb << 32);
         atomicAdd(&s_kept, prune_sc_hi(ba, bb, L, nsub) - ba);
     }
     __syncthreads();
+    PRUNE_STAMP(7); // hulls
     if (tid == 0) {
         __hip_atomic_fetch_add(pg.stat, (unsigned long long)s_kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_add(pg.stat + 1, (unsigned long long)(g.nslots * nsub), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -424,6 +550,11 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
             __hip_atomic_store(pg.host, (k & 0xffffffffull) | (tt << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+    PRUNE_STAMP(8); // publish
+#ifdef PDOG_ABLATIONS
+    if (tid == 0) atomicAdd(pg.stat + 4 + PRUNE_PHASES, 1ull);
+#endif
+#undef PRUNE_STAMP
 }
 #endif // PDOG_ROLL_INST_ONLY
 

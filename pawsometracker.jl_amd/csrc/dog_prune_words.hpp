@@ -42,6 +42,23 @@ PW_HD PwWords pw_words(uint32_t w, uint32_t in_frame, uint32_t counted, uint32_t
     return PwWords{z, z | ~counted};
 }
 
+// CLAMPED LOADS.  A word of the tile that hangs over the frame's left or right edge is not read byte by byte: the load starts
+// at the asked column clamped into [0, fw − width] (pw_clamp_col; the row likewise into [0, fh − 1], pw_clamp_row), so every
+// byte read lies in a row of the frame at a column of the frame, and the tile's word is the loaded one shifted by the clamp
+// distance d = clamped − asked column (pw_shift, pw_rebuild32 / 64): d > 0 (over the left edge) moves the bytes up, d < 0
+// (over the right edge) down, and zeros come in where the column lies outside the frame.  Where |d| ≥ width no byte of the
+// word lies inside the frame (its in-frame mask is 0) and the rebuilt word is not specified.  Needs fw ≥ width.
+PW_HD int pw_clamp_col(int gj, int fw, int width) { return gj < 0 ? 0 : gj > fw - width ? fw - width : gj; }
+PW_HD int pw_clamp_row(int gi, int fh) { return gi < 0 ? 0 : gi > fh - 1 ? fh - 1 : gi; }
+struct PwShift { unsigned up, down; }; // bits
+PW_HD PwShift pw_shift(int d, int width)
+{
+    const int m = width - 1, u = d > m ? m : d, n = -d > m ? m : -d;
+    return PwShift{d > 0 ? 8u * (unsigned)u : 0u, d < 0 ? 8u * (unsigned)n : 0u};
+}
+PW_HD uint32_t pw_rebuild32(uint32_t w, PwShift s) { return (w << s.up) >> s.down; }
+PW_HD uint64_t pw_rebuild64(uint64_t w, PwShift s) { return (w << s.up) >> s.down; }
+
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef unsigned short pw_us2 __attribute__((ext_vector_type(2)));
 PW_HD uint32_t pw_dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }

@@ -1208,7 +1208,7 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         pg.darker = t->darker;
         pg.stat = t->d_prune_stat.get();
         pg.host = &t->h_pinned.device()->prune_pub;
-        hipLaunchKernelGGL(dog_prune_kernel, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
+        hipLaunchKernelGGL(t->fw < 8 ? dog_prune_kernel<true> : dog_prune_kernel<false>, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
         HIP_TRY(hipGetLastError());
         g.prune = 1;
     }
@@ -1436,7 +1436,7 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
             t->F_sym_int = ef.sym_int; t->F_sym_sep = ef.sym_sep; t->F_ring = ef.ring; t->F_rescan = ef.rescan;
         }
         t->K_norm = dog_kernel_norm_up(gp, gm);
-        if (int rc = t->d_prune_stat.reserve(4, nullptr, true)) return rc;
+        if (int rc = t->d_prune_stat.reserve(4 + PRUNE_PHASES + 1, nullptr, true)) return rc; // [4 …]: phase cycles of the pre-pass and the workgroups that stamped (diagnostic build)
         if (int rc = t->d_ref_stat.reserve(16, nullptr, true)) return rc; // [4..7] unused, [8..15]: phase cycles of the refinement (diagnostic build)
         {
             std::vector<double> g2(2 * (size_t)t->L);
@@ -1625,6 +1625,16 @@ int pdog_get_prune_counts(pdog_tracker *t, uint64_t out[2])
     HIP_TRY(hipMemcpy(v, t->d_prune_stat.get(), sizeof v, hipMemcpyDeviceToHost));
     out[0] = (uint64_t)v[0];
     out[1] = (uint64_t)v[1];
+#ifdef PDOG_ABLATIONS
+    {
+        unsigned long long ph[PRUNE_PHASES + 1];
+        HIP_TRY(hipMemcpy(ph, t->d_prune_stat.get() + 4, sizeof ph, hipMemcpyDeviceToHost));
+        const double wg = ph[PRUNE_PHASES] ? (double)ph[PRUNE_PHASES] : 1.0;
+        std::fprintf(stderr, "pdog prune phases (cycles per workgroup, thread 0; %llu workgroups): dc %.0f, energy %.0f, straddle %.0f, cell+E %.0f, patch %.0f, row %.0f, "
+                             "col %.0f, hull %.0f, publish %.0f\n",
+                     ph[PRUNE_PHASES], ph[0] / wg, ph[1] / wg, ph[2] / wg, ph[3] / wg, ph[4] / wg, ph[5] / wg, ph[6] / wg, ph[7] / wg, ph[8] / wg);
+    }
+#endif
     return PDOG_OK;
 }
 
