@@ -91,6 +91,22 @@ def exclusive_args(n_targets, k, min_distance, min_ratio):
     return k, md, float(min_ratio)
 
 
+def motion_args(n_targets, k, min_distance, min_ratio, min_response, coast):
+    """What the motion step takes beside its arrays: exclusive_args' four, the least response an entry must EXCEED — a finite
+    real number >= 0 — and the number of held steps a target keeps its velocity for, an integer >= 0.  Returns (k,
+    min_distance, min_ratio, min_response, coast) as the library takes them."""
+    k, md, rho = exclusive_args(n_targets, k, min_distance, min_ratio)
+    if isinstance(min_response, bool) or not isinstance(min_response, (int, float, np.integer, np.floating)):
+        raise TypeError(f"min_response must be a real number, not {type(min_response).__name__}")
+    if not 0.0 <= float(min_response) <= 3.4028234663852886e38:    # (it is compared as a float32; a NaN fails both comparisons)
+        raise ValueError(f"min_response: {min_response} is not a finite float32 >= 0")
+    if isinstance(coast, bool) or not isinstance(coast, (int, np.integer)):
+        raise TypeError(f"coast must be an integer, not {type(coast).__name__}")
+    if not 0 <= coast < 2**31:
+        raise ValueError(f"coast: {coast} is not a number of steps >= 0")
+    return k, md, rho, float(min_response), int(coast)
+
+
 def host_table(v, name):
     """A frame table — a sequence of rows, a numpy array or a tensor of integers [n_clips, n_steps] — as a contiguous host int32
     array.  Its entries are the library's to judge (it validates them before it launches anything)."""

@@ -136,6 +136,17 @@ EXCLUSIVE_PROTOTYPES = {
 }
 EXCLUSIVE_SYMBOLS = tuple(EXCLUSIVE_PROTOTYPES)
 EXCLUSIVE_MAX_TARGETS = 32   # PDOG_EXCLUSIVE_MAX_TARGETS
+
+# the same for include/pawsome_motion.h, which includes pawsome_exclusive.h: exclusive chains with a motion model
+# (tests/test_motion_cpu.py holds this table against that header)
+MOTION_PROTOTYPES = {
+    "pdog_assign_motion": (_i, [_p, _i, _i, _i, _i, _d, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pdog_assign_motion_host": (_i, [_i, _i, _i, _i, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pdog_detect_chains_motion": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _i, _i, _i, _i, _i, _d, _d, _i, _p, _p, _p, _p]),
+    "pdog_get_motion_counts": (_i, [_p, _pu64]),
+}
+MOTION_SYMBOLS = tuple(MOTION_PROTOTYPES)
+MOTION_MAX_TARGETS = 32      # PDOG_MOTION_MAX_TARGETS
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -181,7 +192,7 @@ def lib():
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
-                                      **EXCLUSIVE_PROTOTYPES}.items():
+                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -274,6 +285,12 @@ class TrackerHandle(Handle):
         """(joint steps enqueued, times a workspace of the exclusive calls grew) — pdog_get_exclusive_counts."""
         out = (C.c_uint64 * 2)()
         check(lib().pdog_get_exclusive_counts(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def motion_counts(self):
+        """(motion steps enqueued, times a workspace of the motion calls grew) — pdog_get_motion_counts."""
+        out = (C.c_uint64 * 2)()
+        check(lib().pdog_get_motion_counts(self._h, out))
         return int(out[0]), int(out[1])
 
     def batch_maxima(self, n):

@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, peaks_args
+from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args
 
 
 class BatchTracker(_lib.TrackerHandle):
@@ -220,6 +220,68 @@ class BatchTracker(_lib.TrackerHandle):
             C.c_void_p(table.ctypes.data), ns, ng, nt, int(first), k, md, rho, C.c_void_p(starts.data_ptr()),
             C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr())))
         return out, state
+
+    def assign_motion(self, prev, mstate, ij, peak, count, min_distance=None, min_ratio=0.5, min_response=0.0, coast=8):
+        """The motion step alone (pdog_assign_motion; this library's addition, the rule is stated in include/pawsome_motion.h):
+        every target takes the free peak NEAREST to its prediction clamp(p + v), a target that finds none coasts along it.
+        prev int32 cuda [n_groups, n_targets, 2], the positions p; mstate int32 cuda [n_groups, n_targets, 4], (v_row, v_col,
+        n_held, 0), UPDATED IN PLACE; ij, peak and count as for assign_exclusive — what detect_peaks returned for the windows
+        at the PREDICTIONS.  An entry must exceed min_response and reach min_ratio times its window's best; a held target
+        keeps its velocity for `coast` steps.  Returns (positions int32 cuda [n_groups, n_targets, 2], state int32 cuda
+        [n_groups, n_targets], next guesses int32 cuda [n_groups, n_targets, 2]): state is the number of the pick a target was
+        assigned, 1 ... k, or -1 where it was held and its position is the prediction."""
+        import torch
+        self.use_torch_stream()
+        if not isinstance(prev, torch.Tensor) or prev.dim() != 3 or not isinstance(ij, torch.Tensor) or ij.dim() != 4:
+            raise TypeError("prev must be an int32 cuda tensor [n_groups, n_targets, 2], ij one [n_groups, n_targets, k, 2]")
+        ng, nt, k = int(ij.shape[0]), int(ij.shape[1]), int(ij.shape[2])
+        if ng < 1:
+            raise ValueError("ij: no group")
+        k, md, rho, m, coast = motion_args(nt, k, min_distance, min_ratio, min_response, coast)
+        device_array(prev, "prev", torch.int32, (ng, nt, 2))
+        device_array(mstate, "mstate", torch.int32, (ng, nt, 4))
+        device_array(ij, "ij", torch.int32, (ng, nt, k, 2))
+        device_array(peak, "peak", torch.float32, (ng, nt, k))
+        device_array(count, "count", torch.int32, (ng, nt))
+        out = torch.empty((ng, nt, 2), dtype=torch.int32, device=ij.device)
+        state = torch.empty((ng, nt), dtype=torch.int32, device=ij.device)
+        nxt = torch.empty((ng, nt, 2), dtype=torch.int32, device=ij.device)
+        P = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().pdog_assign_motion(self._h, ng, nt, k, md, rho, m, coast, P(prev), P(mstate), P(ij), P(peak), P(count),
+                                                 P(out), P(state), P(nxt)))
+        return out, state, nxt
+
+    def detect_chains_motion(self, frames, frame_table, starts, k=None, min_distance=None, min_ratio=0.5, min_response=0.0, coast=8,
+                             first=0, mstate=None):
+        """The walk with a motion model over a frame table (pdog_detect_chains_motion): frames, frame_table, starts, k,
+        min_distance, min_ratio and first as for detect_chains_exclusive.  Per step every target's window is centred on its
+        prediction and the group's targets share out the peaks as assign_motion states.  mstate None: the walk starts at
+        rest; otherwise int32 cuda [n_groups, n_targets, 4], the state a former call returned — it is updated in place, and
+        a walk continued from a call's last positions and its mstate equals the one-call walk.  Returns (indices int32 cuda
+        [n_groups, n_targets, n_steps, 2], state int32 cuda [n_groups, n_targets, n_steps], mstate); steps at and beyond a
+        group's end are not written (both are zeroed)."""
+        import torch
+        self.use_torch_stream()
+        device_frames(frames, "frames", 3, self._hw)
+        table = host_table(frame_table, "frame_table")
+        ng, ns = table.shape
+        if not isinstance(starts, torch.Tensor) or starts.dim() != 3:
+            raise TypeError("starts must be an int32 cuda tensor [n_groups, n_targets, 2]")
+        nt = int(starts.shape[1])
+        k, md, rho, m, coast = motion_args(nt, k, min_distance, min_ratio, min_response, coast)
+        if isinstance(first, bool) or first not in (0, 1):
+            raise ValueError(f"first: {first!r} is neither 0 nor 1")
+        device_array(starts, "starts", torch.int32, (ng, nt, 2))
+        if mstate is None:
+            mstate = torch.zeros((ng, nt, 4), dtype=torch.int32, device=frames.device)
+        device_array(mstate, "mstate", torch.int32, (ng, nt, 4))
+        out = torch.zeros((ng, nt, ns, 2), dtype=torch.int32, device=frames.device)
+        state = torch.zeros((ng, nt, ns), dtype=torch.int32, device=frames.device)
+        _lib.check(_lib.lib().pdog_detect_chains_motion(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
+            C.c_void_p(table.ctypes.data), ns, ng, nt, int(first), k, md, rho, m, coast, C.c_void_p(starts.data_ptr()),
+            C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
+        return out, state, mstate
 
     def measure(self, frames, ij, frame_index=None, want_resp=False):
         """Sub-pixel positions (and peak responses) at tracked points (pdog_measure).  frames: uint8 cuda tensor

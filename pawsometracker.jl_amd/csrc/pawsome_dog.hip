@@ -365,6 +365,7 @@ struct pdog_tracker {
     Ingest ingest;
     pdog::PeaksState peaks; // pdog_detect_peaks (pawsome_peaks.hip): its scratch, switch and counters
     pdog::ExclusiveState exclusive; // the exclusive step and walk (pawsome_exclusive.hip): their scratch and counters
+    pdog::MotionState motion;       // the motion step and walk (pawsome_motion.hip): their scratch, switch and counters
 
     // Drains and destroys the streams and events; the buffers free themselves after that.
     ~pdog_tracker()
@@ -393,6 +394,12 @@ pdog::ExclusiveState *pdog::exclusive_state(pdog_tracker *t)
 {
     t->exclusive.device = t->device;
     return &t->exclusive;
+}
+
+pdog::MotionState *pdog::motion_state(pdog_tracker *t)
+{
+    t->motion.device = t->device;
+    return &t->motion;
 }
 
 namespace {
@@ -1596,6 +1603,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h
+    else if (k == "motion_lds") t->motion.lds = on;       // include/pawsome_motion.h
     else if (k == "no_fused_c" || k == "no_tiled") { // inputs of the plan: the latency kernels' instances and tile layouts
         (k == "no_tiled" ? t->sw.no_tiled : t->sw.no_fused_c) = on;
         return make_plan(t, t->forced_variant ? t->var->id : -1);

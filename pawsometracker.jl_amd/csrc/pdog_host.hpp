@@ -9,9 +9,9 @@
 // raise_lds_limit is keyed on a kernel's address: a second translation unit that included one of those headers would get
 // private copies whose LDS limit was never raised.  So every include of a dog_*.hpp header of the tracker, every launch of
 // its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
-// this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip and
-// pawsome_exclusive.hip launch their own kernels, dog_diag.hpp's, group_compact_kernel, dog_peaks.hpp's and dog_assign.hpp's,
-// which no other unit names.)  The one exception is dog_step.hpp, which
+// this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip,
+// pawsome_exclusive.hip and pawsome_motion.hip launch their own kernels, dog_diag.hpp's, group_compact_kernel, dog_peaks.hpp's,
+// dog_assign.hpp's and dog_motion.hpp's, which no other unit names.)  The one exception is dog_step.hpp, which
 // pawsome_dog.hip and pawsome_clips.hip both include: its kernel uses no dynamic LDS, so no limit is ever raised for it and
 // a private copy per unit is harmless.
 #pragma once
@@ -40,6 +40,8 @@ double dog_kernel_norm_up(const std::vector<double> &gp, const std::vector<doubl
 int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, int n_clips, int n_frames, int32_t *out_len, int *max_len);
 // What the entry points of include/pawsome_exclusive.h refuse alike: sizes outside their ranges, a ratio outside [0, 1] or NaN.
 int check_exclusive(const char *who, int n_groups, int n_targets, int k, double min_ratio);
+// What the entry points of include/pawsome_motion.h refuse beyond that: a min_response that is negative, NaN or infinite, coast < 0.
+int check_motion(const char *who, double min_response, int coast);
 // The test the entry points share for a stack of frames (and `counts_ok`: the entry point's own sizes); PDOG_E_ARG in `who`'s name.
 // Accepted layouts (include/pawsome_dog.h, "frame layouts"): rows fw … PDOG_MAX_ROW_STRIDE bytes apart, any non-negative
 // frame stride (overlapping frames and 0 included), any base address.
@@ -196,6 +198,19 @@ struct ExclusiveState {
     uint64_t steps = 0, grown = 0;  // pdog_get_exclusive_counts
 };
 ExclusiveState *exclusive_state(pdog_tracker *t);
+
+// The same for the motion step and walk (pawsome_motion.hip, its own unit and kernels); motion_state (pawsome_dog.hip).
+struct MotionState {
+    bool lds = false;               // pdog_set_tuning "motion_lds": the kernel stages the lists in LDS (dog_motion.hpp)
+    int device = 0;
+    DeviceBuffer<int32_t> d_words;  // per window: the position [n][2], the guess [n][2], the walk's own mstate [n][4], the picks [n][k][2], the counts [n]
+    DeviceBuffer<float> d_peak;     // [n][k] the picks' values
+    StagedUpload<int32_t> table;    // as ExclusiveState's
+    std::vector<int32_t> len;
+    size_t table_words = 0;
+    uint64_t steps = 0, grown = 0;  // pdog_get_motion_counts
+};
+MotionState *motion_state(pdog_tracker *t);
 
 } // namespace pdog
 #pragma GCC visibility pop

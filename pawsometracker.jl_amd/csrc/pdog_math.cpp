@@ -3,7 +3,9 @@
 // tile packer.  Plain C++: no HIP, no kernel header (pdog_host.hpp says why), so tools/asan_host.sh sanitises it alone.
 #include "pdog_host.hpp"
 #include "pdog_exclusive.hpp"
+#include "pdog_motion.hpp"
 #include "../../include/pawsome_exclusive.h"
+#include "../../include/pawsome_motion.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,6 +31,14 @@ int check_exclusive(const char *who, int n_groups, int n_targets, int k, double 
     if (n_targets < 1 || n_targets > exclusive::kMaxTargets) return fail(PDOG_E_ARG, std::string(who) + ": n_targets = " + std::to_string(n_targets) + " lies outside 1 ... 32");
     if (k < 1 || k > PDOG_PEAKS_MAX_K) return fail(PDOG_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " lies outside 1 ... 32");
     if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) return fail(PDOG_E_ARG, std::string(who) + ": min_ratio lies outside [0, 1]");
+    return PDOG_OK;
+}
+
+// What the motion step's entry points (include/pawsome_motion.h) refuse beyond check_exclusive.
+int check_motion(const char *who, double min_response, int coast)
+{
+    if (!(min_response >= 0.0 && min_response <= 3.4028234663852886e38)) return fail(PDOG_E_ARG, std::string(who) + ": min_response must be finite and not negative");
+    if (coast < 0) return fail(PDOG_E_ARG, std::string(who) + ": coast = " + std::to_string(coast) + " is negative");
     return PDOG_OK;
 }
 
@@ -367,6 +377,84 @@ int pdog_assign_exclusive_host(int n_groups, int n_targets, int k, int min_dista
             oij[2 * t] = pij[2 * best_q];
             oij[2 * t + 1] = pij[2 * best_q + 1];
             ost[t] = best_q + 1;
+        }
+    }
+    return PDOG_OK;
+}
+
+// ---- the motion step on the host (include/pawsome_motion.h): the rule round by round, as the header states it ----
+int pdog_assign_motion_host(int n_groups, int n_targets, int k, int min_distance, double min_ratio, double min_response, int coast,
+                            int frame_h, int frame_w, const int32_t *prev, int32_t *mstate, const int32_t *ij, const float *peak,
+                            const int32_t *count, int32_t *out_ij, int32_t *out_state, int32_t *next)
+{
+    using namespace pdog::motion;
+    const char *who = "pdog_assign_motion_host";
+    if (!prev || !mstate || !ij || !peak || !count || !out_ij || !out_state || !next) return fail(PDOG_E_ARG, std::string(who) + ": null pointer");
+    if (int rc = check_exclusive(who, n_groups, n_targets, k, min_ratio)) return rc;
+    if (int rc = check_motion(who, min_response, coast)) return rc;
+    if (min_distance < 1) return fail(PDOG_E_ARG, std::string(who) + ": min_distance must be given (>= 1)");
+    if (frame_h < 1 || frame_w < 1) return fail(PDOG_E_ARG, std::string(who) + ": the frame size must be given (>= 1 x 1)");
+    const int T = n_targets;
+    const long long d = min_distance;
+    const float rho = (float)min_ratio, m = (float)min_response;
+    for (int g = 0; g < n_groups; ++g) {
+        const size_t w0 = (size_t)g * T;
+        int ci[kMaxTargets] = {}, cj[kMaxTargets] = {}, ai[kMaxTargets] = {}, aj[kMaxTargets] = {}, st[kMaxTargets] = {};
+        for (int t = 0; t < T; ++t) { // 1: the predictions; held until a round says otherwise
+            ci[t] = predict(prev[2 * (w0 + t)], mstate[4 * (w0 + t)], frame_h);
+            cj[t] = predict(prev[2 * (w0 + t) + 1], mstate[4 * (w0 + t) + 1], frame_w);
+            st[t] = -1;
+        }
+        for (int round = 0; round < T; ++round) {
+            bool any = false;
+            uint32_t best_d = 0;
+            uint64_t best_key = 0;
+            int best_q = 0;
+            for (int t = 0; t < T; ++t) {
+                if (st[t] != -1) continue;
+                const int32_t *pij = ij + 2 * (w0 + t) * k;
+                const float *pk = peak + (w0 + t) * k;
+                bool has = false; // 4: the head, the free entry nearest to the prediction
+                uint32_t hd = 0;
+                int hq = 0;
+                for (int q = 0; q < k; ++q) {
+                    if (!admissible(q, count[w0 + t], pk[q], pk[0], m, rho)) continue;
+                    bool blocked = false;
+                    for (int u = 0; u < T && !blocked; ++u)
+                        blocked = st[u] != -1 && blocks(pij[2 * q], pij[2 * q + 1], ai[u], aj[u], d);
+                    if (blocked) continue;
+                    const uint32_t D = dist2(pij[2 * q], pij[2 * q + 1], ci[t], cj[t]);
+                    if (!has || D < hd) { has = true; hd = D; hq = q; }
+                }
+                if (!has) continue;
+                const uint64_t key = head_key(pk[hq], t); // 5: the smallest D, then the larger value, then the smaller t
+                if (!any || hd < best_d || (hd == best_d && key > best_key)) { any = true; best_d = hd; best_key = key; best_q = hq; }
+            }
+            if (!any) break;
+            const int t = key_target(best_key);
+            const int32_t *pij = ij + 2 * (w0 + t) * k;
+            ai[t] = pij[2 * best_q];
+            aj[t] = pij[2 * best_q + 1];
+            st[t] = best_q + 1;
+        }
+        for (int t = 0; t < T; ++t) { // 6 - 8
+            const size_t w = w0 + t;
+            Carry c = {mstate[4 * w], mstate[4 * w + 1], mstate[4 * w + 2]};
+            int oi = ci[t], oj = cj[t];
+            if (st[t] == -1) c = carry_held(c, coast);
+            else {
+                bool contested = false;
+                for (int u = 0; u < T; ++u) contested |= u != t && blocks(ai[t], aj[t], ci[u], cj[u], d);
+                c = carry_assigned(c, contested, prev[2 * w], prev[2 * w + 1], ai[t], aj[t]);
+                oi = ai[t];
+                oj = aj[t];
+            }
+            out_ij[2 * w] = oi;
+            out_ij[2 * w + 1] = oj;
+            out_state[w] = st[t];
+            next[2 * w] = predict(oi, c.vi, frame_h);
+            next[2 * w + 1] = predict(oj, c.vj, frame_w);
+            mstate[4 * w] = c.vi; mstate[4 * w + 1] = c.vj; mstate[4 * w + 2] = c.n_held; mstate[4 * w + 3] = 0;
         }
     }
     return PDOG_OK;

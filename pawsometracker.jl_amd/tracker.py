@@ -378,7 +378,7 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, exclusive=False, min_ratio=None):
+                min_distance=None, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -409,9 +409,16 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     response a second or later peak must reach to be taken, and `min_distance` (None: ceil(target_width)) the least distance
     between two peaks; at most 32 targets.  The result then gains a trailing `state`, int32 cuda [n_targets, m]: 0 for the
     bootstrap, the number of the pick a target was assigned (1: the functor's own answer), -1 where it was held.  Bootstrap,
-    subpixel, diagnostic and n_targets work on the positions as before.  ValueError for min_ratio without exclusive."""
+    subpixel, diagnostic and n_targets work on the positions as before.  ValueError for min_ratio without exclusive.
+    `motion` = True keeps the targets apart WITH A MOTION MODEL (this library's addition; include/pawsome_motion.h states the
+    rule): the loop is BatchTracker.detect_chains_motion over all targets as one group — every target's window is centred on
+    where its last uncontested displacement predicts it, the targets share out the peaks by nearness to their predictions,
+    and a target whose window offers nothing above `min_response` (None: 0.0) coasts along its velocity for `coast` steps
+    (None: 8) and then waits.  `min_distance` and `min_ratio` mean what they mean for `exclusive`, and the result gains the
+    same trailing `state` (-1: held, the position is the prediction).  ValueError for motion together with exclusive, and for
+    coast or min_response without motion."""
     import torch
-    from ._args import exclusive_args, peaks_args
+    from ._args import exclusive_args, motion_args, peaks_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
     if n_targets is not None:
@@ -419,15 +426,24 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             raise ValueError("n_targets finds the targets itself: give it, or start_locations, not both")
         n_targets, md = peaks_args(n_targets, min_distance, "n_targets")
         start_locations = [None] * n_targets
-    elif min_distance is not None and not exclusive:
+    elif min_distance is not None and not exclusive and motion is not True:
         raise ValueError("min_distance belongs to n_targets and exclusive")
     if not isinstance(exclusive, bool):
         raise TypeError("exclusive must be True or False")
-    if min_ratio is not None and not exclusive:
+    if not isinstance(motion, bool):
+        raise TypeError("motion must be True or False")
+    if motion and exclusive:
+        raise ValueError("motion and exclusive are two rules for one loop: give one of them")
+    if min_ratio is not None and not exclusive and not motion:
         raise ValueError("min_ratio belongs to exclusive")
-    if exclusive:
+    if (coast is not None or min_response is not None) and not motion:
+        raise ValueError("coast and min_response belong to motion")
+    if exclusive or motion:
         n_locs = len(start_locations) if isinstance(start_locations, list) else 1
         excl = exclusive_args(max(n_locs, 1), None, min_distance, 0.5 if min_ratio is None else min_ratio)
+    if motion:
+        excl = motion_args(max(n_locs, 1), None, min_distance, excl[2], 0.0 if min_response is None else min_response,
+                           8 if coast is None else coast)
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3):
         raise TypeError("frames must be a uint8 cuda tensor [n_frames, h, w]")
     n, h, w = (int(v) for v in frames.shape)
@@ -477,6 +493,10 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 out, state = bt.detect_chains_exclusive(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None,
                                                         excl[2], first=1)
                 out, state = out[0], state[0]
+            elif motion:
+                out, state, _ = bt.detect_chains_motion(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None,
+                                                        excl[2], excl[3], excl[4], first=1)
+                out, state = out[0], state[0]
             else:
                 out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
             sub = None
@@ -490,6 +510,6 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     dia.set_targets(nt)
                     _render_steps(dia, frames, table, out, chunk, diagnostic)
             res = (ts, out, sub) if subpixel else (ts, out)
-            return res + (state,) if exclusive else res
+            return res + (state,) if exclusive or motion else res
         finally:
             bt.close()
