@@ -51,9 +51,10 @@ def thresholds(tw, darker):
     return float(T), float(max(T, T_rescan))
 
 
-def prepass(tile, fill, tw, darker):
+def prepass(tile, fill, tw, darker, cell_darker=None):
     """tile: the window's padded tile.  Returns a dict: dc, V, E [slot][sub-chunk], the L block's origin, L, the exclusion
-    threshold on ΣE (−1: nothing excluded) and the hull per slot."""
+    threshold on ΣE (−1: nothing excluded) and the hull per slot.  cell_darker: the sign PruneGeo::darker gives the 3 × 3-cell
+    sums, by default the target's own; a test passes the other one to state what a kernel with that sign wrong would keep."""
     gp, gm, _, _ = fr.tap_tables(tw, darker)
     l, hw = len(gp), len(gp) // 2
     NA, TWin = tile.shape
@@ -71,7 +72,7 @@ def prepass(tile, fill, tw, darker):
     pad = np.zeros((nsub + 2, ncx + 2), np.int64)
     pad[1:-1, 1:-1] = cell
     s33 = sum(pad[1 + dy:1 + dy + nsub, 1 + dx:1 + dx + ncx] for dy in (-1, 0, 1) for dx in (-1, 0, 1))
-    if darker:
+    if darker if cell_darker is None else cell_darker:
         s33 = -s33
     cy, cx = divmod(int(np.argmax(s33)), ncx)                         # the first maximum in row-major cell order
     ny, nx = min(PB, n1), min(PB, n2)

@@ -57,8 +57,20 @@ CASES = _cases()
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_bound_lower_bound_and_hull(case):
+    _bound_lower_bound_and_hull(case, True)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_bound_lower_bound_and_hull_bright_sign(case):
+    """The same scenes read for bright targets (PruneGeo::darker = 0: the cell sums and the tap tables take the other sign): the
+    bound, L ≤ the maximum, the hull and the maximum's own block.  What the scenes say about pruning holds for their dark discs only."""
+    _bound_lower_bound_and_hull(case, False)
+
+
+def _bound_lower_bound_and_hull(case, darker):
     name, tw, ws, frame, fill, guess, prunes = case
-    darker = True
+    if not darker:
+        prunes = None
     l = fr.kernel_len(fr.sigma_of(tw))
     radii = (ws[0] // 2, ws[1] // 2)
     tile = fr.window_tile(frame, fill, l, radii, guess)
@@ -85,6 +97,9 @@ def test_bound_lower_bound_and_hull(case):
         near = np.argwhere(resp[:, c0:c0 + w].astype(np.float64) >= M - pp["Tmax"])
         for y, _ in near:
             assert 8 * ba <= y < 8 * bb, (name, s, int(y), (ba, bb))
+        my, mx = np.unravel_index(int(np.argmax(resp)), resp.shape)
+        if c0 <= mx < c0 + w:                       # the maximum's own block is kept
+            assert ba <= my // 8 < bb, (name, s, (int(my), int(mx)), (ba, bb))
     kept, total = pr.kept_pairs(pp, l)
     print(name, "kept", kept, "of", total, "L", pp["L"], "max", M)
     if prunes is True:
