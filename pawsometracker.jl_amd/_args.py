@@ -107,6 +107,12 @@ def motion_args(n_targets, k, min_distance, min_ratio, min_response, coast):
     return k, md, rho, float(min_response), int(coast)
 
 
+def predict_args(min_response, coast):
+    """What the predicted chain takes beside its arrays: min_response and coast as motion_args judges them.  Returns
+    (min_response, coast) as the library takes them."""
+    return motion_args(1, 1, None, 1.0, min_response, coast)[3:]
+
+
 def host_table(v, name):
     """A frame table — a sequence of rows, a numpy array or a tensor of integers [n_clips, n_steps] — as a contiguous host int32
     array.  Its entries are the library's to judge (it validates them before it launches anything)."""

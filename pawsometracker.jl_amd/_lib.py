@@ -147,6 +147,14 @@ MOTION_PROTOTYPES = {
 }
 MOTION_SYMBOLS = tuple(MOTION_PROTOTYPES)
 MOTION_MAX_TARGETS = 32      # PDOG_MOTION_MAX_TARGETS
+
+# the same for include/pawsome_predict.h, which includes pawsome_motion.h: one-launch chains with a motion model
+# (tests/test_predict_cpu.py holds this table against that header)
+PREDICT_PROTOTYPES = {
+    "pdog_detect_chains_predicted": (_i, [_p, _p, _i64, _i64, _i, _p, _i, _i, _i, _d, _i, _p, _p, _p, _p]),
+    "pdog_get_predict_counts": (_i, [_p, _pu64]),
+}
+PREDICT_SYMBOLS = tuple(PREDICT_PROTOTYPES)
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -192,7 +200,7 @@ def lib():
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
-                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES}.items():
+                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -292,6 +300,13 @@ class TrackerHandle(Handle):
         out = (C.c_uint64 * 2)()
         check(lib().pdog_get_motion_counts(self._h, out))
         return int(out[0]), int(out[1])
+
+    def predict_counts(self):
+        """(launches of the fused kernel's predicted instances, of the persistent chain kernel's, walks handed to the motion
+        walk, times the staged table grew) — pdog_get_predict_counts."""
+        out = (C.c_uint64 * 4)()
+        check(lib().pdog_get_predict_counts(self._h, out))
+        return tuple(int(v) for v in out)
 
     def batch_maxima(self, n):
         """Test hook (not stable ABI): FP32 maxima of the n windows of the last strip-kernel batch (numpy float32 [n]) — pdog_get_batch_maxima."""

@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args
+from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args, predict_args
 
 
 class BatchTracker(_lib.TrackerHandle):
@@ -280,6 +280,36 @@ class BatchTracker(_lib.TrackerHandle):
         _lib.check(_lib.lib().pdog_detect_chains_motion(
             self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
             C.c_void_p(table.ctypes.data), ns, ng, nt, int(first), k, md, rho, m, coast, C.c_void_p(starts.data_ptr()),
+            C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
+        return out, state, mstate
+
+    def detect_chains_predicted(self, frames, frame_table, starts, min_response=0.0, coast=8, mstate=None, first=0):
+        """Independent chains with a motion model over a frame table, in one launch where detect_chains_indexed is one launch
+        (pdog_detect_chains_predicted; this library's addition, the rule is stated in include/pawsome_predict.h): frames,
+        frame_table, starts int32 cuda [n_clips, 2] and first as for detect_chains_indexed.  Per step a clip's window is
+        centred on its prediction clamp(p + v); a window whose FP32 maximum does not exceed min_response HOLDS the clip, which
+        then coasts along v for `coast` steps and waits.  mstate None: every clip starts at rest; otherwise int32 cuda
+        [n_clips, 4], (v_row, v_col, n_held, 0), the state a former call returned — it is updated in place, and a walk continued
+        from a call's last positions and its mstate equals the one-call walk.  Returns (indices int32 cuda [n_clips, n_steps, 2],
+        state int32 cuda [n_clips, n_steps] — 1 assigned, -1 held, 0 the start filed by first = 1 —, mstate); steps at and beyond
+        a clip's end are not written (both are zeroed)."""
+        import torch
+        self.use_torch_stream()
+        table = host_table(frame_table, "frame_table")
+        nc, ns = table.shape
+        m, coast = predict_args(min_response, coast)
+        if isinstance(first, bool) or first not in (0, 1):
+            raise ValueError(f"first: {first!r} is neither 0 nor 1")
+        device_frames(frames, "frames", 3, self._hw)
+        device_array(starts, "starts", torch.int32, (nc, 2))
+        if mstate is None:
+            mstate = torch.zeros((nc, 4), dtype=torch.int32, device=frames.device)
+        device_array(mstate, "mstate", torch.int32, (nc, 4))
+        out = torch.zeros((nc, ns, 2), dtype=torch.int32, device=frames.device)
+        state = torch.zeros((nc, ns), dtype=torch.int32, device=frames.device)
+        _lib.check(_lib.lib().pdog_detect_chains_predicted(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
+            C.c_void_p(table.ctypes.data), ns, nc, int(first), m, coast, C.c_void_p(starts.data_ptr()),
             C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
         return out, state, mstate
 

@@ -40,6 +40,9 @@ struct FusedGeo {
                            // itself: no sample loads, no reduction barrier); −1: sampled here
 };
 struct FusedTableGeo : FusedGeo { ClipTable tab; }; // clips over a frame table (dog_roll.hpp): n clips of up to chain_len steps
+struct FusedPredictGeo : FusedTableGeo { PredictCtl pred; }; // … walked as predicted chains (dog_roll.hpp, include/pawsome_predict.h)
+template <bool TABLE, bool PRED>
+using fused_geo_t = std::conditional_t<PRED, FusedPredictGeo, std::conditional_t<TABLE, FusedTableGeo, FusedGeo>>;
 
 constexpr int FUSED_NT = 1024, FUSED_PMAX = 8, FUSED_U = 8;
 
@@ -205,10 +208,16 @@ __device__ __forceinline__ void fusedc_col_task(const f2 *a, tap_ptr taps, f2 (&
 // in 100 MHz ticks) instead of the response.
 // TABLE: the instances that walk a frame table.  A template flag and a kernel argument of their own, not a run-time branch:
 // with the branch every instance spilled 8 … 27 more SGPRs, and the existing launches must compile as they did.
-template <bool RESP, int DIAG = 0, int LT = 0, bool TABLE = false>
-__global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditional_t<TABLE, FusedTableGeo, FusedGeo> fg,
+// PRED: the TABLE instances of the predicted chain (include/pawsome_predict.h), again a flag and an argument of their own.
+// Thread 0 — the lane that files the position — keeps the clip's p, v and n_held in LDS beside s_guess, initialises them for
+// every clip the workgroup walks, and applies pdog_predict.hpp's step: s_guess is then the PREDICTION the next window is centred
+// on.  A held frame's position is not used, so a held frame is never refined: g.ex.stat does not count it, and a lost target
+// does not pay exact mode's Float64 refinement on every flat frame.
+template <bool RESP, int DIAG = 0, int LT = 0, bool TABLE = false, bool PRED = false>
+__global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const fused_geo_t<TABLE, PRED> fg,
                                                              const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
+    static_assert(TABLE || !PRED, "the predicted chain walks a frame table");
     const LaunchGeo &g = fg.g;
     constexpr int NT = FUSED_NT, NW = NT / 64, U = FUSED_U;
     const int L = LT ? LT : g.L, hw = L >> 1, NA = fg.NA;
@@ -224,6 +233,11 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditio
     __shared__ float s_vmax[NW]; // a flagged frame: max |pixel − dc| over the tile, per wave
     __shared__ float s_max, s_sec2;
     __shared__ int s_idx2;
+    int *walk = nullptr; // PRED, thread 0 only: the clip's p (2), v (2), n_held
+    if constexpr (PRED) {
+        __shared__ int s_walk[5];
+        walk = s_walk;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b = blockIdx.x; // this workgroup's window (or clip): b, b + gridDim.x, … — the host launches no more workgroups than stay resident
     const tap_ptr trow = as_taps(taps_row), tcol = as_taps(taps_col);
@@ -259,6 +273,16 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditio
             fg.out_ij[2 * (long long)b * fg.chain_len] = g1;
             fg.out_ij[2 * (long long)b * fg.chain_len + 1] = g2;
         }
+    }
+    if constexpr (PRED) { // this clip's carry: from its mstate or at rest, whatever the workgroup's last clip left behind
+        const int32_t *ms = fg.pred.mstate ? fg.pred.mstate + 4 * (long long)b : nullptr;
+        const int vi = ms ? ms[0] : 0, vj = ms ? ms[1] : 0, nh = ms ? ms[2] : 0;
+        if (tid == 0) {
+            walk[0] = g1; walk[1] = g2; walk[2] = vi; walk[3] = vj; walk[4] = nh; // p is the start as given
+            if (k_first && len >= 1) fg.pred.out_state[(long long)b * fg.chain_len] = 0;
+        }
+        g1 = predict::predict(g1, vi, g.fh); // the first window is centred on clamp(start + v)
+        g2 = predict::predict(g2, vj, g.fw);
     }
     for (int k = k_first; k < (TABLE ? len : fg.chain_len); ++k) { // (len: TABLE instances only — the plain ones read fg.chain_len where they did)
         const long long fidx = TABLE ? (long long)table[k] : fg.chain_len > 1 ? (long long)b * fg.chain_len + k : (g.frame_index ? g.frame_index[b] : b);
@@ -495,6 +519,24 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditio
         stamp(6);
         const bool publish = fg.done_flag && b == 0 && (fg.progress || k == (TABLE ? len : fg.chain_len) - 1);
         int32_t *const o_ij = fg.out_ij + 2 * ((long long)b * fg.chain_len + k);
+        // PRED, thread 0: one step of the rule on this frame, whose window was centred on the prediction (g1, g2) — files position
+        // and state, after the clip's last step the state it ends in, and publishes the next prediction as the next guess
+        auto file_predicted = [&](bool hit, int qi, int qj) {
+            if constexpr (PRED) {
+                predict::Walk w{walk[0], walk[1], {walk[2], walk[3], walk[4]}};
+                const predict::Filed f = predict::step(w, hit, g1, g2, qi, qj, fg.pred.coast, g.fh, g.fw);
+                o_ij[0] = f.i;
+                o_ij[1] = f.j;
+                fg.pred.out_state[(long long)b * fg.chain_len + k] = f.state;
+                s_guess[0] = f.gi;
+                s_guess[1] = f.gj;
+                walk[0] = w.pi; walk[1] = w.pj; walk[2] = w.c.vi; walk[3] = w.c.vj; walk[4] = w.c.n_held;
+                if (k == len - 1 && fg.pred.mstate) {
+                    int32_t *ms = fg.pred.mstate + 4 * (long long)b;
+                    ms[0] = w.c.vi; ms[1] = w.c.vj; ms[2] = w.c.n_held; ms[3] = 0;
+                }
+            }
+        };
         if (wave == 0) { // the 16 wave peaks: lanes 0..15 of wave 0, same tie rule
             peak_init(pk);
             if (lane < NW) { pk.best = s_val[lane]; pk.idx = s_idx[lane]; pk.second = s_sec[lane]; }
@@ -505,13 +547,20 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditio
                 const int x = (int)(((float)pk.idx + 0.5f) * (1.0f / (float)g.n1)), y = pk.idx - x * g.n1;
                 const int i = min(max(g1 - g.r1 + y, 1), g.fh);   // :60-61
                 const int j = min(max(g2 - g.r2 + x, 1), g.fw);
-                o_ij[0] = i;
-                o_ij[1] = j;
-                s_guess[0] = i;
-                s_guess[1] = j;
+                if constexpr (!PRED) {
+                    o_ij[0] = i;
+                    o_ij[1] = j;
+                    s_guess[0] = i;
+                    s_guess[1] = j;
+                }
                 if (k == k_first) range_check(g.ex, g1, g2, hw, g.fh, g.fw);
                 // exact mode (dog_exact.hpp): a runner-up within 2δ of the maximum → the reference's own arithmetic decides
-                const bool rf = fg.rp && (pk.best - pk.second <= g.ex.T);
+                bool rf = fg.rp && (pk.best - pk.second <= g.ex.T);
+                if constexpr (PRED) { // a held frame is filed at once and never refined; a near-tie once it has been decided
+                    const bool hit = predict::assigned(pk.best, fg.pred.m);
+                    rf = rf && hit;
+                    if (!rf) file_predicted(hit, i, j);
+                }
                 s_refine = rf;
                 s_max = pk.best;
                 s_sec2 = pk.second;
@@ -554,6 +603,13 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditio
             for (int w = 0; w < NW; ++w) vm = fmaxf(vm, s_vmax[w]);
             vknown = (int)vm;
             refine = s_max - s_sec2 <= g.ex.T * (vm * (1.0f / 255.0f)) * 1.00001f;
+            if constexpr (PRED) { // withdrawn: the FP32 answer stands and is filed now; everyone reads s_guess behind the barrier
+                if (!refine && tid == 0) {
+                    const int x = (int)(((float)s_idx2 + 0.5f) * (1.0f / (float)g.n1)), y = s_idx2 - x * g.n1;
+                    file_predicted(true, min(max(g1 - g.r1 + y, 1), g.fh), min(max(g2 - g.r2 + x, 1), g.fw));
+                }
+                __syncthreads();
+            }
             if (!refine && tid == 0 && publish) // withdrawn: the FP32 answer (already written) stands
                 __hip_atomic_store(fg.done_flag, fg.progress ? k + 1 : fg.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
@@ -587,10 +643,14 @@ __global__ __launch_bounds__(FUSED_NT) void dog_fused_kernel(const std::conditio
                 const int x = idx / g.n1, y = idx - x * g.n1;
                 const int i = min(max(g1 - g.r1 + y, 1), g.fh);
                 const int j = min(max(g2 - g.r2 + x, 1), g.fw);
-                o_ij[0] = i;
-                o_ij[1] = j;
-                s_guess[0] = i;
-                s_guess[1] = j;
+                if constexpr (PRED) {
+                    file_predicted(true, i, j);
+                } else {
+                    o_ij[0] = i;
+                    o_ij[1] = j;
+                    s_guess[0] = i;
+                    s_guess[1] = j;
+                }
                 if (publish)
                     __hip_atomic_store(fg.done_flag, fg.progress ? k + 1 : fg.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }

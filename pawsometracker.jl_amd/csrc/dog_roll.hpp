@@ -54,6 +54,7 @@
 #pragma once
 #include "dog_kernels.hpp"
 #include "dog_exact.hpp"
+#include "pdog_predict.hpp"
 #include <type_traits>
 
 namespace pdog {
@@ -688,13 +689,28 @@ struct ClipTable {
     int first;            // 1: row 0 of a clip that has one receives its start guess as given, the loop begins at step 1 (:104, :161)
 };
 struct ChainTableGeo : ChainGeo { ClipTable tab; };
+// The predicted chain (include/pawsome_predict.h): what the lane that files a clip's positions needs beside the table.
+struct PredictCtl {
+    float m;            // (float)min_response: a frame whose FP32 maximum does not exceed it is HELD
+    int coast;          // held steps a clip keeps its velocity for
+    int32_t *out_state; // [n_clips][n_steps]: 1 assigned, -1 held (0: the start filed as given, first = 1)
+    int32_t *mstate;    // [n_clips][4] in (v_row, v_col, n_held, -), out after a clip's last step (word 3 = 0); null: at rest, dropped
+};
+struct ChainPredictGeo : ChainTableGeo { PredictCtl pred; };
+template <bool TABLE, bool PRED>
+using chain_geo_t = std::conditional_t<PRED, ChainPredictGeo, std::conditional_t<TABLE, ChainTableGeo, ChainGeo>>;
 // TABLE: the instances that walk a frame table.  A template flag and a kernel argument of their own, not a run-time branch
 // on a wider ChainGeo: the existing instances compile exactly as before (the branch cost them SGPR spills, the wider
 // argument 16 bytes of scratch).
-template <int LT, bool TABLE = false>
-__global__ __launch_bounds__(512) void dog_chain_kernel(const std::conditional_t<TABLE, ChainTableGeo, ChainGeo> cg,
+// PRED: the TABLE instances of the predicted chain — again a flag and an argument of their own.  Thread 0, which files the
+// position, carries the clip's p, v and n_held in LDS beside `cur` and applies pdog_predict.hpp's step: `cur` is then the
+// PREDICTION the next window is centred on.  A held frame's position is not used, so a held frame is never refined and
+// g.ex.stat does not count it.
+template <int LT, bool TABLE = false, bool PRED = false>
+__global__ __launch_bounds__(512) void dog_chain_kernel(const chain_geo_t<TABLE, PRED> cg,
                                                         const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
+    static_assert(TABLE || !PRED, "the predicted chain walks a frame table");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int cur[2];
     __shared__ float pv[8], ps[8];
@@ -713,7 +729,44 @@ __global__ __launch_bounds__(512) void dog_chain_kernel(const std::conditional_t
         len = cg.tab.len[c_];
         k_first = cg.tab.first;
     }
-    if (tid == 0) {
+    int *walk = nullptr; // PRED, thread 0 only: p (2), v (2), n_held
+    if constexpr (PRED) {
+        __shared__ int s_walk[5];
+        walk = s_walk;
+    }
+    // PRED, thread 0: one step of the rule on the frame at prediction (ci, cj) — files position and state, after the clip's
+    // last step the state it ends in, and makes the next prediction the current guess
+    auto file_predicted = [&](int k, bool hit, int ci, int cj, int qi, int qj) {
+        if constexpr (PRED) {
+            predict::Walk w{walk[0], walk[1], {walk[2], walk[3], walk[4]}};
+            const predict::Filed f = predict::step(w, hit, ci, cj, qi, qj, cg.pred.coast, g.fh, g.fw);
+            const long long o = (long long)c_ * cg.n_frames + k;
+            cg.out_ij[2 * o] = f.i; cg.out_ij[2 * o + 1] = f.j;
+            cg.pred.out_state[o] = f.state;
+            cur[0] = f.gi; cur[1] = f.gj;
+            walk[0] = w.pi; walk[1] = w.pj; walk[2] = w.c.vi; walk[3] = w.c.vj; walk[4] = w.c.n_held;
+            if (k == len - 1 && cg.pred.mstate) {
+                int32_t *ms = cg.pred.mstate + 4 * (long long)c_;
+                ms[0] = w.c.vi; ms[1] = w.c.vj; ms[2] = w.c.n_held; ms[3] = 0;
+            }
+        }
+    };
+    if constexpr (PRED) {
+        if (tid == 0) {
+            const int si = cg.start[2 * c_], sj = cg.start[2 * c_ + 1];
+            const int32_t *ms = cg.pred.mstate ? cg.pred.mstate + 4 * (long long)c_ : nullptr;
+            walk[0] = si; walk[1] = sj;
+            walk[2] = ms ? ms[0] : 0; walk[3] = ms ? ms[1] : 0; walk[4] = ms ? ms[2] : 0;
+            cur[0] = predict::predict(si, walk[2], g.fh); // the first window is centred on clamp(start + v)
+            cur[1] = predict::predict(sj, walk[3], g.fw);
+            if (len > k_first) range_check(g.ex, cur[0], cur[1], LT / 2, g.fh, g.fw);
+            if (k_first && len >= 1) { // the start, stored as given, with state 0
+                cg.out_ij[2 * (long long)c_ * cg.n_frames] = si;
+                cg.out_ij[2 * (long long)c_ * cg.n_frames + 1] = sj;
+                cg.pred.out_state[(long long)c_ * cg.n_frames] = 0;
+            }
+        }
+    } else if (tid == 0) {
         cur[0] = cg.start[2 * c_];
         cur[1] = cg.start[2 * c_ + 1];
         if (!TABLE || len > k_first) range_check(g.ex, cur[0], cur[1], LT / 2, g.fh, g.fw); // (a start that no step uses raises nothing)
@@ -739,10 +792,16 @@ __global__ __launch_bounds__(512) void dog_chain_kernel(const std::conditional_t
             const int x = w.idx / g.n1, y = w.idx - x * g.n1;
             const int i = min(max(g1 - g.r1 + y, 1), g.fh);   // :60-61
             const int j = min(max(g2 - g.r2 + x, 1), g.fw);
-            int *o = cg.out_ij + 2 * ((long long)c_ * cg.n_frames + k);
-            o[0] = i; o[1] = j;
-            cur[0] = i; cur[1] = j;
-            s_refine = cg.rp && (w.best - w.second <= g.ex.T);
+            if constexpr (PRED) {
+                const bool hit = predict::assigned(w.best, cg.pred.m);
+                s_refine = hit && cg.rp && (w.best - w.second <= g.ex.T);
+                if (!s_refine) file_predicted(k, hit, g1, g2, i, j); // (a near-tie is filed once the refinement has decided)
+            } else {
+                int *o = cg.out_ij + 2 * ((long long)c_ * cg.n_frames + k);
+                o[0] = i; o[1] = j;
+                cur[0] = i; cur[1] = j;
+                s_refine = cg.rp && (w.best - w.second <= g.ex.T);
+            }
             s_max = w.best;
             s_sec2 = w.second;
             s_idx2 = w.idx;
@@ -780,9 +839,13 @@ __global__ __launch_bounds__(512) void dog_chain_kernel(const std::conditional_t
                 const int x = idx / g.n1, y = idx - x * g.n1;
                 const int i = min(max(g1 - g.r1 + y, 1), g.fh);
                 const int j = min(max(g2 - g.r2 + x, 1), g.fw);
-                int *o = cg.out_ij + 2 * ((long long)c_ * cg.n_frames + k);
-                o[0] = i; o[1] = j;
-                cur[0] = i; cur[1] = j;
+                if constexpr (PRED) {
+                    file_predicted(k, true, g1, g2, i, j);
+                } else {
+                    int *o = cg.out_ij + 2 * ((long long)c_ * cg.n_frames + k);
+                    o[0] = i; o[1] = j;
+                    cur[0] = i; cur[1] = j;
+                }
             }
             __syncthreads();
         }

@@ -14,4 +14,6 @@ template __global__ void dog_tiled_kernel<true, PDOG_LAT_L>(const TiledGeo, cons
 // chains over a frame table (no response map: a chain has none)
 template __global__ void dog_fused_kernel<false, 0, PDOG_LAT_L, true>(const FusedTableGeo, const f2 *, const f2 *);
 template __global__ void dog_tiled_kernel<false, PDOG_LAT_L, true>(const TiledTableGeo, const f2 *, const f2 *);
+// the predicted chain over a frame table (include/pawsome_predict.h)
+template __global__ void dog_fused_kernel<false, 0, PDOG_LAT_L, true, true>(const FusedPredictGeo, const f2 *, const f2 *);
 } // namespace pdog

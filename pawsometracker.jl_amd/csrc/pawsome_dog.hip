@@ -42,7 +42,8 @@ namespace pdog {
     extern template __global__ void dog_tiled_kernel<false, LT>(const TiledGeo, const f2 *, const f2 *);       \
     extern template __global__ void dog_tiled_kernel<true, LT>(const TiledGeo, const f2 *, const f2 *);        \
     extern template __global__ void dog_fused_kernel<false, 0, LT, true>(const FusedTableGeo, const f2 *, const f2 *); \
-    extern template __global__ void dog_tiled_kernel<false, LT, true>(const TiledTableGeo, const f2 *, const f2 *);
+    extern template __global__ void dog_tiled_kernel<false, LT, true>(const TiledTableGeo, const f2 *, const f2 *); \
+    extern template __global__ void dog_fused_kernel<false, 0, LT, true, true>(const FusedPredictGeo, const f2 *, const f2 *);
 #include "lat_lengths.def"
 #undef PDOG_LAT_L
 } // namespace pdog
@@ -56,7 +57,8 @@ namespace pdog {
     extern template __global__ void dog_thin_kernel<LT, false>(const LaunchGeo, const f2 *, const f2 *);         \
     extern template __global__ void dog_thin_kernel<LT, true>(const LaunchGeo, const f2 *, const f2 *);          \
     extern template __global__ void dog_chain_kernel<LT>(const ChainGeo, const f2 *, const f2 *);                \
-    extern template __global__ void dog_chain_kernel<LT, true>(const ChainTableGeo, const f2 *, const f2 *);
+    extern template __global__ void dog_chain_kernel<LT, true>(const ChainTableGeo, const f2 *, const f2 *);    \
+    extern template __global__ void dog_chain_kernel<LT, true, true>(const ChainPredictGeo, const f2 *, const f2 *);
 #include "roll_lengths.def"
 #undef PDOG_ROLL_L
 #define PDOG_EPI_CLASSES(X) X(10) X(2) X(16) X(14) X(6) X(4) X(0) X(1) X(3) X(5) X(7) X(8) X(9) X(11) X(12) X(13) X(15) X(17) // roll_inst.hip: every window-height class
@@ -181,6 +183,8 @@ struct Variant {
     chain_table_fn chain_table = nullptr; // … its instance that walks a frame table
     bool fused = false;        // dog_fused.hpp: one workgroup per window, whole tile in LDS
     kernel_fn fn_prune = nullptr; // the roll instance that honours kept ranges (dog_prune.hpp)
+    typedef void (*chain_predict_fn)(const ChainPredictGeo, const f2 *, const f2 *);
+    chain_predict_fn chain_predict = nullptr; // the chain kernel's instance that walks a table as predicted chains
     int tw() const { return P * XG; }
     int ring(int L) const { return LT ? ring_rows(CH, LT, Q) : ring_rows(CH, L, Q); }
     int pa(int L) const { return pitch_a(tw() + L - 1); }
@@ -198,7 +202,7 @@ struct Variant {
     Variant { id, ROLL_P, ROLL_TW / ROLL_P, ROLL_CH, ROLL_CH, LT, 64, (kernel_fn)dog_roll_kernel<LT, false>, \
               (kernel_fn)dog_roll_kernel<LT, true>, true, (kernel_fn)dog_thin_kernel<LT, false>, \
               (kernel_fn)dog_thin_kernel<LT, true>, 0, dog_chain_kernel<LT>, dog_chain_kernel<LT, true>, false, \
-              (kernel_fn)dog_roll_kernel<LT, false, 0, -1, true> }
+              (kernel_fn)dog_roll_kernel<LT, false, 0, -1, true>, dog_chain_kernel<LT, true, true> }
 
 const Variant kVariants[] = {
     // runtime-L (any target_width)
@@ -366,6 +370,7 @@ struct pdog_tracker {
     pdog::PeaksState peaks; // pdog_detect_peaks (pawsome_peaks.hip): its scratch, switch and counters
     pdog::ExclusiveState exclusive; // the exclusive step and walk (pawsome_exclusive.hip): their scratch and counters
     pdog::MotionState motion;       // the motion step and walk (pawsome_motion.hip): their scratch, switch and counters
+    pdog::PredictState predict;     // the predicted chain (pawsome_predict.hip): its table lengths and counters
 
     // Drains and destroys the streams and events; the buffers free themselves after that.
     ~pdog_tracker()
@@ -402,6 +407,12 @@ pdog::MotionState *pdog::motion_state(pdog_tracker *t)
     return &t->motion;
 }
 
+pdog::PredictState *pdog::predict_state(pdog_tracker *t)
+{
+    t->predict.device = t->device;
+    return &t->predict;
+}
+
 namespace {
 
 // The instances of the latency kernels (dog_fused.hpp, dog_tiled.hpp): a row per compile-time length of lat_lengths.def, then
@@ -409,12 +420,14 @@ namespace {
 // map, and the one that walks a frame table (no response map: a chain has none).
 typedef void (*fused_fn_t)(const FusedGeo, const f2 *, const f2 *);
 typedef void (*fused_table_fn_t)(const FusedTableGeo, const f2 *, const f2 *);
+typedef void (*fused_predict_fn_t)(const FusedPredictGeo, const f2 *, const f2 *);
 typedef void (*tiled_fn_t)(const TiledGeo, const f2 *, const f2 *);
 enum { kLatPlain, kLatResp, kLatTable };
-struct LatInstances { int L; const void *fused[3], *tiled[3]; };
+struct LatInstances { int L; const void *fused[3], *tiled[3]; fused_predict_fn_t fused_predict; }; // fused_predict: the table instance of the predicted chain
 #define PDOG_LAT_L(LT)                                                                                                                \
     { LT, {(const void *)dog_fused_kernel<false, 0, LT>, (const void *)dog_fused_kernel<true, 0, LT>, (const void *)dog_fused_kernel<false, 0, LT, true>}, \
-          {(const void *)dog_tiled_kernel<false, LT>, (const void *)dog_tiled_kernel<true, LT>, (const void *)dog_tiled_kernel<false, LT, true>} },
+          {(const void *)dog_tiled_kernel<false, LT>, (const void *)dog_tiled_kernel<true, LT>, (const void *)dog_tiled_kernel<false, LT, true>}, \
+          dog_fused_kernel<false, 0, LT, true, true> },
 const LatInstances kLatInstances[] = {
 #include "lat_lengths.def"
     PDOG_LAT_L(0)
@@ -660,6 +673,7 @@ struct Request {
     int32_t done_value = 0;                // `progress`, with k + 1 after frame k of a chain
     bool progress = false;
     int dc_host = -1;                      // the window's DC level where the host already sampled it
+    const PredictCtl *predict = nullptr;   // chains over a table walked as predicted chains (launch_fused, launch_persistent)
 };
 
 // The LaunchGeo fields every path fills the same way; everything else is zero.  A path then sets what it uses: the
@@ -992,7 +1006,8 @@ int launch_fused(pdog_tracker *t, const Request &req)
 {
     const int n = req.n, chain_len = req.chain_len;
     FusedPlan &p = t->fused;
-    FusedTableGeo fg; // (a launch without a table takes its FusedGeo part)
+    FusedPredictGeo fg; // (a launch without a table takes its FusedGeo part, one without prediction its FusedTableGeo part)
+    fg.pred = req.predict ? *req.predict : PredictCtl{0.f, 0, nullptr, nullptr};
     fg.tab = req.table;
     fg.g = base_geo(t, req);
     LaunchGeo &g = fg.g;
@@ -1060,7 +1075,12 @@ int launch_fused(pdog_tracker *t, const Request &req)
         p.resident = per_cu * cus;
     }
     const dim3 grid(std::min(n, p.resident));
-    if (req.table.index) hipLaunchKernelGGL((fused_table_fn_t)fused_instances(t).fused[kLatTable], grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
+    if (req.predict) {
+        const fused_predict_fn_t fp = fused_instances(t).fused_predict;
+        if (int rc = raise_lds_limit((const void *)fp, lds)) return rc; // (here, not in make_plan: a tracker that never predicts sets nothing up)
+        hipLaunchKernelGGL(fp, grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
+    } else if (req.table.index)
+        hipLaunchKernelGGL((fused_table_fn_t)fused_instances(t).fused[kLatTable], grid, dim3(FUSED_NT), lds, t->stream, static_cast<const FusedTableGeo &>(fg), tr, tc);
     else hipLaunchKernelGGL(fn, grid, dim3(FUSED_NT), lds, t->stream, static_cast<const FusedGeo &>(fg), tr, tc);
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
@@ -2023,7 +2043,8 @@ int launch_persistent(pdog_tracker *t, const Request &req)
 {
     const Variant &v = *t->var;
     const int strips = chain_strips(t);
-    ChainTableGeo cg; // (a launch without a table takes its ChainGeo part)
+    ChainPredictGeo cg; // (a launch without a table takes its ChainGeo part, one without prediction its ChainTableGeo part)
+    cg.pred = req.predict ? *req.predict : PredictCtl{0.f, 0, nullptr, nullptr};
     cg.tab = req.table;
     cg.g = base_geo(t, req);
     LaunchGeo &g = cg.g;
@@ -2036,9 +2057,10 @@ int launch_persistent(pdog_tracker *t, const Request &req)
     // the strips' LDS doubles as the refinement's scratch
     const size_t lds = std::max((size_t)strips * roll_lds_bytes(v.LT), refine_lds_bytes(t->n1, t->L, 1, 8));
     fit_refine_scratch(t, lds, &cg.ref_cbw, &cg.ref_rows);
-    if (int rc = raise_lds_limit(req.table.index ? (const void *)v.chain_table : (const void *)v.chain, lds)) return rc;
+    if (int rc = raise_lds_limit(req.predict ? (const void *)v.chain_predict : req.table.index ? (const void *)v.chain_table : (const void *)v.chain, lds)) return rc;
     const f2 *tr = t->d_taps_row.get(), *troll = t->d_taps_roll.get();
-    if (req.table.index) hipLaunchKernelGGL(v.chain_table, dim3(req.n), dim3(64 * strips), lds, t->stream, cg, tr, troll);
+    if (req.predict) hipLaunchKernelGGL(v.chain_predict, dim3(req.n), dim3(64 * strips), lds, t->stream, cg, tr, troll);
+    else if (req.table.index) hipLaunchKernelGGL(v.chain_table, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainTableGeo &>(cg), tr, troll);
     else hipLaunchKernelGGL(v.chain, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainGeo &>(cg), tr, troll);
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
@@ -2195,6 +2217,33 @@ extern "C" int pdog_detect_chains_indexed(pdog_tracker *t, const uint8_t *d_fram
     clips.frames = d_frames; clips.frame_stride = frame_stride; clips.row_stride = row_stride;
     clips.guesses = d_start; clips.n = n_clips; clips.chain_len = n_steps; clips.out_ij = d_out_ij;
     return run_chains(t, clips, &ct);
+}
+
+// The predicted chain's one-launch paths (pdog_host.hpp; pawsome_predict.hip validated the walk).
+int pdog::launch_predicted(pdog_tracker *t, const PredictWalk &w, int *taken)
+{
+    *taken = 0;
+    const ChainPath path = chain_path(t, w.n_clips, w.n_steps, true, false);
+    if (path != ChainPath::Fused && !(path == ChainPath::Persistent && t->var->chain_predict)) return PDOG_OK;
+    HIP_TRY(hipSetDevice(t->device));
+    Request clips;
+    clips.frames = w.d_frames; clips.frame_stride = w.frame_stride; clips.row_stride = w.row_stride;
+    clips.guesses = w.d_start; clips.n = w.n_clips; clips.chain_len = w.n_steps; clips.out_ij = w.d_out_ij;
+    const size_t words = (size_t)w.n_clips * w.n_steps + (size_t)w.n_clips;
+    if (words > t->predict.table_words) { ++t->predict.grown; t->predict.table_words = words; }
+    const ChainTable ct{w.h_table, w.len, w.first, w.max_len};
+    if (int rc = upload_chain_table(t, ct, w.n_clips, w.n_steps, false, &clips.table.index, &clips.table.len)) return rc;
+    clips.table.first = w.first;
+    const PredictCtl pc{w.m, w.coast, w.d_out_state, w.d_mstate};
+    clips.predict = &pc;
+    if (path == ChainPath::Fused) {
+        ++t->predict.fused;
+        *taken = 1;
+        return launch_fused(t, clips);
+    }
+    ++t->predict.persistent;
+    *taken = 2;
+    return launch_persistent(t, clips);
 }
 
 extern "C" int pdog_detect_chain(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_stride, int64_t row_stride,

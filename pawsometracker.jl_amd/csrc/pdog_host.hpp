@@ -11,7 +11,8 @@
 // its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
 // this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip,
 // pawsome_exclusive.hip and pawsome_motion.hip launch their own kernels, dog_diag.hpp's, group_compact_kernel, dog_peaks.hpp's,
-// dog_assign.hpp's and dog_motion.hpp's, which no other unit names.)  The one exception is dog_step.hpp, which
+// dog_assign.hpp's and dog_motion.hpp's, which no other unit names; pawsome_predict.hip launches nothing itself: the predicted
+// chain's kernels are instances of the tracker's own, launched by launch_predicted in pawsome_dog.hip.)  The one exception is dog_step.hpp, which
 // pawsome_dog.hip and pawsome_clips.hip both include: its kernel uses no dynamic LDS, so no limit is ever raised for it and
 // a private copy per unit is harmless.
 #pragma once
@@ -211,6 +212,30 @@ struct MotionState {
     uint64_t steps = 0, grown = 0;  // pdog_get_motion_counts
 };
 MotionState *motion_state(pdog_tracker *t);
+
+// The predicted chain (include/pawsome_predict.h; pawsome_predict.hip holds its entry points).  Its one-launch kernels are
+// instances of the tracker's own chain kernels, so their launch stays in pawsome_dog.hip (see above): launch_predicted.
+struct PredictState {
+    int device = 0;
+    std::vector<int32_t> len;       // steps per clip of the table being served
+    size_t table_words = 0;         // the most words the staged table was asked for
+    uint64_t fused = 0, persistent = 0, fallback = 0, grown = 0; // pdog_get_predict_counts
+};
+PredictState *predict_state(pdog_tracker *t);
+// A validated walk (h_table's lengths in len, the longest max_len >= 1) on the kernel chain_path chooses.  *taken = 1: one
+// launch of the fused kernel's predicted instance; 2: of the persistent chain kernel's; 0: nothing was launched or staged — the
+// geometry is the tiled kernel's or the stepped walk's, or the kernel length has no instance — and the caller falls back.
+struct PredictWalk {
+    const uint8_t *d_frames;
+    int64_t frame_stride, row_stride;
+    const int32_t *h_table, *len;
+    int max_len, n_steps, n_clips, first;
+    float m;
+    int coast;
+    const int32_t *d_start;
+    int32_t *d_out_ij, *d_out_state, *d_mstate;
+};
+int launch_predicted(pdog_tracker *t, const PredictWalk &w, int *taken);
 
 } // namespace pdog
 #pragma GCC visibility pop

@@ -14,7 +14,8 @@ namespace pdog {
     template __global__ void dog_thin_kernel<LT, false>(const LaunchGeo, const f2 *, const f2 *);         \
     template __global__ void dog_thin_kernel<LT, true>(const LaunchGeo, const f2 *, const f2 *);          \
     template __global__ void dog_chain_kernel<LT>(const ChainGeo, const f2 *, const f2 *);                \
-    template __global__ void dog_chain_kernel<LT, true>(const ChainTableGeo, const f2 *, const f2 *);
+    template __global__ void dog_chain_kernel<LT, true>(const ChainTableGeo, const f2 *, const f2 *);    \
+    template __global__ void dog_chain_kernel<LT, true, true>(const ChainPredictGeo, const f2 *, const f2 *);
 #include "roll_lengths.def"
 #undef PDOG_ROLL_L
 // l = 65 (target_width 25, the reference default) for EVERY window-height class (roll_epi_class = ((n1 + 2) ÷ 4) mod 18):

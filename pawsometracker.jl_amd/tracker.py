@@ -378,7 +378,7 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
+                min_distance=None, predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -416,9 +416,15 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     and a target whose window offers nothing above `min_response` (None: 0.0) coasts along its velocity for `coast` steps
     (None: 8) and then waits.  `min_distance` and `min_ratio` mean what they mean for `exclusive`, and the result gains the
     same trailing `state` (-1: held, the position is the prediction).  ValueError for motion together with exclusive, and for
-    coast or min_response without motion."""
+    coast or min_response without motion or predict.
+    `predict` = True gives every target an INDEPENDENT chain with the same motion model (this library's addition;
+    include/pawsome_predict.h states the rule): the loop is BatchTracker.detect_chains_predicted, one launch for all targets
+    where the plain loop is one launch — every target's window is centred on where its last displacement predicts it, and a
+    target whose window offers nothing above `min_response` (None: 0.0) coasts for `coast` steps (None: 8) and then waits.
+    Nothing keeps two targets apart.  The result gains the trailing `state`: 0 for the bootstrap, 1 assigned, -1 held.
+    ValueError for predict together with motion or exclusive."""
     import torch
-    from ._args import exclusive_args, motion_args, peaks_args
+    from ._args import exclusive_args, motion_args, peaks_args, predict_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
     if n_targets is not None:
@@ -432,12 +438,18 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
         raise TypeError("exclusive must be True or False")
     if not isinstance(motion, bool):
         raise TypeError("motion must be True or False")
+    if not isinstance(predict, bool):
+        raise TypeError("predict must be True or False")
+    if predict and (motion or exclusive):
+        raise ValueError("predict walks independent chains, motion and exclusive joint ones: give one of predict, motion and exclusive")
     if motion and exclusive:
         raise ValueError("motion and exclusive are two rules for one loop: give one of them")
     if min_ratio is not None and not exclusive and not motion:
         raise ValueError("min_ratio belongs to exclusive")
-    if (coast is not None or min_response is not None) and not motion:
-        raise ValueError("coast and min_response belong to motion")
+    if (coast is not None or min_response is not None) and not motion and not predict:
+        raise ValueError("coast and min_response belong to motion and predict")
+    if predict:
+        pred = predict_args(0.0 if min_response is None else min_response, 8 if coast is None else coast)
     if exclusive or motion:
         n_locs = len(start_locations) if isinstance(start_locations, list) else 1
         excl = exclusive_args(max(n_locs, 1), None, min_distance, 0.5 if min_ratio is None else min_ratio)
@@ -497,6 +509,8 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 out, state, _ = bt.detect_chains_motion(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None,
                                                         excl[2], excl[3], excl[4], first=1)
                 out, state = out[0], state[0]
+            elif predict:
+                out, state, _ = bt.detect_chains_predicted(frames, np.tile(table, (nt, 1)), starts, pred[0], pred[1], first=1)
             else:
                 out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
             sub = None
@@ -510,6 +524,6 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     dia.set_targets(nt)
                     _render_steps(dia, frames, table, out, chunk, diagnostic)
             res = (ts, out, sub) if subpixel else (ts, out)
-            return res + (state,) if exclusive or motion else res
+            return res + (state,) if exclusive or motion or predict else res
         finally:
             bt.close()
