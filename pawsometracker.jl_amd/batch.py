@@ -12,6 +12,14 @@ from . import _lib
 from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args, predict_args
 
 
+def _targets_of(starts):
+    """n_targets of a group walk's starts, [n_groups, n_targets, 2]; the rest of the shape is judged with the table's."""
+    import torch
+    if not isinstance(starts, torch.Tensor) or starts.dim() != 3:
+        raise TypeError("starts must be an int32 cuda tensor [n_groups, n_targets, 2]")
+    return int(starts.shape[1])
+
+
 class BatchTracker(_lib.TrackerHandle):
     _clips = None
 
@@ -143,6 +151,28 @@ class BatchTracker(_lib.TrackerHandle):
                                                  nf, nc, C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
+    def _table_walk(self, frames, frame_table, starts, first, n_targets=None, state=False, out=None, name="starts"):
+        """What the methods over a frame table begin with: torch's stream, the table on the host, `first` (None: the library's
+        to judge), the frame stack, starts int32 cuda [n_rows, 2] — [n_rows, n_targets, 2] with n_targets —, and the zeroed
+        outputs: positions [n_rows, (n_targets,) n_steps, 2] (`out`, checked, where one is given) and, with `state`, the states
+        beside them.  Returns (the library's arguments behind the handle: the stack, the table and its sizes; positions;
+        states or None)."""
+        import torch
+        self.use_torch_stream()
+        table = host_table(frame_table, "frame_table")
+        nr, ns = table.shape
+        if first is not None and (isinstance(first, bool) or first not in (0, 1)):
+            raise ValueError(f"first: {first!r} is neither 0 nor 1")
+        device_frames(frames, "frames", 3, self._hw)
+        rows = (nr,) if n_targets is None else (nr, n_targets)
+        device_array(starts, name, torch.int32, rows + (2,))
+        if out is None:
+            out = torch.zeros(rows + (ns, 2), dtype=torch.int32, device=frames.device)
+        device_array(out, "out", torch.int32, rows + (ns, 2))
+        st = torch.zeros(rows + (ns,), dtype=torch.int32, device=frames.device) if state else None
+        tab = table.ctypes.data_as(C.c_void_p)      # (data_as keeps the array alive as long as the pointer)
+        return (C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], tab, ns, nr), out, st
+
     def detect_chains_indexed(self, frames, frame_table, start_guesses, first=0, out=None):
         """Chains over a frame table (pdog_detect_chains_indexed): frames uint8 cuda [n_frames, h, w] is ONE stack that every
         clip shares; frame_table — rows of integers [n_clips, n_steps], host side — names the frame of each step, and a clip
@@ -152,18 +182,8 @@ class BatchTracker(_lib.TrackerHandle):
         start/stop windows of it).  The library checks the table before it launches anything (PdogError, PDOG_E_ARG, for an
         entry >= n_frames or a non-negative entry behind a negative one).  Returns int32 cuda [n_clips, n_steps, 2]; rows at
         and beyond a clip's end are not written (a fresh `out` is zeroed)."""
-        import torch
-        self.use_torch_stream()
-        device_frames(frames, "frames", 3, self._hw)
-        table = host_table(frame_table, "frame_table")
-        nc, ns = table.shape
-        device_array(start_guesses, "start_guesses", torch.int32, (nc, 2))
-        if out is None:
-            out = torch.zeros((nc, ns, 2), dtype=torch.int32, device=frames.device)
-        device_array(out, "out", torch.int32, (nc, ns, 2))
-        _lib.check(_lib.lib().pdog_detect_chains_indexed(
-            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
-            C.c_void_p(table.ctypes.data), ns, nc, int(first), C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
+        walk, out, _ = self._table_walk(frames, frame_table, start_guesses, None, out=out, name="start_guesses")
+        _lib.check(_lib.lib().pdog_detect_chains_indexed(self._h, *walk, int(first), C.c_void_p(start_guesses.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
     def assign_exclusive(self, prev, ij, peak, count, min_distance=None, min_ratio=0.5):
@@ -201,24 +221,11 @@ class BatchTracker(_lib.TrackerHandle):
         group's targets share them out as assign_exclusive states; first as for detect_chains_indexed (first = 1 files the
         starts as given, with state 0).  Returns (indices int32 cuda [n_groups, n_targets, n_steps, 2], state int32 cuda
         [n_groups, n_targets, n_steps]); steps at and beyond a group's end are not written (both are zeroed)."""
-        import torch
-        self.use_torch_stream()
-        device_frames(frames, "frames", 3, self._hw)
-        table = host_table(frame_table, "frame_table")
-        ng, ns = table.shape
-        if not isinstance(starts, torch.Tensor) or starts.dim() != 3:
-            raise TypeError("starts must be an int32 cuda tensor [n_groups, n_targets, 2]")
-        nt = int(starts.shape[1])
+        nt = _targets_of(starts)
         k, md, rho = exclusive_args(nt, k, min_distance, min_ratio)
-        if isinstance(first, bool) or first not in (0, 1):
-            raise ValueError(f"first: {first!r} is neither 0 nor 1")
-        device_array(starts, "starts", torch.int32, (ng, nt, 2))
-        out = torch.zeros((ng, nt, ns, 2), dtype=torch.int32, device=frames.device)
-        state = torch.zeros((ng, nt, ns), dtype=torch.int32, device=frames.device)
-        _lib.check(_lib.lib().pdog_detect_chains_exclusive(
-            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
-            C.c_void_p(table.ctypes.data), ns, ng, nt, int(first), k, md, rho, C.c_void_p(starts.data_ptr()),
-            C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr())))
+        walk, out, state = self._table_walk(frames, frame_table, starts, first, nt, state=True)
+        _lib.check(_lib.lib().pdog_detect_chains_exclusive(self._h, *walk, nt, int(first), k, md, rho, C.c_void_p(starts.data_ptr()),
+                                                           C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr())))
         return out, state
 
     def assign_motion(self, prev, mstate, ij, peak, count, min_distance=None, min_ratio=0.5, min_response=0.0, coast=8):
@@ -261,26 +268,14 @@ class BatchTracker(_lib.TrackerHandle):
         [n_groups, n_targets, n_steps, 2], state int32 cuda [n_groups, n_targets, n_steps], mstate); steps at and beyond a
         group's end are not written (both are zeroed)."""
         import torch
-        self.use_torch_stream()
-        device_frames(frames, "frames", 3, self._hw)
-        table = host_table(frame_table, "frame_table")
-        ng, ns = table.shape
-        if not isinstance(starts, torch.Tensor) or starts.dim() != 3:
-            raise TypeError("starts must be an int32 cuda tensor [n_groups, n_targets, 2]")
-        nt = int(starts.shape[1])
+        nt = _targets_of(starts)
         k, md, rho, m, coast = motion_args(nt, k, min_distance, min_ratio, min_response, coast)
-        if isinstance(first, bool) or first not in (0, 1):
-            raise ValueError(f"first: {first!r} is neither 0 nor 1")
-        device_array(starts, "starts", torch.int32, (ng, nt, 2))
+        walk, out, state = self._table_walk(frames, frame_table, starts, first, nt, state=True)
         if mstate is None:
-            mstate = torch.zeros((ng, nt, 4), dtype=torch.int32, device=frames.device)
-        device_array(mstate, "mstate", torch.int32, (ng, nt, 4))
-        out = torch.zeros((ng, nt, ns, 2), dtype=torch.int32, device=frames.device)
-        state = torch.zeros((ng, nt, ns), dtype=torch.int32, device=frames.device)
-        _lib.check(_lib.lib().pdog_detect_chains_motion(
-            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
-            C.c_void_p(table.ctypes.data), ns, ng, nt, int(first), k, md, rho, m, coast, C.c_void_p(starts.data_ptr()),
-            C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
+            mstate = torch.zeros((state.shape[0], nt, 4), dtype=torch.int32, device=frames.device)
+        device_array(mstate, "mstate", torch.int32, (state.shape[0], nt, 4))
+        _lib.check(_lib.lib().pdog_detect_chains_motion(self._h, *walk, nt, int(first), k, md, rho, m, coast, C.c_void_p(starts.data_ptr()),
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
         return out, state, mstate
 
     def detect_chains_predicted(self, frames, frame_table, starts, min_response=0.0, coast=8, mstate=None, first=0):
@@ -294,23 +289,13 @@ class BatchTracker(_lib.TrackerHandle):
         state int32 cuda [n_clips, n_steps] — 1 assigned, -1 held, 0 the start filed by first = 1 —, mstate); steps at and beyond
         a clip's end are not written (both are zeroed)."""
         import torch
-        self.use_torch_stream()
-        table = host_table(frame_table, "frame_table")
-        nc, ns = table.shape
         m, coast = predict_args(min_response, coast)
-        if isinstance(first, bool) or first not in (0, 1):
-            raise ValueError(f"first: {first!r} is neither 0 nor 1")
-        device_frames(frames, "frames", 3, self._hw)
-        device_array(starts, "starts", torch.int32, (nc, 2))
+        walk, out, state = self._table_walk(frames, frame_table, starts, first, state=True)
         if mstate is None:
-            mstate = torch.zeros((nc, 4), dtype=torch.int32, device=frames.device)
-        device_array(mstate, "mstate", torch.int32, (nc, 4))
-        out = torch.zeros((nc, ns, 2), dtype=torch.int32, device=frames.device)
-        state = torch.zeros((nc, ns), dtype=torch.int32, device=frames.device)
-        _lib.check(_lib.lib().pdog_detect_chains_predicted(
-            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
-            C.c_void_p(table.ctypes.data), ns, nc, int(first), m, coast, C.c_void_p(starts.data_ptr()),
-            C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
+            mstate = torch.zeros((state.shape[0], 4), dtype=torch.int32, device=frames.device)
+        device_array(mstate, "mstate", torch.int32, (state.shape[0], 4))
+        _lib.check(_lib.lib().pdog_detect_chains_predicted(self._h, *walk, int(first), m, coast, C.c_void_p(starts.data_ptr()),
+                                                           C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()), C.c_void_p(mstate.data_ptr())))
         return out, state, mstate
 
     def measure(self, frames, ij, frame_index=None, want_resp=False):
@@ -398,20 +383,10 @@ class BatchTracker(_lib.TrackerHandle):
         its row turns negative: the lengths are the table's), fills holds one value per clip (None: the tracker's fill for
         all).  Returns int32 cuda [n_clips, n_steps, 2]; rows at and beyond a clip's end are not written (a fresh `out` is
         zeroed)."""
-        import torch
-        self.use_torch_stream()
-        device_frames(frames, "frames", 3, self._hw)
-        table = host_table(frame_table, "frame_table")
-        nc, ns = table.shape
-        device_array(starts, "starts", torch.int32, (nc, 2))
-        fa = host_i32(fills, "fills", nc)
-        if out is None:
-            out = torch.zeros((nc, ns, 2), dtype=torch.int32, device=frames.device)
-        device_array(out, "out", torch.int32, (nc, ns, 2))
-        _lib.check(_lib.lib().pdog_clips_track_indexed(
-            self._clips_handle(), C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
-            C.c_void_p(table.ctypes.data), ns, nc, None if fa is None else C.c_void_p(fa.ctypes.data), int(first),
-            C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
+        walk, out, _ = self._table_walk(frames, frame_table, starts, None, out=out)
+        fa = host_i32(fills, "fills", out.shape[0])
+        _lib.check(_lib.lib().pdog_clips_track_indexed(self._clips_handle(), *walk, None if fa is None else C.c_void_p(fa.ctypes.data), int(first),
+                                                       C.c_void_p(starts.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
     def close(self):

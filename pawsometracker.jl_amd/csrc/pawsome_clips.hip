@@ -266,12 +266,9 @@ int pdog_clips_track_indexed(pdog_clips *c, const uint8_t *d_frames, int64_t fra
 {
     if (!c) return fail(PDOG_E_ARG, "pdog_clips_track_indexed: null handle");
     if (!d_frames || !h_table || !d_start || !d_out_ij) return fail(PDOG_E_ARG, "pdog_clips_track_indexed: null pointer");
-    if (int rc = check_stack("pdog_clips_track_indexed", c->fw, n_frames, row_stride, frame_stride, n_steps > 0 && n_clips > 0 && (long long)n_clips * n_steps <= 0x7fffffffLL)) return rc;
-    if (first != 0 && first != 1) return fail(PDOG_E_ARG, "pdog_clips_track_indexed: first must be 0 or 1");
     // the lengths come from the table's negative tails; it is checked before anything is launched
-    if (c->table_len.size() < (size_t)n_clips) c->table_len.resize((size_t)n_clips);
-    int max_len = 0;
-    if (int rc = chain_table_lengths("pdog_clips_track_indexed", h_table, n_steps, n_clips, n_frames, c->table_len.data(), &max_len)) return rc;
+    TableWalk w{"pdog_clips_track_indexed", c->fw, n_frames, row_stride, frame_stride, h_table, n_steps, n_clips, 1, first, 0, 0};
+    if (int rc = check_table_walk(w, c->table_len)) return rc;
     return track_walk(c, d_frames, frame_stride, row_stride, n_steps, n_clips, h_fill, c->table_len.data(), first, d_start, d_out_ij,
                       h_table, n_frames);
 }

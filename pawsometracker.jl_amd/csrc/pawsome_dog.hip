@@ -312,9 +312,7 @@ struct pdog_tracker {
     FusedPlan fused;
     int hp_rows = HP_ROWS;         // RT rows (window columns) per column-pass workgroup: 16 (P = 13) or 8 (P = 7)
     DeviceBuffer<int32_t> d_chain_tmp; // [2][n_clips][2]: current guesses / step results of multi-clip chains
-    // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it
-    StagedUpload<int32_t> table;
-    std::vector<int32_t> table_len;    // steps per clip of the table being served
+    pdog::StagedTable table;       // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it
     int tp_ph1 = 13, tp_php = 7;   // outputs per task of the two-pass row / column pass (pick_twopass_p)
     TiledPlan tiled;
     TiledRun tiled_run;
@@ -368,9 +366,10 @@ struct pdog_tracker {
     PinnedBuffer<uint8_t> h_tile{hipHostMallocMapped}; // the functor's window tile when the kernels read it in place
     Ingest ingest;
     pdog::PeaksState peaks; // pdog_detect_peaks (pawsome_peaks.hip): its scratch, switch and counters
-    pdog::ExclusiveState exclusive; // the exclusive step and walk (pawsome_exclusive.hip): their scratch and counters
-    pdog::MotionState motion;       // the motion step and walk (pawsome_motion.hip): their scratch, switch and counters
-    pdog::PredictState predict;     // the predicted chain (pawsome_predict.hip): its table lengths and counters
+    pdog::GroupWalkState exclusive; // the exclusive step and walk (pawsome_exclusive.hip): their scratch, table and counters
+    pdog::GroupWalkState motion;    // the motion step and walk (pawsome_motion.hip): the same
+    bool motion_lds = false;        // pdog_set_tuning "motion_lds": the motion kernel stages the lists in LDS (dog_motion.hpp)
+    pdog::PredictState predict;     // the predicted chain (pawsome_predict.hip): its table and counters
 
     // Drains and destroys the streams and events; the buffers free themselves after that.
     ~pdog_tracker()
@@ -395,17 +394,19 @@ pdog::PeaksState *pdog::peaks_state(pdog_tracker *t)
     return &t->peaks;
 }
 
-pdog::ExclusiveState *pdog::exclusive_state(pdog_tracker *t)
+pdog::GroupWalkState *pdog::exclusive_state(pdog_tracker *t)
 {
     t->exclusive.device = t->device;
     return &t->exclusive;
 }
 
-pdog::MotionState *pdog::motion_state(pdog_tracker *t)
+pdog::GroupWalkState *pdog::motion_state(pdog_tracker *t)
 {
     t->motion.device = t->device;
     return &t->motion;
 }
+
+bool pdog::motion_lds(const pdog_tracker *t) { return t->motion_lds; }
 
 pdog::PredictState *pdog::predict_state(pdog_tracker *t)
 {
@@ -1623,7 +1624,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h
-    else if (k == "motion_lds") t->motion.lds = on;       // include/pawsome_motion.h
+    else if (k == "motion_lds") t->motion_lds = on;       // include/pawsome_motion.h
     else if (k == "no_fused_c" || k == "no_tiled") { // inputs of the plan: the latency kernels' instances and tile layouts
         (k == "no_tiled" ? t->sw.no_tiled : t->sw.no_fused_c) = on;
         return make_plan(t, t->forced_variant ? t->var->id : -1);
@@ -2006,34 +2007,9 @@ extern "C" int pdog_detect_batch_host(pdog_tracker *t, const uint8_t *h_frames, 
 
 namespace {
 
-// A validated frame table (pdog_detect_chains_indexed): step k of clip c looks at frame h[c*n_steps + k], clip c has len[c] steps.
-struct ChainTable {
-    const int32_t *h;   // host, n_clips x n_steps
-    const int32_t *len; // host, n_clips
-    int first;          // 1: row 0 receives the start as given, the loop begins at step 1
-    int max_len;
-};
-
-// The table on the device, on the tracker's stream.  by_step = false: rows as given, then the lengths — what the kernels
-// that walk a clip themselves read.  by_step = true: the table transposed (step k's frames of all clips are one batch's
-// frame index), a clip that has ended repeating its last frame (frame 0 if it has none), then the lengths.
-int upload_chain_table(pdog_tracker *t, const ChainTable &ct, int n_clips, int n_steps, bool by_step, const int32_t **d_tab, const int32_t **d_len)
-{
-    const size_t cells = (size_t)n_clips * (by_step ? ct.max_len : n_steps), words = cells + (size_t)n_clips;
-    int32_t *hp = nullptr;
-    if (int rc = t->table.staging(words, t->stream, &hp)) return rc;
-    if (!by_step) std::memcpy(hp, ct.h, sizeof(int32_t) * cells);
-    else
-        for (int c = 0; c < n_clips; ++c) {
-            const int32_t *row = ct.h + (size_t)c * n_steps;
-            for (int k = 0; k < ct.max_len; ++k) hp[(size_t)k * n_clips + c] = k < ct.len[c] ? row[k] : (ct.len[c] ? row[ct.len[c] - 1] : 0);
-        }
-    std::memcpy(hp + cells, ct.len, sizeof(int32_t) * (size_t)n_clips);
-    if (int rc = t->table.send(words, t->stream)) return rc;
-    *d_tab = t->table.device();
-    *d_len = t->table.device() + cells;
-    return PDOG_OK;
-}
+// A validated frame table (pdog_detect_chains_indexed, pdog_detect_chains_predicted) is the checked TableWalk: step k of
+// row c looks at frame h_table[c*n_steps + k], `first` = 1 means that step 0 receives the start as given and the loop begins at
+// step 1; row c has table.len[c] steps on the StagedTable that was checked with it.
 
 int chain_strips(const pdog_tracker *t) { return (t->n2 + ROLL_TW - 1) / ROLL_TW; }
 
@@ -2096,19 +2072,19 @@ ChainPath chain_path(const pdog_tracker *t, int n_clips, int n_steps, bool table
 // (clamped) answer, read straight from the output array (device or host-mapped), no host round trip per frame.  With a
 // table the host names each step's frame itself.  With clip.done_flag every step publishes k + 1 there: by the kernels'
 // own ticket where the launch arms one, by dog_publish_kernel behind them otherwise.
-int walk_clip(pdog_tracker *t, const Request &clip, const ChainTable *ct)
+int walk_clip(pdog_tracker *t, const Request &clip, const TableWalk *ct)
 {
     if (int rc = ensure_capacity(t, 1)) return rc;
     Request req = clip; // one independent window per launch
     req.n = 1; req.chain_len = 1; req.progress = false;
     req.table = ClipTable{nullptr, nullptr, 0};
-    const int len = ct ? ct->len[0] : clip.chain_len, first = ct ? ct->first : 0;
+    const int len = ct ? t->table.len[0] : clip.chain_len, first = ct ? ct->first : 0;
     if (first && len >= 1) { // the bootstrap's position, stored as given (:161); step 1 starts from the caller's copy of it
         HIP_TRY(hipMemcpyAsync(req.out_ij, clip.guesses, sizeof(int32_t) * 2, hipMemcpyDeviceToDevice, t->stream));
         req.out_ij += 2;
     }
     for (int k = first; k < len; ++k) {
-        req.frames = clip.frames + (int64_t)(ct ? ct->h[k] : k) * clip.frame_stride;
+        req.frames = clip.frames + (int64_t)(ct ? ct->h_table[k] : k) * clip.frame_stride;
         if (req.done_flag) req.done_value = k + 1;
         bool armed = false;
         if (int rc = launch_detect(t, req, req.done_flag ? &armed : nullptr)) return rc;
@@ -2125,7 +2101,7 @@ int walk_clip(pdog_tracker *t, const Request &clip, const ChainTable *ct)
 // The stepped walk of SEVERAL clips: step k of all clips is one batch, and dog_step_kernel files its answers under [clip][k]
 // and makes them the next guesses.  Contiguous: window c looks at frame c*n_steps + k, a batch whose frame stride is one
 // clip.  Table: the batch's frame index is the table's column k; a clip that has ended rides along and stores nothing.
-int walk_clips(pdog_tracker *t, const Request &clips, const ChainTable *ct)
+int walk_clips(pdog_tracker *t, const Request &clips, const TableWalk *ct)
 {
     const int n_clips = clips.n, n_steps = clips.chain_len, blocks = (n_clips + 255) / 256;
     if (int rc = ensure_capacity(t, n_clips)) return rc;
@@ -2137,7 +2113,7 @@ int walk_clips(pdog_tracker *t, const Request &clips, const ChainTable *ct)
     batch.out_ij = step;
     const int32_t *d_cols = nullptr, *d_len = nullptr;
     if (ct) {
-        if (int rc = upload_chain_table(t, *ct, n_clips, n_steps, true, &d_cols, &d_len)) return rc;
+        if (int rc = t->table.upload(ct->h_table, TableShape{n_steps, n_clips, ct->max_len, 1}, t->stream, nullptr, &d_cols, &d_len)) return rc;
         hipLaunchKernelGGL(dog_chain_table_init_kernel, dim3(blocks), dim3(256), 0, t->stream, clips.guesses, d_len, cur, clips.out_ij,
                            n_clips, n_steps, ct->first);
         HIP_TRY(hipGetLastError());
@@ -2158,7 +2134,7 @@ int walk_clips(pdog_tracker *t, const Request &clips, const ChainTable *ct)
 }
 
 // clips.n clips of clips.chain_len steps each: contiguous (ct null: clip c's step k is frame c*chain_len + k) or over a table.
-int run_chains(pdog_tracker *t, Request clips, const ChainTable *ct)
+int run_chains(pdog_tracker *t, Request clips, const TableWalk *ct)
 {
     if (t->sw.tiled_force && clips.n == 1 && !t->forced_variant && !ct && !clips.progress) { // experiment switch: the tiled kernel first
         bool launched = false;
@@ -2167,7 +2143,7 @@ int run_chains(pdog_tracker *t, Request clips, const ChainTable *ct)
     }
     const ChainPath path = chain_path(t, clips.n, clips.chain_len, ct != nullptr, clips.progress);
     if (ct && path != ChainPath::Stepped) { // the kernels that walk a clip themselves read the table's rows
-        if (int rc = upload_chain_table(t, *ct, clips.n, clips.chain_len, false, &clips.table.index, &clips.table.len)) return rc;
+        if (int rc = t->table.upload(ct->h_table, TableShape{clips.chain_len, clips.n, ct->max_len, 0}, t->stream, nullptr, &clips.table.index, &clips.table.len)) return rc;
         clips.table.first = ct->first;
     }
     switch (path) {
@@ -2206,11 +2182,8 @@ extern "C" int pdog_detect_chains_indexed(pdog_tracker *t, const uint8_t *d_fram
                                           const int32_t *d_start, int32_t *d_out_ij)
 {
     if (!t || !d_frames || !h_table || !d_start || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: null pointer");
-    if (int rc = check_stack("pdog_detect_chains_indexed", t->fw, n_frames, row_stride, frame_stride, n_steps > 0 && n_clips > 0 && (long long)n_clips * n_steps <= 0x7fffffffLL)) return rc;
-    if (first != 0 && first != 1) return fail(PDOG_E_ARG, "pdog_detect_chains_indexed: first must be 0 or 1");
-    if (t->table_len.size() < (size_t)n_clips) t->table_len.resize((size_t)n_clips);
-    ChainTable ct{h_table, t->table_len.data(), first, 0};
-    if (int rc = chain_table_lengths("pdog_detect_chains_indexed", h_table, n_steps, n_clips, n_frames, t->table_len.data(), &ct.max_len)) return rc;
+    TableWalk ct{"pdog_detect_chains_indexed", t->fw, n_frames, row_stride, frame_stride, h_table, n_steps, n_clips, 1, first, 0, 0};
+    if (int rc = check_table_walk(ct, t->table.len)) return rc;
     if (ct.max_len == 0) return PDOG_OK; // no clip has a step
     HIP_TRY(hipSetDevice(t->device));
     Request clips;
@@ -2223,17 +2196,17 @@ extern "C" int pdog_detect_chains_indexed(pdog_tracker *t, const uint8_t *d_fram
 int pdog::launch_predicted(pdog_tracker *t, const PredictWalk &w, int *taken)
 {
     *taken = 0;
-    const ChainPath path = chain_path(t, w.n_clips, w.n_steps, true, false);
+    const TableWalk &tw = w.walk;
+    const ChainPath path = chain_path(t, tw.n_rows, tw.n_steps, true, false);
     if (path != ChainPath::Fused && !(path == ChainPath::Persistent && t->var->chain_predict)) return PDOG_OK;
     HIP_TRY(hipSetDevice(t->device));
     Request clips;
-    clips.frames = w.d_frames; clips.frame_stride = w.frame_stride; clips.row_stride = w.row_stride;
-    clips.guesses = w.d_start; clips.n = w.n_clips; clips.chain_len = w.n_steps; clips.out_ij = w.d_out_ij;
-    const size_t words = (size_t)w.n_clips * w.n_steps + (size_t)w.n_clips;
-    if (words > t->predict.table_words) { ++t->predict.grown; t->predict.table_words = words; }
-    const ChainTable ct{w.h_table, w.len, w.first, w.max_len};
-    if (int rc = upload_chain_table(t, ct, w.n_clips, w.n_steps, false, &clips.table.index, &clips.table.len)) return rc;
-    clips.table.first = w.first;
+    clips.frames = w.d_frames; clips.frame_stride = tw.frame_stride; clips.row_stride = tw.row_stride;
+    clips.guesses = w.d_start; clips.n = tw.n_rows; clips.chain_len = tw.n_steps; clips.out_ij = w.d_out_ij;
+    if (int rc = t->predict.table.upload(tw.h_table, TableShape{tw.n_steps, tw.n_rows, tw.max_len, 0}, t->stream, &t->predict.grown,
+                                         &clips.table.index, &clips.table.len))
+        return rc;
+    clips.table.first = tw.first;
     const PredictCtl pc{w.m, w.coast, w.d_out_state, w.d_mstate};
     clips.predict = &pc;
     if (path == ChainPath::Fused) {

@@ -19,16 +19,12 @@ extern "C" int pdog_detect_chains_predicted(pdog_tracker *t, const uint8_t *d_fr
     if (int rc = pdog::check_motion(who, min_response, coast)) return rc;
     pdog_info info;
     if (int rc = pdog_get_info(t, &info)) return rc;
-    if (int rc = pdog::check_stack(who, info.frame_w, n_frames, row_stride, frame_stride, n_steps > 0 && n_clips > 0 && (long long)n_clips * n_steps <= 0x7fffffffLL)) return rc;
-    if (first != 0 && first != 1) return fail(PDOG_E_ARG, std::string(who) + ": first must be 0 or 1");
     pdog::PredictState *ps = pdog::predict_state(t);
-    if (ps->len.size() < (size_t)n_clips) ps->len.resize((size_t)n_clips);
-    int max_len = 0;
-    if (int rc = pdog::chain_table_lengths(who, h_table, n_steps, n_clips, n_frames, ps->len.data(), &max_len)) return rc;
-    if (max_len == 0) return PDOG_OK; // no clip has a step
+    pdog::PredictWalk w{{who, info.frame_w, n_frames, row_stride, frame_stride, h_table, n_steps, n_clips, 1, first, 0, 0}, d_frames,
+                        (float)min_response, coast, d_start, d_out_ij, d_out_state, d_mstate};
+    if (int rc = pdog::check_table_walk(w.walk, ps->table.len)) return rc;
+    if (w.walk.max_len == 0) return PDOG_OK; // no clip has a step
 
-    const pdog::PredictWalk w{d_frames, frame_stride, row_stride, h_table, ps->len.data(), max_len, n_steps, n_clips, first,
-                              (float)min_response, coast, d_start, d_out_ij, d_out_state, d_mstate};
     int taken = 0;
     if (int rc = pdog::launch_predicted(t, w, &taken)) return rc;
     if (taken) return PDOG_OK;

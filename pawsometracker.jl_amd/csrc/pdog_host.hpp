@@ -9,9 +9,11 @@
 // raise_lds_limit is keyed on a kernel's address: a second translation unit that included one of those headers would get
 // private copies whose LDS limit was never raised.  So every include of a dog_*.hpp header of the tracker, every launch of
 // its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
-// this header and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip,
+// this header, pdog_walk.hpp and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip,
 // pawsome_exclusive.hip and pawsome_motion.hip launch their own kernels, dog_diag.hpp's, group_compact_kernel, dog_peaks.hpp's,
-// dog_assign.hpp's and dog_motion.hpp's, which no other unit names; pawsome_predict.hip launches nothing itself: the predicted
+// dog_assign.hpp's and dog_motion.hpp's, which no other unit names; the last two hold nothing but those launches and their
+// geometry: the walk around them — checks, scratch, staged table, the loop over pdog_detect_peaks — is pdog_walk.hpp's, which
+// takes the rule's launch as a callable and so names no kernel.  pawsome_predict.hip launches nothing itself: the predicted
 // chain's kernels are instances of the tracker's own, launched by launch_predicted in pawsome_dog.hip.)  The one exception is dog_step.hpp, which
 // pawsome_dog.hip and pawsome_clips.hip both include: its kernel uses no dynamic LDS, so no limit is ever raised for it and
 // a private copy per unit is harmless.
@@ -39,6 +41,27 @@ double dog_kernel_norm_up(const std::vector<double> &gp, const std::vector<doubl
 // negative entries only as the tail of a row.  out_len[c] = steps of clip c (its row's leading non-negative entries),
 // *max_len the longest.  PDOG_E_ARG in `who`'s name, outputs undefined, otherwise.
 int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, int n_clips, int n_frames, int32_t *out_len, int *max_len);
+// One walk over a frame table, as every entry point that takes one describes it: the frame stack, the table's n_rows rows of
+// n_steps entries, `windows` windows per row (a clip is one, a group its targets) and `first`.  n_strips > 0: the walk's steps
+// go through pdog_detect_peaks, whose limit on a batch (n_rows * windows windows of n_strips strips) is judged here.
+struct TableWalk {
+    const char *who;
+    int fw, n_frames;
+    int64_t row_stride, frame_stride;
+    const int32_t *h_table;
+    int n_steps, n_rows, windows, first, n_strips;
+    int max_len; // check_table_walk's: the longest row (0: no row has a step, nothing is to be done)
+};
+// The tests the table walks share, in the order they are refused: check_stack (the sizes positive, n_rows * windows * n_steps
+// within 31 bits), the batch limit, first = 0 or 1, then the table itself; len grows to n_rows and receives the rows' lengths.
+int check_table_walk(TableWalk &w, std::vector<int32_t> &len);
+// The words a walk's table is staged as, and their arithmetic.  windows = 0: the rows as given, n_rows x n_steps — what the
+// kernels that walk a clip themselves read.  windows = T >= 1: by step with a frame per WINDOW, [max_len][n_rows][T] (step s's
+// cells are that batch's frame index); a row that has ended repeats its last frame (frame 0 if it has none).  The rows'
+// lengths follow the cells either way.
+struct TableShape { int n_steps, n_rows, max_len, windows; };
+inline size_t table_cells(const TableShape &s) { return s.windows ? (size_t)s.max_len * s.n_rows * s.windows : (size_t)s.n_rows * s.n_steps; }
+void fill_table(const int32_t *h_table, const int32_t *len, const TableShape &s, int32_t *out); // out: table_cells(s) + n_rows words
 // What the entry points of include/pawsome_exclusive.h refuse alike: sizes outside their ranges, a ratio outside [0, 1] or NaN.
 int check_exclusive(const char *who, int n_groups, int n_targets, int k, double min_ratio);
 // What the entry points of include/pawsome_motion.h refuse beyond that: a min_response that is negative, NaN or infinite, coast < 0.
@@ -187,49 +210,62 @@ struct PeaksState {
 };
 PeaksState *peaks_state(pdog_tracker *t);
 
-// What the exclusive step and walk (pawsome_exclusive.hip, a unit of its own with its own kernels) keep on a tracker: a member
-// of pdog_tracker like PeaksState; exclusive_state (pawsome_dog.hip) hands it out with the tracker's device filled in.
-struct ExclusiveState {
-    int device = 0;
-    DeviceBuffer<int32_t> d_words;  // per window: the current guess [n][2], the picks [n][k][2], the counts [n]
-    DeviceBuffer<float> d_peak;     // [n][k] the picks' values
-    StagedUpload<int32_t> table;    // the validated table by step, a frame per WINDOW [max_len][n], then the groups' lengths [G]
-    std::vector<int32_t> len;       // steps per group of the table being served
-    size_t table_words = 0;         // the most words `table` was asked for
-    uint64_t steps = 0, grown = 0;  // pdog_get_exclusive_counts
-};
-ExclusiveState *exclusive_state(pdog_tracker *t);
+// A walk's validated table on its way to the device: the rows' lengths, the staged words (fill_table's layouts) and the most
+// words any upload asked for.  Every family of walks keeps its own (the tracker's chains, the exclusive and the motion walk, the
+// predicted chain), so a family's `grown` counts its own high-water marks alone.  Walks may follow each other on one stream
+// without a synchronisation: staging() waits for the previous upload's event before the pinned words are overwritten, and the
+// device copy is overwritten in stream order, behind the kernels that read it.
+struct StagedTable {
+    std::vector<int32_t> len; // steps per row of the table being served (check_table_walk)
 
-// The same for the motion step and walk (pawsome_motion.hip, its own unit and kernels); motion_state (pawsome_dog.hip).
-struct MotionState {
-    bool lds = false;               // pdog_set_tuning "motion_lds": the kernel stages the lists in LDS (dog_motion.hpp)
-    int device = 0;
-    DeviceBuffer<int32_t> d_words;  // per window: the position [n][2], the guess [n][2], the walk's own mstate [n][4], the picks [n][k][2], the counts [n]
-    DeviceBuffer<float> d_peak;     // [n][k] the picks' values
-    StagedUpload<int32_t> table;    // as ExclusiveState's
-    std::vector<int32_t> len;
-    size_t table_words = 0;
-    uint64_t steps = 0, grown = 0;  // pdog_get_motion_counts
+    // h_table and len in `s`'s layout, queued on `stream`; ++*grown (if given) where that takes more words than ever before.
+    int upload(const int32_t *h_table, const TableShape &s, hipStream_t stream, uint64_t *grown, const int32_t **d_cells, const int32_t **d_len)
+    {
+        const size_t cells = table_cells(s), n = cells + (size_t)s.n_rows;
+        if (n > most_) { most_ = n; if (grown) ++*grown; }
+        int32_t *hp = nullptr;
+        if (int rc = words_.staging(n, stream, &hp)) return rc;
+        fill_table(h_table, len.data(), s, hp);
+        if (int rc = words_.send(n, stream)) return rc;
+        *d_cells = words_.device();
+        *d_len = words_.device() + cells;
+        return PDOG_OK;
+    }
+
+private:
+    StagedUpload<int32_t> words_;
+    size_t most_ = 0;
 };
-MotionState *motion_state(pdog_tracker *t);
+
+// What a walk of groups keeps on a tracker — the exclusive walk and the motion walk, a member of pdog_tracker each like
+// PeaksState (their units, pawsome_exclusive.hip and pawsome_motion.hip, have their own kernels); exclusive_state and
+// motion_state (pawsome_dog.hip) hand them out with the tracker's device filled in, motion_lds the motion kernel's switch.
+struct GroupWalkState {
+    int device = 0;
+    DeviceBuffer<int32_t> d_words;  // per window: what the rule carries from step to step, then the picks [n][k][2], the counts [n] (pdog_walk.hpp)
+    DeviceBuffer<float> d_peak;     // [n][k] the picks' values
+    StagedTable table;              // by step, a frame per window
+    uint64_t steps = 0, grown = 0;  // pdog_get_exclusive_counts / pdog_get_motion_counts
+};
+GroupWalkState *exclusive_state(pdog_tracker *t);
+GroupWalkState *motion_state(pdog_tracker *t);
+bool motion_lds(const pdog_tracker *t); // pdog_set_tuning "motion_lds": the kernel stages the lists in LDS (dog_motion.hpp)
 
 // The predicted chain (include/pawsome_predict.h; pawsome_predict.hip holds its entry points).  Its one-launch kernels are
 // instances of the tracker's own chain kernels, so their launch stays in pawsome_dog.hip (see above): launch_predicted.
 struct PredictState {
     int device = 0;
-    std::vector<int32_t> len;       // steps per clip of the table being served
-    size_t table_words = 0;         // the most words the staged table was asked for
+    StagedTable table;              // the rows as given
     uint64_t fused = 0, persistent = 0, fallback = 0, grown = 0; // pdog_get_predict_counts
 };
 PredictState *predict_state(pdog_tracker *t);
-// A validated walk (h_table's lengths in len, the longest max_len >= 1) on the kernel chain_path chooses.  *taken = 1: one
-// launch of the fused kernel's predicted instance; 2: of the persistent chain kernel's; 0: nothing was launched or staged — the
-// geometry is the tiled kernel's or the stepped walk's, or the kernel length has no instance — and the caller falls back.
+// A validated walk (its rows' lengths in the state's table, the longest walk.max_len >= 1) on the kernel chain_path chooses.
+// *taken = 1: one launch of the fused kernel's predicted instance; 2: of the persistent chain kernel's; 0: nothing was launched
+// or staged — the geometry is the tiled kernel's or the stepped walk's, or the kernel length has no instance — and the caller
+// falls back.
 struct PredictWalk {
+    TableWalk walk;
     const uint8_t *d_frames;
-    int64_t frame_stride, row_stride;
-    const int32_t *h_table, *len;
-    int max_len, n_steps, n_clips, first;
     float m;
     int coast;
     const int32_t *d_start;

@@ -172,6 +172,31 @@ int chain_table_lengths(const char *who, const int32_t *h_table, int n_steps, in
     return PDOG_OK;
 }
 
+int check_table_walk(TableWalk &w, std::vector<int32_t> &len)
+{
+    const long long n = (long long)w.n_rows * w.windows;
+    if (int rc = check_stack(w.who, w.fw, w.n_frames, w.row_stride, w.frame_stride,
+                             w.n_steps > 0 && w.n_rows > 0 && w.windows > 0 && n <= 0x7fffffffLL && n * w.n_steps <= 0x7fffffffLL))
+        return rc;
+    if (n * w.n_strips > 0x7ffffff0LL) return fail(PDOG_E_ARG, std::string(w.who) + ": batch too large"); // (judged before the first launch)
+    if (w.first != 0 && w.first != 1) return fail(PDOG_E_ARG, std::string(w.who) + ": first must be 0 or 1");
+    if (len.size() < (size_t)w.n_rows) len.resize((size_t)w.n_rows);
+    return chain_table_lengths(w.who, w.h_table, w.n_steps, w.n_rows, w.n_frames, len.data(), &w.max_len);
+}
+
+void fill_table(const int32_t *h_table, const int32_t *len, const TableShape &s, int32_t *out)
+{
+    const size_t cells = table_cells(s);
+    if (!s.windows) std::copy_n(h_table, cells, out);
+    else
+        for (int r = 0; r < s.n_rows; ++r) {
+            const int32_t *row = h_table + (size_t)r * s.n_steps;
+            for (int k = 0; k < s.max_len; ++k)
+                std::fill_n(out + ((size_t)k * s.n_rows + r) * s.windows, s.windows, k < len[r] ? row[k] : (len[r] ? row[len[r] - 1] : 0));
+        }
+    std::copy_n(len, s.n_rows, out + cells);
+}
+
 } // namespace pdog
 
 using namespace pdog;

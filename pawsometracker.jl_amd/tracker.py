@@ -501,16 +501,11 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     bt4.close()
             # the loop from the second selected frame on, :161-167: every target over the same table
             state = None
-            if exclusive:
-                out, state = bt.detect_chains_exclusive(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None,
-                                                        excl[2], first=1)
-                out, state = out[0], state[0]
-            elif motion:
-                out, state, _ = bt.detect_chains_motion(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None,
-                                                        excl[2], excl[3], excl[4], first=1)
-                out, state = out[0], state[0]
+            if exclusive or motion:      # all targets as ONE group: excl is the rule's (k, min_distance, min_ratio[, min_response, coast])
+                walk = bt.detect_chains_motion if motion else bt.detect_chains_exclusive
+                out, state = (r[0] for r in walk(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None, *excl[2:], first=1)[:2])
             elif predict:
-                out, state, _ = bt.detect_chains_predicted(frames, np.tile(table, (nt, 1)), starts, pred[0], pred[1], first=1)
+                out, state, _ = bt.detect_chains_predicted(frames, np.tile(table, (nt, 1)), starts, *pred, first=1)
             else:
                 out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
             sub = None
