@@ -161,6 +161,15 @@ __device__ __forceinline__ void range_check(const ExactCtl &x, int g1, int g2, i
         __hip_atomic_store(&x.range_err->raised, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// One kept strip of a pruned roll batch (dog_prune.hpp, "the job list"): the pre-pass appends one per strip whose hull is not
+// empty, the PRUNE instance of dog_roll_kernel takes entry blockIdx-many.  Entry 0 of the list is its header: b = the number
+// of entries that follow, as the pre-pass's last workgroup published it.
+struct PruneJob {
+    int b;    // window
+    int s_dc; // strip | the window's DC level << 16
+    int ba, bb; // the kept range of 8-row output blocks
+};
+
 struct LaunchGeo {
     const uint8_t *__restrict__ frames;
     long long frame_stride, row_stride;
@@ -181,10 +190,17 @@ struct LaunchGeo {
     // every window also produces the row-pass outputs (R+, R−) of window column thin_x0 and leaves them here,
     // [n][n1 + L − 1]; dog_finish_kernel runs that one column's column pass.  Same operation order as a strip: the column's
     // values are bit-identical to what a strip would have produced.
-    f2 *__restrict__ fold_r;
+    // A pruned launch never folds: the PRUNE instance of dog_roll_kernel finds the job list (PruneJob) in the same word, so the
+    // struct every other instance receives keeps its size and layout.
+    union {
+        f2 *__restrict__ fold_r;
+        const PruneJob *__restrict__ jobs;
+    };
     int no_pad_skip;                     // roll kernels: padding-only sub-chunks run the full path (pdog_set_tuning "no_pad_skip")
     // roll and thin kernels (dog_prune.hpp): on entry part_mask[b][slot] holds the slot's kept range of 8-row output blocks,
-    // (first | one past the last << 32), and only that range is computed (the struct's size does not change: this word was padding)
+    // (first | one past the last << 32; a remainder column's word also carries the window's DC level, bits 24 … 31), and only
+    // that range is computed (the struct's size does not change: this word was padding).  Non-zero: a pruned launch; the value
+    // is the number of consecutive jobs that go to one XCD (a power of two, prune_job_index).
     int prune;
 };
 

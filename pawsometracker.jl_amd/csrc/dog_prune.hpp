@@ -39,7 +39,18 @@
 // kept / total counts this kernel publishes and stops running it on such batches (pawsome_dog.hip, "pruning policy").
 //
 // The ranges travel in LaunchGeo::part_mask: slot [b][s] holds (first block | one past the last block << 32) when the roll /
-// thin kernels start (LaunchGeo::prune) and the strip's column mask, as ever, when they end.
+// thin kernels start (LaunchGeo::prune) and the strip's column mask, as ever, when they end.  A remainder column's word also
+// carries the window's DC level (bits 24 … 31): dog_thin_kernel reads its range there and skips the DC samples.
+//
+// THE JOB LIST.  A launch of one wave per (window, strip) interleaves the kept strips, all of nearly one length, with as many
+// waves that find an empty range and return at once, and the SIMDs stood empty for 45 % of the roll kernel (1.66 resident
+// waves per SIMD where the dense kernel holds 2.8).  So the pre-pass appends every window's kept STRIPS to a list
+// the tracker owns (PruneJob: window, strip, range, DC level; entry 0 is the header with the batch's count), a window's
+// entries next to each other, and writes itself what the returning wave wrote: the initialised Peak of a strip with an empty
+// hull (its range word, 0, is already its column mask).  The PRUNE instance of dog_roll_kernel takes entry
+// prune_job_index(blockIdx.x) and needs neither the range word nor the DC samples.  No memset, no extra launch, no waiting
+// on the device: one returning atomic per workgroup (the one that counted arrivals before) hands out the list positions, and
+// the last workgroup to arrive publishes the count.  The list's order differs from run to run; results go to [b][s].
 #pragma once
 #include "dog_roll.hpp"
 #include "dog_prune_words.hpp"
@@ -51,8 +62,9 @@ struct PruneGeo {
     double kinv;              // 255 / ‖K‖₂ with ‖K‖₂ rounded up
     float tmax;               // T_max (header comment)
     int darker;               // sign of the cell sums that point at a target
-    unsigned long long *stat; // [0] kept, [1] total (slot, sub-chunk) pairs since the tracker was created, [2] arrivals of the batch in flight
+    unsigned long long *stat; // [0] kept, [1] total (slot, sub-chunk) pairs since the tracker was created, [2] of the batch in flight: arrivals | jobs appended << 32
     uint64_t *host;           // Mailbox::prune_pub, one host-coherent word: the low halves of [0] and ([1] << 32) as the last workgroup of a batch saw them
+    PruneJob *jobs;           // the job list: the header, then room for n · nstrips entries
 };
 
 constexpr int PRUNE_NT = 256;
@@ -101,11 +113,13 @@ __host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots)
 // (Tried: 80 SGPRs at most, for eight resident workgroups per CU instead of six at 106: 35 SGPR spills, the kernel no faster.)
 // REGISTERS.  The next cell's loads in flight cost sixteen VGPRs: 79, six waves per SIMD by the compiler's count.  (Tried:
 // amdgpu_waves_per_eu(7) — 72 VGPRs, five spilled, scratch loads in the cell loop: slower in every run,
-// profiles/prepass_latency_ab.txt.  A second cell in flight would be sixteen more.)
+// profiles/prepass_latency_ab.txt.  A second cell in flight would be sixteen more.)  With the wave that files the job list at
+// the kernel's end the allocator took 82, five waves per SIMD: amdgpu_waves_per_eu(6) holds it to 79 with nothing spilled
+// (profiles/compact_kernel_regs.txt).
 // NARROW: the instance for frames narrower than one clamped load (below), which keeps the byte path; every other frame runs
 // the instance without it.
 template <bool NARROW>
-static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneGeo pg, const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
+static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu(6))) void dog_prune_kernel(const PruneGeo pg, const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col)
 {
     constexpr int NT = PRUNE_NT, NW = NT / 64, CH = ROLL_CH, TW = ROLL_TW, PB = PRUNE_B;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -121,7 +135,7 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
     unsigned *S = reinterpret_cast<unsigned *>(smem + lo.S);       // [nsub][nseg] (Σ p², Σ p)
     f2 *R = reinterpret_cast<f2 *>(smem + lo.R);                   // [PB + l − 1][PB] row-pass outputs of the L pixels
     uint8_t *patch = smem + lo.patch;                              // their input pixels
-    __shared__ int s_sum[NW], s_pmax[NW], s_pmin[NW], s_cv[NW], s_ci[NW], s_cellbest, s_kept, s_nstr;
+    __shared__ int s_sum[NW], s_pmax[NW], s_pmin[NW], s_cv[NW], s_ci[NW], s_cellbest, s_nstr;
     __shared__ double s_emax;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -204,7 +218,7 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         }
     };
 
-    if (tid == 0) { s_kept = 0; s_nstr = 0; }
+    if (tid == 0) s_nstr = 0;
     // ---- the window's DC level: the strips' samples (dc_sample_sum's grid) and rounding.  A thread's samples are requested
     // together at clamped addresses and the fill is selected afterwards; the first cell's loads follow them at once — a
     // cell's moments do not depend on dc — so both are in flight while the segment sums are zeroed and the samples reduced ----
@@ -235,7 +249,7 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         __syncthreads();
         int tot = 0;
         for (int w = 0; w < NW; ++w) tot += s_sum[w];
-        dc = dc_from_sum(tot, g.fill);
+        dc = __builtin_amdgcn_readfirstlane(dc_from_sum(tot, g.fill)); // (workgroup-uniform, and live to the kernel's last lines: a scalar)
     }
     for (int d = tid; d < TQ2; d += NT) {
         int sd = -1;
@@ -528,27 +542,76 @@ static __global__ __launch_bounds__(PRUNE_NT) void dog_prune_kernel(const PruneG
         }
     }
     __syncthreads();
-    for (int sl = tid; sl < g.nslots; sl += NT) {
-        int ba = hull[2 * sl];
-        const int bb = hull[2 * sl + 1];
-        if (bb == 0) ba = 0;
-        g.part_mask[(long long)b * g.nslots + sl] = (unsigned long long)(unsigned)ba | ((unsigned long long)(unsigned)bb << 32);
-        atomicAdd(&s_kept, prune_sc_hi(ba, bb, L, nsub) - ba);
-    }
-    __syncthreads();
     PRUNE_STAMP(7); // hulls
-    if (tid == 0) {
-        __hip_atomic_fetch_add(pg.stat, (unsigned long long)s_kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(pg.stat + 1, (unsigned long long)(g.nslots * nsub), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the last workgroup of the batch publishes both counts where the host sees them without a copy or a wait (the way
-        // dog_finish_kernel publishes its flagged count): one plain store per batch.  (Tried: arrival and kept pairs in ONE
-        // atomic per workgroup instead of three on neighbouring words: the kernel's time did not move.)
-        const unsigned long long arrived = __hip_atomic_fetch_add(pg.stat + 2, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (arrived == (unsigned long long)gridDim.x - 1) {
-            __hip_atomic_store(pg.stat + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long k = __hip_atomic_load(pg.stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), tt = __hip_atomic_load(pg.stat + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(pg.host, (k & 0xffffffffull) | (tt << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // ---- the window's slots are filed by its first wave, 64 at a time: the range words, the finished partial of a strip with
+    // an empty hull, and the window's kept strips as consecutive entries of the job list (header comment) ----
+    if (wave == 0) {
+        int kept = 0, njobs = 0;
+        auto slot_hull = [&](int sl, int &ba, int &bb) {
+            ba = bb = 0;
+            if (sl < g.nslots) {
+                bb = hull[2 * sl + 1];
+                ba = bb == 0 ? 0 : hull[2 * sl];
+            }
+            return sl < g.nstrips && bb > ba; // a job
+        };
+        for (int sl0 = 0; sl0 < g.nslots; sl0 += 64) {
+            const int sl = sl0 + lane;
+            int ba, bb;
+            const bool job = slot_hull(sl, ba, bb);
+            if (sl < g.nslots) {
+                const long long o = (long long)b * g.nslots + sl;
+                // (a remainder column's word carries the DC level: dog_thin_kernel skips its samples.  A strip's word stays
+                // as it was: the word of an empty strip is its column mask, 0)
+                const unsigned lo = (unsigned)ba | (sl < g.nstrips ? 0u : (unsigned)dc << 24);
+                g.part_mask[o] = (unsigned long long)lo | ((unsigned long long)(unsigned)bb << 32);
+                if (sl < g.nstrips && !job) { // what the strip's wave would have left: an initialised Peak
+                    Peak pk;
+                    peak_init(pk);
+                    g.part_val[o] = pk.best;
+                    g.part_idx[o] = pk.idx;
+                    g.part_sec[o] = pk.second;
+                }
+                kept += prune_sc_hi(ba, bb, L, nsub) - ba;
+            }
+            njobs += __builtin_popcountll(__builtin_amdgcn_ballot_w64(job));
         }
+        kept = wave_sum(kept);
+        // One returning atomic per workgroup, as before: stat[2] takes the arrival in its low half and the window's job count in
+        // its high half, and returns how many workgroups arrived before this one and how many jobs they appended — the place of
+        // this window's entries in the list.  The last workgroup of the batch publishes the pair counts where the host sees
+        // them without a copy or a wait (the way dog_finish_kernel publishes its flagged count: one plain store per batch;
+        // every workgroup's additions to stat[0] and stat[1] precede its arrival), writes the batch's job count to the list's
+        // header, where the strips read it, and zeroes stat[2] for the next batch.  The entries themselves are read by the
+        // next kernel in the stream: no order among them and the arrivals is needed.  (Tried: arrival and kept pairs in ONE
+        // atomic per workgroup instead of three on neighbouring words: the kernel's time did not move.  A separate running job
+        // count, a second returning atomic per workgroup: the kernel 5 % slower.)
+        unsigned base = 0;
+        if (lane == 0) {
+            __hip_atomic_fetch_add(pg.stat, (unsigned long long)kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(pg.stat + 1, (unsigned long long)(g.nslots * nsub), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long v = __hip_atomic_fetch_add(pg.stat + 2, 1ull | ((unsigned long long)njobs << 32), __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            base = (unsigned)(v >> 32);
+            if ((unsigned)v == gridDim.x - 1) {
+                __hip_atomic_store(pg.stat + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long k = __hip_atomic_load(pg.stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), tt = __hip_atomic_load(pg.stat + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(pg.host, (k & 0xffffffffull) | (tt << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(&pg.jobs[0].b, (int)(base + (unsigned)njobs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (njobs)
+            for (int sl0 = 0; sl0 < g.nstrips; sl0 += 64) {
+                const int sl = sl0 + lane;
+                int ba, bb;
+                const bool job = slot_hull(sl, ba, bb);
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(job);
+                // (1 + …: entry 0 is the header.  A batch appends at most n · nstrips jobs, the list's room; the test holds a
+                // count that an aborted batch left behind inside it)
+                const unsigned at = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                if (job && at < (unsigned)(g.n * g.nstrips)) pg.jobs[1 + at] = PruneJob{b, sl | (dc << 16), ba, bb};
+                base += (unsigned)__builtin_popcountll(m);
+            }
     }
     PRUNE_STAMP(8); // publish
 #ifdef PDOG_ABLATIONS

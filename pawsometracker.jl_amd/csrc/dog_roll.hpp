@@ -95,6 +95,16 @@ __host__ __device__ constexpr int prune_span(int L) { return (ROLL_CH + L - 1 + 
 __host__ __device__ constexpr int prune_tail(int L) { return (L - 1 + ROLL_CH - 1) / ROLL_CH; }
 __host__ __device__ constexpr int prune_sc_hi(int ba, int bb, int L, int nsub) { return bb > ba ? (bb + prune_tail(L) < nsub ? bb + prune_tail(L) : nsub) : ba; }
 
+// Which entry of the job list workgroup `blk` of a PRUNE launch takes.  Consecutive workgroups go to consecutive XCDs, so
+// blk & 7 is the XCD and blk >> 3 the workgroup's turn on it: the list is dealt out in groups of G = 2^k consecutive entries
+// (LaunchGeo::prune), group after group over all eight XCDs — a list of any length is spread evenly, and with G > 1 a
+// window's neighbouring entries mostly share an L2.  A bijection on [0, grid) for a grid that is a multiple of 8·G.
+__host__ __device__ constexpr int prune_job_index(int blk, int G)
+{
+    const unsigned turn = (unsigned)blk >> 3, xcd = (unsigned)blk & 7u, g = (unsigned)G;
+    return (int)((turn / g * 8u + xcd) * g + turn % g);
+}
+
 // Re-derive a tap pointer through an empty asm: the scalar loads that use it cannot be hoisted above
 // this point (hoisted, every block's taps are live at once and the SGPRs spill through v_writelane).
 // A fake use + redefinition of an accumulator pair: the FMAs that feed it cannot be sunk below this
@@ -236,6 +246,28 @@ __host__ __device__ constexpr int roll_prologue_blocks(int sc) { return 2 * sc +
 __host__ __device__ constexpr int roll_epi_c0(int n1) { return (n1 + 2) / 4; }
 __host__ __device__ constexpr int roll_epi_class(int n1, int L) { return roll_epi_c0(n1) % (2 * (roll_slots(L) / ROLL_CH)); }
 __host__ __device__ constexpr int roll_prologue_len(int L) { return (roll_col_blocks(L) - 2 + 1) / 2; } // sub-chunks with fewer blocks than the full body
+// The shortened bodies at the START of a run of sub-chunks (a window's top; a kept range's first sub-chunk, roll_strip):
+// sub-chunk j of the run, rows a = 8j … 8j + 7 counted from its first row, runs tap blocks 0 … roll_prologue_blocks(j) − 1
+// (all of them from j = roll_prologue_len on).  True iff those blocks hold every tap t of every output y = a − t ≥ 0 of the
+// run, i.e. of every output at or below the run's first row.  Row a (parity p) meets tap t in the pair (T[tt], T[tt − 1]),
+// tt = t or t + 1 with tt ≡ p mod 2, which lies in block (tt − p) ÷ 2 ÷ ROLL_QB (roll_col_body).
+__host__ __device__ constexpr bool roll_start_covers(int L)
+{
+    for (int j = 0; j < roll_prologue_len(L); ++j) {
+        const int nblk = roll_prologue_blocks(j) < roll_col_blocks(L) ? roll_prologue_blocks(j) : roll_col_blocks(L);
+        for (int i = 0; i < ROLL_CH; ++i) {
+            const int a = ROLL_CH * j + i, p = a & 1;
+            for (int t = 0; t <= a && t <= L - 1; ++t) {
+                const int tt = ((t ^ p) & 1) ? t + 1 : t;
+                if ((tt - p) / 2 / ROLL_QB >= nblk) return false;
+            }
+        }
+    }
+    return true;
+}
+#define PDOG_ROLL_L(LT) static_assert(roll_start_covers(LT), "a shortened prologue body leaves out a tap of an output inside the range");
+#include "roll_lengths.def"
+#undef PDOG_ROLL_L
 // QLO > 0: an EPILOGUE body, blocks QLO … only: the last input rows a > n1−1 have no output below row n1−1 to feed,
 // rows a … a+7 only need taps t ≥ a − (n1−1).  Down there sub-chunk and phase are tied through the window height, so
 // these bodies exist per HEIGHT CLASS (roll_epi_class) — instances for the common window sizes only.
@@ -321,7 +353,8 @@ __device__ __forceinline__ void roll_col_zero(f2 (&acc2)[roll_slots(L) / 2])
 template <int LT, bool RESP, int ABL, int EPI = -1, bool PRUNE = false>
 __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restrict__ taps_row, const f2 *__restrict__ taps_col,
                                            unsigned char *smem, const uint8_t *__restrict__ frame, int g1, int g2, int s,
-                                           int b, int logical, Peak &peak_out, unsigned long long &mask_out)
+                                           int b, int logical, Peak &peak_out, unsigned long long &mask_out, int job_ba = 0, int job_bb = 0,
+                                           int job_dc = 0)
 {
     constexpr int L = LT, hw = L / 2, S = roll_slots(L), CH = ROLL_CH, P = ROLL_P, TW = ROLL_TW;
     constexpr int NBODY = S / CH;
@@ -347,26 +380,16 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     const int tj0 = wj0 + x0;
     const int NA = g.n1 + L - 1;
 
-    // ---- kept range (dog_prune.hpp), read ahead of everything else: a slot with an empty range leaves an initialised partial
-    // and mask 0 at once, without taking its share of the window's DC samples from the frame ----
-    int prune_ba = 0, prune_bb = 0;
-    if constexpr (PRUNE) {
-        const unsigned long long rng = g.part_mask[(long long)b * g.nslots + s];
-        prune_ba = __builtin_amdgcn_readfirstlane((int)(unsigned)rng);
-        prune_bb = __builtin_amdgcn_readfirstlane((int)(unsigned)(rng >> 32));
-        if (prune_bb <= prune_ba) {
-            Peak pk;
-            peak_init(pk);
-            peak_wave_reduce(pk);
-            peak_out = pk;
-            mask_out = 0ull;
-            return;
-        }
-    }
+    // ---- kept range (dog_prune.hpp): the strip's job carries it (never empty: the pre-pass itself leaves the partial and
+    // mask 0 of a strip with an empty hull) ----
+    const int prune_ba = PRUNE ? job_ba : 0, prune_bb = PRUNE ? job_bb : 0;
 
-    // ---- per-window DC level (see dog_kernels.hpp): same samples in every strip ----
+    // ---- per-window DC level (see dog_kernels.hpp): same samples in every strip; a job carries the pre-pass's, which is
+    // dc_from_sum of the same samples ----
     int dc;
-    {
+    if constexpr (PRUNE) {
+        dc = job_dc;
+    } else {
         int sum = dc_sample_sum(g, frame, ti0, wj0, L, lane, 64);
         sum = wave_sum(sum);
         dc = dc_from_sum(sum, g.fill);
@@ -402,7 +425,7 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     // ---- folded remainder column (LaunchGeo::fold_r): the last strip's row pass also produces window column 64·nstrips.
     // Its last input is strip column TW + L − 1; where the 8·SB staged columns end one short of it (l = 33, 65, 97, 129)
     // the lanes of the last segment stage that one byte more, into the slack of the A row ----
-    constexpr bool FOLD_OK = !RESP && ABL == 0 && roll_folds(L);
+    constexpr bool FOLD_OK = !RESP && ABL == 0 && !PRUNE && roll_folds(L); // (a pruned launch never folds; LaunchGeo::fold_r is its job list)
     constexpr bool FOLD_EXTRA = (8 * SB < TW + L);
     const bool fold = FOLD_OK && g.fold_r != nullptr && s == g.nstrips - 1; // wave-uniform
     const int xcol = tj0 + 8 * SB;                                          // frame col of the extra byte
@@ -447,12 +470,19 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     // [sc_lo, sc_hi) that hold the input rows of the kept output blocks.  Outputs above row y_lo = 8·sc_lo lack their first
     // terms and are not fed to the peak; every output from y_lo on that the loop emits is complete (its last input row,
     // y + l − 1, lies in the sub-chunk that emits it), so the few rows it may emit past the range's end are the window's own
-    // values and harmless.  Starting late needs no reset (every output's first term is a multiply), and the shortened
-    // prologue bodies stay right: they are chosen by the sub-chunk NUMBER and leave out only taps whose outputs lie above row 0 ----
+    // values and harmless.  Starting late needs no reset (every output's first term is a multiply).
+    // BODIES THAT MATCH THE RANGE'S START.  A PRUNE instance numbers its sub-chunks from sc_lo on (`rel`): the phase, the
+    // prologue switch, the slot rotation of the emit part and roll_col_zero all take the relative number, so output y sits in
+    // slot (y − y_lo) mod S and the first sub-chunks of EVERY kept range run the shortened prologue bodies — in sub-chunk
+    // sc_lo + j only tap blocks 0 … 2j + 1 feed outputs at or below y_lo, the rest would scatter into slots whose outputs are
+    // withheld from the peak anyway (the triangle the prologue bodies leave out at a window's top; roll_start_covers above
+    // checks the blocks for every length).  The bits do not change: every output from y_lo on still receives its terms
+    // t = 0, 1, … in order, in another register.  ybase, pad_sc, the staging rows and the counts keep the absolute number.
+    // (The END of a range still runs full-length bodies: the rows past 8·bb it feeds are emitted whole and harmless.) ----
     static_assert(!PRUNE || (!RESP && ABL == 0 && EPI < 0), "kept ranges: the plain instances only");
     int sc_lo = 0, sc_hi = nsub, y_lo = 0;
     if constexpr (PRUNE) {
-        sc_lo = prune_ba; // (read above, ahead of the DC level)
+        sc_lo = prune_ba;
         sc_hi = prune_sc_hi(prune_ba, prune_bb, L, nsub);
         y_lo = prune_ba * CH;
     }
@@ -521,7 +551,8 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
 #pragma unroll
             for (int i = 0; i < CH; ++i) rv[i] = Rb[i * ROLL_PR + lane];
         }
-        const int phase = sc % NBODY;
+        const int rel = PRUNE ? sc - sc_lo : sc; // the number that picks the body (kept ranges: above)
+        const int phase = rel % NBODY;
         const int sc_e = roll_epi_c0(g.n1) / 2 + 1; // first sub-chunk whose rows need no tap of the first block(s)
         auto emit = [&](auto SCc, auto QHIc, auto QLOc) {
             constexpr int SC = decltype(SCc)::value, QHI = decltype(QHIc)::value, QLO = decltype(QLOc)::value;
@@ -571,8 +602,8 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
                 }
 #undef PDOG_EPI
             }
-        } else if (sc < NPRO) { // the first rows: shortened bodies (sub-chunk = phase)
-            switch (sc) {
+        } else if (rel < NPRO) { // the first rows: shortened bodies (sub-chunk = phase)
+            switch (rel) {
                 PDOG_PRO(0) PDOG_PRO(1) PDOG_PRO(2) PDOG_PRO(3) PDOG_PRO(4) PDOG_PRO(5) PDOG_PRO(6) PDOG_PRO(7)
                 PDOG_PRO(8) PDOG_PRO(9) PDOG_PRO(10) PDOG_PRO(11) PDOG_PRO(12) PDOG_PRO(13) PDOG_PRO(14) PDOG_PRO(15)
                 PDOG_PRO(16) PDOG_PRO(17) PDOG_PRO(18) PDOG_PRO(19)
@@ -646,18 +677,35 @@ __global__ __launch_bounds__(64, roll_waves(LT)) void dog_roll_kernel(const Laun
                                                                       const f2 *__restrict__ taps_col)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // XCD-aware block → (window, strip), see dog_kernels.hpp
-    const int per_xcd = (g.nblocks + 7) >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (logical >= g.nblocks) return;
-    const int b = logical / g.nstrips;
-    const int s = logical - b * g.nstrips;
+    int logical, b, s, ba = 0, bb = 0, dc = 0;
+    if constexpr (PRUNE) {
+        // THE JOB LIST (dog_prune.hpp): the workgroup takes one kept strip of the pre-pass's list.  The grid is the host's
+        // upper bound; the workgroups past the list's end return, and they all sit at the END of the grid — the kept waves,
+        // all of nearly one length, start back to back and fill the SIMDs, where one wave per (window, strip) in index
+        // order interleaved them with as many waves that returned at once.  Results go to [b][s] whatever the list's order.
+        logical = prune_job_index((int)blockIdx.x, g.prune);
+        const int count = min(g.jobs[0].b, g.nblocks);
+        if (logical >= count) return;
+        const PruneJob job = g.jobs[1 + logical];
+        b = job.b;
+        s = job.s_dc & 0xffff;
+        dc = (job.s_dc >> 16) & 0xff;
+        ba = job.ba;
+        bb = job.bb;
+    } else {
+        // XCD-aware block → (window, strip), see dog_kernels.hpp
+        const int per_xcd = (g.nblocks + 7) >> 3;
+        logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+        if (logical >= g.nblocks) return;
+        b = logical / g.nstrips;
+        s = logical - b * g.nstrips;
+    }
     const int g1 = g.guesses[2 * b], g2 = g.guesses[2 * b + 1];
     const int fidx = g.frame_index ? g.frame_index[b] : b;
     const uint8_t *__restrict__ frame = g.frames + (long long)fidx * g.frame_stride;
     Peak pk;
     unsigned long long mask;
-    roll_strip<LT, RESP, ABL, EPI, PRUNE>(g, taps_row, taps_col, smem, frame, g1, g2, s, b, logical, pk, mask);
+    roll_strip<LT, RESP, ABL, EPI, PRUNE>(g, taps_row, taps_col, smem, frame, g1, g2, s, b, logical, pk, mask, ba, bb, dc);
     if (threadIdx.x == 0) {
         g.part_mask[b * g.nslots + s] = mask;
         g.part_val[b * g.nslots + s] = pk.best;
@@ -916,9 +964,12 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
     // ---- kept range (dog_prune.hpp), read ahead of the DC level: output rows [y_lo, y_hi) and the input rows [a_lo, a_hi)
     // they read; an empty range (the same for the whole workgroup) leaves an initialised Peak at once ----
     int a_lo = 0, a_hi = NA, y_lo = 0, y_hi = g.n1;
-    if (!RESP && g.prune) {
+    int dc = 0;
+    const bool pruned = !RESP && g.prune;
+    if (pruned) {
         const unsigned long long rng = g.part_mask[(long long)b * g.nslots + g.nstrips + rc];
-        const int ba = (int)(unsigned)rng, bb = (int)(unsigned)(rng >> 32);
+        const int ba = (int)((unsigned)rng & 0xffffffu), bb = (int)(unsigned)(rng >> 32);
+        dc = (int)(((unsigned)rng >> 24) & 0xffu); // the pre-pass's dc_from_sum of the same samples: no sampling here
         if (bb <= ba) {
             if (tid == 0) {
                 Peak pk;
@@ -934,8 +985,7 @@ __global__ __launch_bounds__(256) void dog_thin_kernel(const LaunchGeo g, const 
         a_lo = y_lo;
         a_hi = y_hi + L - 1;
     }
-    int dc;
-    {
+    if (!pruned) {
         int sum = dc_sample_sum(g, frame, ti0, wj0, L, tid, NT);
         sum = wave_sum(sum);
         if (lane == 0) ssum[wave] = sum;

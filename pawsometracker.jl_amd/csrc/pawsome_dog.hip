@@ -326,7 +326,8 @@ struct pdog_tracker {
     // kept ranges on the roll family's batch path (dog_prune.hpp; pdog_policy.hpp)
     PrunePolicy prune_policy;
     double K_norm = 0;                       // ‖K‖₂ of the dense kernel, rounded up (dog_kernel_norm_up)
-    DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] arrivals of the pre-pass in flight
+    DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] arrivals of the pre-pass in flight | jobs it has appended << 32
+    DeviceBuffer<PruneJob> d_prune_jobs;     // the kept strips of the batch in flight: the header, then up to n·nstrips entries (dog_prune.hpp, "the job list")
     int last_n = 0, last_nslots = 0;         // windows and partial slots per window of the last launch_strips batch (pdog_get_batch_maxima)
     DeviceBuffer<float> d_map; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
     DeviceBuffer<int> d_dc;    // [cap] DC levels, then [cap] the windows' own V (exact mode)
@@ -1187,6 +1188,13 @@ int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticke
 }
 
 // ---- pruning policy (dog_prune.hpp; PrunePolicy, pdog_policy.hpp) ----
+// Consecutive entries of the job list that go to one XCD (LaunchGeo::prune, prune_job_index): 1 deals the list out entry by
+// entry.
+#ifndef PDOG_PRUNE_XCD_GROUP
+#define PDOG_PRUNE_XCD_GROUP 1
+#endif
+constexpr int kPruneXcdGroup = PDOG_PRUNE_XCD_GROUP;
+static_assert(kPruneXcdGroup >= 1 && (kPruneXcdGroup & (kPruneXcdGroup - 1)) == 0, "a power of two");
 constexpr size_t kPruneMaxLds = 64 * 1024; // (the pre-pass's dynamic LDS without raising the kernel's limit; larger windows stay dense)
 bool use_pruning(pdog_tracker *t, const Variant &v, bool want_resp, int nslots)
 {
@@ -1202,7 +1210,7 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
 {
     const Variant &v = *t->var;
     const int n = req.n;
-    const int grid = round_up(g.nblocks, 8);
+    int grid = round_up(g.nblocks, 8);
     // Exact mode: batches whose predecessors flagged many of their windows write their responses, and the finishing kernel
     // reads its candidates off that map (MapPolicy, pdog_policy.hpp).  The counts come through host-coherent memory: nothing
     // here waits for the GPU.
@@ -1236,9 +1244,12 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         pg.darker = t->darker;
         pg.stat = t->d_prune_stat.get();
         pg.host = &t->h_pinned.device()->prune_pub;
+        if (int rc = t->d_prune_jobs.reserve((size_t)g.nblocks + 1, &t->stream)) return rc;
+        pg.jobs = t->d_prune_jobs.get();
         hipLaunchKernelGGL(t->fw < 8 ? dog_prune_kernel<true> : dog_prune_kernel<false>, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
         HIP_TRY(hipGetLastError());
-        g.prune = 1;
+        g.prune = kPruneXcdGroup;
+        grid = round_up(g.nblocks, 8 * kPruneXcdGroup); // (prune_job_index maps whole groups)
     }
     if (fold) {
         if (int rc = t->d_fold_r.reserve((size_t)n * NA, &t->stream)) return rc;
@@ -1266,7 +1277,11 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         PDOG_EPI_CLASSES(PDOG_EPI_PICK)
 #undef PDOG_EPI_PICK
     }
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(v.NT), lds_bytes, t->stream, g, tr, v.roll ? (const f2 *)t->d_taps_roll.get() : tc);
+    {
+        LaunchGeo gs = g; // (the finishing kernel reads fold_r: the job list is the strips' alone)
+        if (prune) gs.jobs = t->d_prune_jobs.get();
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(v.NT), lds_bytes, t->stream, gs, tr, v.roll ? (const f2 *)t->d_taps_roll.get() : tc);
+    }
     HIP_TRY(hipGetLastError());
     if (t->nthin && !fold) HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0)); // join before the strip combine
     // roll: 64-column strips over the first `covered` columns, the last one shifted left to stay inside; ring: tw() columns each

@@ -44,7 +44,8 @@ private:
 // (Since the pre-pass forms its energies from raw-pixel moments it takes 0.331 ms, 25 % of the dense roll kernel:
 // profiles/prepass_profile_this.txt.  The constant has not followed yet: bench data at ±40 levels keeps 76 % of its pairs,
 // right at the share that ratio would give, and whether pruning pays there is unmeasured — profiles/prepass_ab.txt.
-// With clamped loads and the next cell's loads in flight: 0.302 ms, 23 % — profiles/prepass_latency_ab.txt.)
+// With clamped loads and the next cell's loads in flight: 0.302 ms, 23 % — profiles/prepass_latency_ab.txt.
+// With the job list, which the pre-pass also files: 0.306 ms, still 23 % — profiles/compact_ab.txt.)
 // The pre-pass publishes its cumulative kept / total counts in one word (Mailbox::prune_pub); when the pairs counted since the
 // last look kept more than the break-even share, the next kPruneProbeEvery batches run dense, then one batch probes again.
 constexpr int kPrunePrePct = 36;
