@@ -417,5 +417,7 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
 /* the overlay over a frame table and for several targets: pdog_diag_set_targets, pdog_diag_get_targets,
  * pdog_diag_render_indexed.  On a handle set to several targets pdog_diag_render above returns PDOG_E_ARG. */
 #include "pawsome_overlay.h"
+/* a static background model — the per-pixel median of some frames — and frames with it subtracted: pdog_bg_* */
+#include "pawsome_background.h"
 
 #endif /* PAWSOME_DOG_H */

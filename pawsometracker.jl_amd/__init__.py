@@ -9,3 +9,4 @@ from .tracker import (DEFAULT_STOP, Tracker, fix_window_size, fps_table, get_gue
                       track_segments, track_video)
 from .batch import BatchTracker, GroupTracker, gather_positions, mode_device, shard_range  # noqa: F401
 from .diagnose import DIAG_MAX_TARGETS, DIAG_SIZE, Diagnose, diag_point  # noqa: F401
+from .background import BG_MAX_SAMPLES, Background, background_samples  # noqa: F401

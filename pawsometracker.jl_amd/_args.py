@@ -141,6 +141,23 @@ def host_steps(v, name):
     return host_table(a[None, :], name)[0]
 
 
+def background_k(k, name="k"):
+    """A number of background samples: an integer 1 ... 64 (PDOG_BG_MAX_SAMPLES)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer, not {type(k).__name__}")
+    if not 1 <= k <= 64:
+        raise ValueError(f"{name}: {k} lies outside 1 ... 64")
+    return int(k)
+
+
+def host_samples(v, name):
+    """The sample list of a background estimate: host_steps' row, of 1 ... 64 entries.  The entries are the library's to judge."""
+    a = host_steps(v, name)
+    if not 1 <= len(a) <= 64:
+        raise ValueError(f"{name}: {len(a)} samples, 1 ... 64 expected")
+    return a
+
+
 def device_positions(t, name, n_steps, device=None):
     """Positions of several targets as the overlay reads them: an int32 cuda tensor [n_targets, n_steps, 2] whose pairs and steps
     lie densely (strides 1 and 2) and whose targets lie an even number of words >= 2 * n_steps apart — a column slice

@@ -155,6 +155,20 @@ PREDICT_PROTOTYPES = {
     "pdog_get_predict_counts": (_i, [_p, _pu64]),
 }
 PREDICT_SYMBOLS = tuple(PREDICT_PROTOTYPES)
+
+# the same for include/pawsome_background.h, the fourth header pawsome_dog.h includes: a static background model and frames
+# with it subtracted (tests/test_background_cpu.py holds this table against that header)
+BACKGROUND_PROTOTYPES = {
+    "pdog_bg_create": (_i, [_i, _i, _i, _pp]),
+    "pdog_bg_destroy": (_i, [_p]),
+    "pdog_bg_samples": (_i, [_p, _i, _i, _p, _i, _pi]),
+    "pdog_bg_estimate": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _i]),
+    "pdog_bg_set": (_i, [_p, _p, _p, _i64]),
+    "pdog_bg_get": (_i, [_p, _p, _p, _i64]),
+    "pdog_bg_subtract_indexed": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _i, _p, _i64, _i64]),
+}
+BACKGROUND_SYMBOLS = tuple(BACKGROUND_PROTOTYPES)
+BG_MAX_SAMPLES = 64          # PDOG_BG_MAX_SAMPLES
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -200,7 +214,7 @@ def lib():
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
-                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES}.items():
+                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -378,7 +378,8 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
+                min_distance=None, background=None, background_chunk=256, predict=False, motion=False, coast=None, min_response=None,
+                exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -422,11 +423,29 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     where the plain loop is one launch — every target's window is centred on where its last displacement predicts it, and a
     target whose window offers nothing above `min_response` (None: 0.0) coasts for `coast` steps (None: 8) and then waits.
     Nothing keeps two targets apart.  The result gains the trailing `state`: 0 for the bootstrap, 1 assigned, -1 held.
-    ValueError for predict together with motion or exclusive."""
+    ValueError for predict together with motion or exclusive.
+    `background` removes a STATIC BACKGROUND first (this library's addition; include/pawsome_background.h states the rule): an
+    int K (1 ... 64) estimates the per-pixel lower median of background_samples(table, K) of the selected frames, a uint8 cuda
+    tensor [h, w] is taken as the model itself (the empty arena).  The tracker then sees only the subtracted video,
+    clamp(128 + frame - model, 0, 255): the fill is the mode of the first subtracted selected frame, the bootstrap (n_targets
+    included) runs on that frame and the loop — plain, exclusive, motion or predict — on the subtracted frames, which exist at
+    most `background_chunk` steps at a time in one reused buffer: chunk 0 starts from the bootstrap, every later chunk from the
+    chunk before it (its last positions and, for motion and predict, its mstate), so the result does not depend on
+    background_chunk.  subpixel measures on the subtracted frames; diagnostic draws on the original ones.  ValueError for
+    background_chunk without background and for K outside 1 ... 64."""
     import torch
-    from ._args import exclusive_args, motion_args, peaks_args, predict_args
+    from ._args import background_k, device_frames, exclusive_args, motion_args, peaks_args, predict_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
+    if isinstance(background_chunk, bool) or not isinstance(background_chunk, (int, np.integer)):
+        raise TypeError("background_chunk must be an integer")
+    if background_chunk < 1:
+        raise ValueError(f"background_chunk: {background_chunk} is not a positive number of steps")
+    if background is None:
+        if background_chunk != 256:
+            raise ValueError("background_chunk belongs to background")
+    elif not isinstance(background, torch.Tensor):
+        background = background_k(background, "background")
     if n_targets is not None:
         if start_locations is not None:
             raise ValueError("n_targets finds the targets itself: give it, or start_locations, not both")
@@ -470,20 +489,52 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
         window_size = guess_window_size(target_width)            # :136
     window_size = fix_window_size(window_size)                   # :142
     dev = frames.device
+    if isinstance(background, torch.Tensor):
+        device_frames(background, "background", 2, (h, w), dev.index)
+    bstep = int(background_chunk)
+
+    def walk(bt, fr, tab, starts, first, mstate):
+        """One call of the loop the keywords chose over the steps `tab` of the stack `fr`: (positions [nt, len(tab), 2], state
+        or None, mstate or None)."""
+        if exclusive:    # all targets as ONE group: excl is the rule's (k, min_distance, min_ratio[, min_response, coast])
+            o, st = bt.detect_chains_exclusive(fr, tab[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None, *excl[2:], first=first)
+            return o[0], st[0], None
+        if motion:
+            o, st, ms = bt.detect_chains_motion(fr, tab[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None, *excl[2:],
+                                                first=first, mstate=mstate)
+            return o[0], st[0], ms
+        if predict:
+            return bt.detect_chains_predicted(fr, np.tile(tab, (nt, 1)), starts, *pred, mstate=mstate, first=first)
+        return bt.detect_chains_indexed(fr, np.tile(tab, (nt, 1)), starts, first=first), None, None
+
     with torch.cuda.device(dev):
-        f0 = int(table[0])
-        fill = mode_device(frames[f0])                           # :159, :47
-        bt = BatchTracker(h, w, target_width, window_size, darker_target, fill, device=dev.index)
+        bg = buf = None
+        seen, f0 = frames, int(table[0])          # the stack the tracker sees, and its first selected frame in it
+        if background is not None:
+            from .background import Background
+            bg = Background(h, w, dev.index)
+        bt = None
         try:
+            if bg is not None:
+                if isinstance(background, torch.Tensor):
+                    bg.set(background)
+                else:
+                    from .background import background_samples
+                    bg.estimate(frames, background_samples(table, background))
+                buf = torch.empty((min(bstep, m), h, w), dtype=torch.uint8, device=dev)
+                bg.subtract(frames, table[:len(buf)], out=buf)              # chunk 0: its first frame is the bootstrap frame
+                seen, f0 = buf, 0
+            fill = mode_device(seen[f0])                                 # :159, :47
+            bt = BatchTracker(h, w, target_width, window_size, darker_target, fill, device=dev.index)
             # the first positions, :92-107: one functor application per target on the first selected frame
-            guesses = torch.tensor([get_guess(loc, frames[f0], sar) for loc in locs], dtype=torch.int32, device=dev).reshape(nt, 2)
+            guesses = torch.tensor([get_guess(loc, frames[0], sar) for loc in locs], dtype=torch.int32, device=dev).reshape(nt, 2)
             on_f0 = torch.full((nt,), f0, dtype=torch.int32, device=dev)
-            starts = bt.detect(frames, guesses, on_f0)                                                    # :95
+            starts = bt.detect(seen, guesses, on_f0)                                                      # :95
             auto = torch.tensor([loc is None for loc in locs], device=dev)
             if n_targets is not None:
                 bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, fill, device=dev.index)   # :102-103
                 try:
-                    ij, peak, _ = bt4.detect_peaks(frames, guesses[:1], n_targets, md or None, on_f0[:1])         # :104, and K - 1 more
+                    ij, peak, _ = bt4.detect_peaks(seen, guesses[:1], n_targets, md or None, on_f0[:1])           # :104, and K - 1 more
                     bt4.sync()
                 finally:
                     bt4.close()
@@ -495,23 +546,34 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             elif bool(auto.any()):
                 bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, fill, device=dev.index)   # :102-103
                 try:
-                    starts = torch.where(auto[:, None], bt4.detect(frames, guesses, on_f0), starts).contiguous()  # :104
+                    starts = torch.where(auto[:, None], bt4.detect(seen, guesses, on_f0), starts).contiguous()    # :104
                     bt4.sync()           # a guess outside the padded frame raises here, like the reference's BoundsError
                 finally:
                     bt4.close()
             # the loop from the second selected frame on, :161-167: every target over the same table
-            state = None
-            if exclusive or motion:      # all targets as ONE group: excl is the rule's (k, min_distance, min_ratio[, min_response, coast])
-                walk = bt.detect_chains_motion if motion else bt.detect_chains_exclusive
-                out, state = (r[0] for r in walk(frames, table[None, :], starts.unsqueeze(0).contiguous(), None, excl[1] or None, *excl[2:], first=1)[:2])
-            elif predict:
-                out, state, _ = bt.detect_chains_predicted(frames, np.tile(table, (nt, 1)), starts, *pred, first=1)
-            else:
-                out = bt.detect_chains_indexed(frames, np.tile(table, (nt, 1)), starts, first=1)
             sub = None
-            if subpixel:
-                fi = torch.from_numpy(np.tile(table, nt)).to(dev)
-                sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
+            if bg is None:
+                out, state, _ = walk(bt, frames, table, starts, 1, None)
+                if subpixel:
+                    fi = torch.from_numpy(np.tile(table, nt)).to(dev)
+                    sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
+            else:                        # the same over the subtracted frames, a buffer of them at a time
+                out = torch.zeros((nt, m, 2), dtype=torch.int32, device=dev)
+                state = torch.zeros((nt, m), dtype=torch.int32, device=dev) if exclusive or motion or predict else None
+                sub = torch.empty((nt, m, 2), dtype=torch.float64, device=dev) if subpixel else None
+                mstate = None
+                for k0 in range(0, m, bstep):
+                    nk = min(bstep, m - k0)
+                    if k0:
+                        bg.subtract(frames, table[k0:k0 + nk], out=buf[:nk])     # (behind the last chunk's walk, in stream order)
+                        starts = out[:, k0 - 1].contiguous()
+                    o, st, mstate = walk(bt, buf[:nk], np.arange(nk, dtype=np.int32), starts, 0 if k0 else 1, mstate)
+                    out[:, k0:k0 + nk] = o
+                    if state is not None:
+                        state[:, k0:k0 + nk] = st
+                    if subpixel:
+                        fi = torch.from_numpy(np.tile(np.arange(nk, dtype=np.int32), nt)).to(dev)
+                        sub[:, k0:k0 + nk] = bt.measure(buf[:nk], o.reshape(-1, 2).contiguous(), fi).view(nt, nk, 2)
             bt.sync()                    # what the kernels raised (PdogError) surfaces before the positions are handed out
             if diagnostic is not None:
                 from .diagnose import Diagnose
@@ -521,4 +583,7 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             res = (ts, out, sub) if subpixel else (ts, out)
             return res + (state,) if exclusive or motion or predict else res
         finally:
-            bt.close()
+            if bt is not None:
+                bt.close()
+            if bg is not None:
+                bg.close()
