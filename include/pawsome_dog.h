@@ -361,9 +361,15 @@ int pdog_group_detect_batch(pdog_group *g, const uint8_t *const *d_frames, int64
                             const int32_t *const *d_guesses, int n_total, int32_t *d_out_ij);
 /* Waits for EVERY rank (each rank's raised flags are reported and cleared); returns the first error. */
 int pdog_group_sync(pdog_group *g);
-/* Test hook: runs the copy kernel that compacts the gathered blocks of unequal shards (d_gathered: int32[ndev][⌈n_total/ndev⌉][2],
- * d_out: int32[n_total][2], both on the current device) — the one step of pdog_group_detect_batch a one-GPU box cannot reach. */
+/* Test hooks (not stable ABI).  The first runs the copy kernel that compacts the gathered blocks of unequal shards on buffers
+ * of the caller's (d_gathered: int32[ndev][⌈n_total/ndev⌉][2], d_out: int32[n_total][2], both on the current device).  The
+ * second creates a group whose nranks (1 … 64) trackers ALL live on `device`, each with its own stream, and whose gather is a
+ * stream-ordered stand-in inside this library (events and device-to-device copies on the root's stream; RCCL is not opened):
+ * every other pdog_group_* call takes the handle as it takes pdog_group_create's and runs the same code, so the per-rank loop,
+ * the gather's protocol and the compaction run with more than one rank on a one-GPU box.  No byte crosses between two GPUs. */
 int pdog_group_test_compact(const int32_t *d_gathered, int n_total, int ndev, int32_t *d_out);
+int pdog_group_test_create_local(int nranks, int device, int frame_h, int frame_w, double target_width,
+                                 int win_h, int win_w, int darker_target, int fill, pdog_group **out);
 
 /* ---- diagnostic overlay (the reference's `Diagnose`, src/diagnose.jl) ----
  * For every frame the reference's dia(img, point) (:30-38) runs on, it resizes the frame into a 360 x 640

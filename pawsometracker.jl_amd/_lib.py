@@ -82,6 +82,7 @@ PROTOTYPES = {
     "pdog_group_detect_batch": (_i, [_p, _p, _i64, _i64, _p, _p, _p, _i, _p]),
     "pdog_group_sync": (_i, [_p]),
     "pdog_group_test_compact": (_i, [_p, _i, _i, _p]),
+    "pdog_group_test_create_local": (_i, [_i, _i, _i, _i, _d, _i, _i, _i, _i, _pp]),
     "pdog_diag_create": (_i, [_i, _i, _pp]),
     "pdog_diag_destroy": (_i, [_p]),
     "pdog_diag_point": (_i, [_i, _i, _p, _p]),

@@ -451,6 +451,18 @@ class GroupTracker(_lib.Handle):
                                          int(bool(darker_target)), int(fill)), "pdog_group_destroy")
         self.frame_h, self.frame_w = int(frame_h), int(frame_w)
 
+    @classmethod
+    def local(cls, n_ranks, frame_h, frame_w, target_width, window_size, darker_target, fill, device=0):
+        """Tests: a group of n_ranks trackers that all live on `device`, each with its own stream, whose gather is the
+        library's stream-ordered stand-in instead of RCCL (pdog_group_test_create_local).  Everything else is the same code."""
+        self = cls.__new__(cls)
+        self.devices = [int(device)] * int(n_ranks)
+        _lib.Handle.__init__(self, _lib.new_handle(_lib.lib().pdog_group_test_create_local, int(n_ranks), int(device), int(frame_h),
+                                                   int(frame_w), float(target_width), int(window_size[0]), int(window_size[1]),
+                                                   int(bool(darker_target)), int(fill)), "pdog_group_destroy")
+        self.frame_h, self.frame_w = int(frame_h), int(frame_w)
+        return self
+
     def size(self):
         return _lib.lib().pdog_group_size(self._h)
 

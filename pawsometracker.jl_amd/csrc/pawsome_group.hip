@@ -8,9 +8,14 @@
 // enqueued on each rank's tracker stream right behind its kernels (8 B per window: latency-bound over xGMI, no
 // data-path collective).  Shards differ by at most one window, so the gather sends max-shard-sized blocks and a
 // copy kernel on the root compacts them when n_total is not a multiple of the group size.
+//
+// The six collective calls go through a table (struct Rccl) that the group points to.  pdog_group_create installs librccl's;
+// the test entry pdog_group_test_create_local installs a stand-in that keeps every rank on ONE device (below), so that the
+// per-rank loop, the gather's protocol and the compaction run with ndev > 1 where there is one GPU.  Everything behind the
+// create calls is the same code for both.
 #include "pdog_host.hpp"
+#include "pdog_dl.hpp"
 #include <rccl/rccl.h>   // types and prototypes only: the library is opened when the first group is created (below)
-#include <dlfcn.h>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -37,26 +42,172 @@ Rccl &rccl()
     static Rccl r;
     static std::once_flag once;
     std::call_once(once, [] {
-        for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            r.handle = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (r.handle) break;
+        pdog::DlLibrary lib;
+        lib.open_first("librccl", std::initializer_list<const char *>{"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"});
+        if (lib.handle) {
+            r.CommInitAll = (decltype(r.CommInitAll))lib.symbol("librccl", "ncclCommInitAll");
+            r.CommDestroy = (decltype(r.CommDestroy))lib.symbol("librccl", "ncclCommDestroy");
+            r.GroupStart = (decltype(r.GroupStart))lib.symbol("librccl", "ncclGroupStart");
+            r.GroupEnd = (decltype(r.GroupEnd))lib.symbol("librccl", "ncclGroupEnd");
+            r.Gather = (decltype(r.Gather))lib.symbol("librccl", "ncclGather");
+            r.GetErrorString = (decltype(r.GetErrorString))lib.symbol("librccl", "ncclGetErrorString");
         }
-        if (!r.handle) { r.error = std::string("librccl not found (") + (dlerror() ? dlerror() : "dlopen failed") + ")"; return; }
-        auto sym = [&](const char *n) { void *p = dlsym(r.handle, n); if (!p && r.error.empty()) r.error = std::string("librccl lacks ") + n; return p; };
-        r.CommInitAll = (decltype(r.CommInitAll))sym("ncclCommInitAll");
-        r.CommDestroy = (decltype(r.CommDestroy))sym("ncclCommDestroy");
-        r.GroupStart = (decltype(r.GroupStart))sym("ncclGroupStart");
-        r.GroupEnd = (decltype(r.GroupEnd))sym("ncclGroupEnd");
-        r.Gather = (decltype(r.Gather))sym("ncclGather");
-        r.GetErrorString = (decltype(r.GetErrorString))sym("ncclGetErrorString");
+        r.handle = lib.handle;
+        r.error = lib.error;
     });
     return r;
 }
-#define G_NCCL(expr)                                                                                  \
-    do {                                                                                              \
-        ncclResult_t r__ = (expr);                                                                    \
-        if (r__ != ncclSuccess) return fail(PDOG_E_HIP, std::string(#expr) + ": " + rccl().GetErrorString(r__)); \
+// a collective call through the group's table `net`: G_NCCL(net, GroupStart())
+#define G_NCCL(net, call)                                                                                       \
+    do {                                                                                                        \
+        ncclResult_t r__ = (net)->call;                                                                         \
+        if (r__ != ncclSuccess) return fail(PDOG_E_HIP, std::string("nccl" #call ": ") + (net)->GetErrorString(r__)); \
     } while (0)
+
+// ---- the local transport: every rank on one device (pdog_group_test_create_local, tests only) ----
+// What NCCL documents for a grouped gather on streams, and no more.  A communicator is a rank, the group's size and the state
+// the group shares.  Gather is legal between GroupStart and GroupEnd, once per rank; every Gather of one group call carries
+// the same count, root 0 and ncclInt32, and the root's recv is non-null — anything else is ncclInvalidUsage, from Gather or
+// from GroupEnd.  At the outermost GroupEnd, for every rank r: an event is recorded on r's stream, the root's stream waits for
+// it and copies r's block device-to-device into recv + r * count; then an event is recorded on the root's stream and every
+// other rank's stream waits for it.  So the data is read after the sender's kernels, the root's later work (the compaction
+// kernel, the next call) comes after all arrivals, and a sender's buffer is not overwritten by its next batch before it was
+// read.  No host synchronisation anywhere; the events are created once per group and destroyed with its last communicator.
+struct LocalShared {
+    int size = 0, device = 0, alive = 0;
+    std::vector<hipEvent_t> ev; // [r] rank r's work is queued, [size] the root has queued every copy
+    struct Pending { bool have = false; const void *send = nullptr; void *recv = nullptr; size_t count = 0; hipStream_t stream = nullptr; };
+    std::vector<Pending> pending;
+    bool listed = false; // in local_open (below)
+};
+struct LocalComm { int rank, size; LocalShared *shared; };
+// ncclGroupStart / ncclGroupEnd take no communicator: the open group is the calling thread's
+thread_local int local_depth = 0;
+thread_local std::vector<LocalShared *> local_open;
+
+ncclResult_t local_comm_init_all(ncclComm_t *comm, int ndev, const int *devlist)
+{
+    if (!comm || ndev <= 0 || !devlist) return ncclInvalidArgument;
+    for (int r = 1; r < ndev; ++r)
+        if (devlist[r] != devlist[0]) return ncclInvalidArgument; // one device: that is what this transport is
+    if (hipSetDevice(devlist[0]) != hipSuccess) return ncclUnhandledCudaError;
+    LocalShared *s = new LocalShared();
+    s->size = s->alive = ndev;
+    s->device = devlist[0];
+    s->pending.resize(ndev);
+    for (int k = 0; k <= ndev; ++k) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+            for (hipEvent_t q : s->ev) (void)hipEventDestroy(q);
+            delete s;
+            return ncclUnhandledCudaError;
+        }
+        s->ev.push_back(e);
+    }
+    for (int r = 0; r < ndev; ++r) comm[r] = (ncclComm_t) new LocalComm{r, ndev, s};
+    return ncclSuccess;
+}
+
+ncclResult_t local_comm_destroy(ncclComm_t comm)
+{
+    LocalComm *c = (LocalComm *)comm;
+    if (!c) return ncclInvalidArgument;
+    LocalShared *s = c->shared;
+    delete c;
+    if (--s->alive == 0) { // (the owner has drained every stream)
+        for (auto it = local_open.begin(); it != local_open.end(); ++it)
+            if (*it == s) { local_open.erase(it); break; }
+        (void)hipSetDevice(s->device);
+        for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
+        delete s;
+    }
+    return ncclSuccess;
+}
+
+ncclResult_t local_group_start()
+{
+    ++local_depth;
+    return ncclSuccess;
+}
+
+ncclResult_t local_gather(const void *sendbuff, void *recvbuff, size_t sendcount, ncclDataType_t datatype, int root, ncclComm_t comm, hipStream_t stream)
+{
+    LocalComm *c = (LocalComm *)comm;
+    if (!c || !sendbuff) return ncclInvalidArgument;
+    if (local_depth <= 0) return ncclInvalidUsage;                         // outside GroupStart … GroupEnd
+    LocalShared *s = c->shared;
+    LocalShared::Pending &p = s->pending[c->rank];
+    if (p.have) return ncclInvalidUsage;                                   // twice for one rank
+    if (datatype != ncclInt32 || root != 0) return ncclInvalidUsage;
+    if (c->rank == 0 && !recvbuff) return ncclInvalidUsage;
+    p.have = true; p.send = sendbuff; p.recv = recvbuff; p.count = sendcount; p.stream = stream;
+    if (!s->listed) { s->listed = true; local_open.push_back(s); }
+    return ncclSuccess;
+}
+
+// one group's gathers, checked and queued; its pending calls are forgotten either way
+ncclResult_t local_flush(LocalShared *s)
+{
+    std::vector<LocalShared::Pending> p(s->size);
+    p.swap(s->pending);
+    s->listed = false;
+    for (int r = 0; r < s->size; ++r)
+        if (!p[r].have || p[r].count != p[0].count) return ncclInvalidUsage; // a rank is missing, or the ranks disagree
+    const size_t bytes = p[0].count * sizeof(int32_t);
+    hipStream_t root = p[0].stream;
+    if (hipSetDevice(s->device) != hipSuccess) return ncclUnhandledCudaError;
+    for (int r = 0; r < s->size; ++r) {
+        if (r > 0) {
+            if (hipEventRecord(s->ev[r], p[r].stream) != hipSuccess) return ncclUnhandledCudaError;
+            if (hipStreamWaitEvent(root, s->ev[r], 0) != hipSuccess) return ncclUnhandledCudaError;
+        }
+        if (bytes && hipMemcpyAsync((char *)p[0].recv + r * bytes, p[r].send, bytes, hipMemcpyDeviceToDevice, root) != hipSuccess) return ncclUnhandledCudaError;
+    }
+    if (hipEventRecord(s->ev[s->size], root) != hipSuccess) return ncclUnhandledCudaError;
+    for (int r = 1; r < s->size; ++r)
+        if (hipStreamWaitEvent(p[r].stream, s->ev[s->size], 0) != hipSuccess) return ncclUnhandledCudaError;
+    return ncclSuccess;
+}
+
+ncclResult_t local_group_end()
+{
+    if (local_depth <= 0) return ncclInvalidUsage;
+    if (--local_depth > 0) return ncclSuccess; // a nested group: the outermost GroupEnd issues the calls
+    std::vector<LocalShared *> open;
+    open.swap(local_open);
+    ncclResult_t first = ncclSuccess;
+    for (LocalShared *s : open) {
+        const ncclResult_t nr = local_flush(s);
+        if (first == ncclSuccess) first = nr;
+    }
+    return first;
+}
+
+const char *local_error_string(ncclResult_t r)
+{
+    switch (r) {
+    case ncclSuccess: return "no error (local transport)";
+    case ncclUnhandledCudaError: return "unhandled HIP error (local transport)";
+    case ncclInvalidArgument: return "invalid argument (local transport)";
+    case ncclInvalidUsage: return "invalid usage (local transport)";
+    default: return "error (local transport)";
+    }
+}
+
+const Rccl &local_transport()
+{
+    static const Rccl t = [] {
+        Rccl l;
+        l.CommInitAll = local_comm_init_all;
+        l.CommDestroy = local_comm_destroy;
+        l.GroupStart = local_group_start;
+        l.GroupEnd = local_group_end;
+        l.Gather = local_gather;
+        l.GetErrorString = local_error_string;
+        return l;
+    }();
+    return t;
+}
 
 // Contiguous shards whose sizes differ by at most one: the first n_total % ndev ranks own one window more.
 __host__ __device__ inline void shard_bounds(int n_total, int ndev, int rank, int &lo, int &hi)
@@ -91,12 +242,36 @@ __global__ void group_compact_kernel(const int32_t *__restrict__ gathered, int32
 
 struct pdog_group {
     int ndev = 0;
+    const Rccl *net = nullptr; // the collective calls of this group: librccl's, or the local transport's
     std::vector<int> dev;
     std::vector<pdog_tracker *> tr;
     std::vector<ncclComm_t> comm;
     std::vector<pdog::DeviceBuffer<int32_t>> d_local; // per rank: max_n x 2 results of its shard
     pdog::DeviceBuffer<int32_t> d_gathered;           // root: ndev x max_n x 2 (unequal shards only)
 };
+
+// g->dev and g->net are set: a tracker per rank, then the communicators.  On failure g is destroyed.
+static int group_finish_create(pdog_group *g, const char *who, int frame_h, int frame_w, double target_width, int win_h, int win_w,
+                               int darker_target, int fill, pdog_group **out)
+{
+    const int ndev = g->ndev;
+    g->tr.assign(ndev, nullptr);
+    g->d_local.resize(ndev);
+    for (int r = 0; r < ndev; ++r) {
+        int rc = pdog_create(g->dev[r], frame_h, frame_w, target_width, win_h, win_w, darker_target, fill, &g->tr[r]);
+        if (rc) { pdog_group_destroy(g); return rc; } // pdog_last_error() already holds pdog_create's text
+    }
+    g->comm.assign(ndev, nullptr);
+    ncclResult_t nr = g->net->CommInitAll(g->comm.data(), ndev, g->dev.data());
+    if (nr != ncclSuccess) {
+        g->comm.clear();
+        const std::string text = std::string(who) + ": ncclCommInitAll: " + g->net->GetErrorString(nr);
+        pdog_group_destroy(g);
+        return fail(PDOG_E_HIP, text);
+    }
+    *out = g;
+    return PDOG_OK;
+}
 
 extern "C" {
 
@@ -126,7 +301,7 @@ int pdog_group_destroy(pdog_group *g)
     for (int r = 0; r < (int)g->tr.size(); ++r)
         if (g->tr[r]) (void)pdog_sync(g->tr[r]);
     for (int r = 0; r < (int)g->comm.size(); ++r)
-        if (g->comm[r]) (void)rccl().CommDestroy(g->comm[r]);
+        if (g->comm[r]) (void)g->net->CommDestroy(g->comm[r]);
     for (int r = 0; r < (int)g->dev.size(); ++r) {
         (void)hipSetDevice(g->dev[r]);
         if (r < (int)g->d_local.size()) g->d_local[r].release();
@@ -151,6 +326,7 @@ int pdog_group_create(int ndev, const int *devices, int frame_h, int frame_w, do
         return fail(PDOG_E_NODEV, "pdog_group_create: RCCL is not available: " + rccl().error + " — the single-device entry points do not need it");
     pdog_group *g = new pdog_group();
     g->ndev = ndev;
+    g->net = &rccl();
     for (int r = 0; r < ndev; ++r) {
         const int d = devices ? devices[r] : r;
         if (d < 0 || d >= have) {
@@ -161,21 +337,7 @@ int pdog_group_create(int ndev, const int *devices, int frame_h, int frame_w, do
             if (g->dev[q] == d) { delete g; return fail(PDOG_E_ARG, "pdog_group_create: a device appears twice (RCCL needs distinct devices)"); }
         g->dev.push_back(d);
     }
-    g->tr.assign(ndev, nullptr);
-    g->d_local.resize(ndev);
-    for (int r = 0; r < ndev; ++r) {
-        int rc = pdog_create(g->dev[r], frame_h, frame_w, target_width, win_h, win_w, darker_target, fill, &g->tr[r]);
-        if (rc) { pdog_group_destroy(g); return rc; } // pdog_last_error() already holds pdog_create's text
-    }
-    g->comm.assign(ndev, nullptr);
-    ncclResult_t nr = rccl().CommInitAll(g->comm.data(), ndev, g->dev.data());
-    if (nr != ncclSuccess) {
-        g->comm.clear();
-        pdog_group_destroy(g);
-        return fail(PDOG_E_HIP, std::string("pdog_group_create: ncclCommInitAll: ") + rccl().GetErrorString(nr));
-    }
-    *out = g;
-    return PDOG_OK;
+    return group_finish_create(g, "pdog_group_create", frame_h, frame_w, target_width, win_h, win_w, darker_target, fill, out);
 }
 
 int pdog_group_size(const pdog_group *g) { return g ? g->ndev : 0; }
@@ -194,6 +356,7 @@ int pdog_group_detect_batch(pdog_group *g, const uint8_t *const *d_frames, int64
     if (!g) return fail(PDOG_E_ARG, "pdog_group_detect_batch: null group");
     if (n_total == 0) return PDOG_OK;
     if (!d_frames || !n_frames || !d_guesses || !d_out_ij || n_total < 0) return fail(PDOG_E_ARG, "pdog_group_detect_batch: bad argument");
+    const Rccl *net = g->net;
     const int ndev = g->ndev;
     const int max_n = (n_total + ndev - 1) / ndev;
     const bool equal = n_total % ndev == 0;
@@ -233,15 +396,15 @@ int pdog_group_detect_batch(pdog_group *g, const uint8_t *const *d_frames, int64
     }
     // one gather of the (row, col) pairs to the root, each rank's part enqueued behind its own kernels
     int32_t *recv = equal ? d_out_ij : g->d_gathered.get();
-    G_NCCL(rccl().GroupStart());
+    G_NCCL(net, GroupStart());
     for (int r = 0; r < ndev; ++r) {
-        ncclResult_t nr = rccl().Gather(g->d_local[r].get(), recv, (size_t)2 * max_n, ncclInt32, 0, g->comm[r], st[r]);
+        ncclResult_t nr = net->Gather(g->d_local[r].get(), recv, (size_t)2 * max_n, ncclInt32, 0, g->comm[r], st[r]);
         if (nr != ncclSuccess) {
-            (void)rccl().GroupEnd();
-            return fail(PDOG_E_HIP, std::string("pdog_group_detect_batch: ncclGather: ") + rccl().GetErrorString(nr));
+            (void)net->GroupEnd();
+            return fail(PDOG_E_HIP, std::string("pdog_group_detect_batch: ncclGather: ") + net->GetErrorString(nr));
         }
     }
-    G_NCCL(rccl().GroupEnd());
+    G_NCCL(net, GroupEnd());
     if (!equal) {
         HIP_TRY(hipSetDevice(g->dev[0]));
         hipLaunchKernelGGL(group_compact_kernel, dim3((n_total + 255) / 256), dim3(256), 0, st[0], (const int32_t *)g->d_gathered.get(), d_out_ij,
@@ -265,7 +428,7 @@ int pdog_group_sync(pdog_group *g)
 }
 
 // Test hook (tests/test_gpu_group.py): the copy kernel that compacts the gathered max-shard-sized blocks when the shards are
-// unequal — a path no one-GPU box reaches through pdog_group_detect_batch (with one rank the shards are always equal).
+// unequal, on synthetic gathered buffers (with one rank the shards are always equal).
 // d_gathered: int32[ndev][max_n][2] with max_n = ⌈n_total / ndev⌉; d_out: int32[n_total][2]; both on the current device.
 int pdog_group_test_compact(const int32_t *d_gathered, int n_total, int ndev, int32_t *d_out)
 {
@@ -275,6 +438,27 @@ int pdog_group_test_compact(const int32_t *d_gathered, int n_total, int ndev, in
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(0));
     return PDOG_OK;
+}
+
+// Test hook (tests/test_gpu_group_ranks.py): a group of nranks trackers that all live on `device`, each with its own stream, over
+// the local transport above — librccl is not opened.  Every other pdog_group_* call takes the handle as it takes
+// pdog_group_create's.  Reachable through this entry alone: no environment variable and no tuning key selects the transport.
+int pdog_group_test_create_local(int nranks, int device, int frame_h, int frame_w, double target_width, int win_h, int win_w,
+                                 int darker_target, int fill, pdog_group **out)
+{
+    if (!out) return fail(PDOG_E_ARG, "pdog_group_test_create_local: out is null");
+    *out = nullptr;
+    if (nranks <= 0 || nranks > 64) return fail(PDOG_E_ARG, "pdog_group_test_create_local: nranks must be 1 … 64");
+    int have = 0;
+    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0)
+        return fail(PDOG_E_NODEV, "pdog_group_test_create_local: no HIP device (this library has no CPU path)");
+    if (device < 0 || device >= have)
+        return fail(PDOG_E_NODEV, "pdog_group_test_create_local: device ordinal " + std::to_string(device) + " requested, " + std::to_string(have) + " visible");
+    pdog_group *g = new pdog_group();
+    g->ndev = nranks;
+    g->net = &local_transport();
+    g->dev.assign(nranks, device);
+    return group_finish_create(g, "pdog_group_test_create_local", frame_h, frame_w, target_width, win_h, win_w, darker_target, fill, out);
 }
 
 } // extern "C"

@@ -221,7 +221,7 @@ def test_prototype_table_matches_the_header():
     """Every prototype of the header against _lib.PROTOTYPES, argument by argument: a stride bound as c_int where the header
     says int64_t would be truncated without a word and hand the kernels a wrong address."""
     protos = _header_prototypes()
-    assert [name for name, _, _ in protos] == list(_lib.PROTOTYPES) and len(protos) == 55
+    assert [name for name, _, _ in protos] == list(_lib.PROTOTYPES) and len(protos) == 56
     for name, ret, args in protos:
         restype, argtypes = _lib.PROTOTYPES[name]
         assert _same_kind(restype, ret), (name, restype, ret)

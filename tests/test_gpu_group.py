@@ -1,8 +1,11 @@
 """Multi-GPU leg on the one-GPU box: the C ABI's tracker group (pdog_group_*, in-process RCCL ncclGather) with a
 single rank — RCCL accepts a 1-rank communicator, so ncclCommInitAll, the grouped ncclGather on the tracker's stream
 and the result placement all run for real — plus torch.distributed's nccl (= RCCL) backend at world size 1 through
-gather_positions, the bench's --group line, and the stream hand-over of pdog_set_stream.  More ranks need more
-devices: the driver's 8-GPU run is the first time RCCL moves bytes between GPUs."""
+gather_positions, the bench's --group line, and the stream hand-over of pdog_set_stream.  pdog_group_detect_batch with
+2 … 8 ranks — the per-rank loop, unequal and empty shards, the gather into the staging buffer and the compaction behind it,
+per-rank errors — runs in tests/test_gpu_group_ranks.py, on one device over a stream-ordered stand-in for the gather.  RCCL
+itself with more ranks needs more devices: ncclCommInitAll over distinct devices and bench.py --group with N > 1 have not
+run, and the driver's 8-GPU run is the first time RCCL moves bytes between GPUs."""
 import json
 import os
 import subprocess
