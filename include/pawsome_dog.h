@@ -425,5 +425,7 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
 #include "pawsome_overlay.h"
 /* a static background model — the per-pixel median of some frames — and frames with it subtracted: pdog_bg_* */
 #include "pawsome_background.h"
+/* how a target lies at a tracked position — orientation, axes, width: pdog_shape, pdog_shape_derive, pdog_shape_headings */
+#include "pawsome_shape.h"
 
 #endif /* PAWSOME_DOG_H */

@@ -150,6 +150,24 @@ def background_k(k, name="k"):
     return int(k)
 
 
+def shape_args(radius, min_contrast, prefix=""):
+    """What pdog_shape takes beside its arrays: the radius — None: the library's default, ceil(target_width) capped at 127,
+    passed on as 0; otherwise an integer 2 ... 127 (PDOG_SHAPE_MAX_RADIUS) — and the least contrast of a target, an integer
+    1 ... 255.  Returns (radius, min_contrast) as the library takes them; `prefix` goes in front of the names in a message."""
+    rn, cn = prefix + "radius", prefix + "min_contrast"
+    if radius is None:
+        radius = 0
+    elif isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+        raise TypeError(f"{rn} must be None or an integer, not {type(radius).__name__}")
+    elif not 2 <= radius <= 127:
+        raise ValueError(f"{rn}: {radius} lies outside 2 ... 127")
+    if isinstance(min_contrast, bool) or not isinstance(min_contrast, (int, np.integer)):
+        raise TypeError(f"{cn} must be an integer, not {type(min_contrast).__name__}")
+    if not 1 <= min_contrast <= 255:
+        raise ValueError(f"{cn}: {min_contrast} lies outside 1 ... 255")
+    return int(radius), int(min_contrast)
+
+
 def host_samples(v, name):
     """The sample list of a background estimate: host_steps' row, of 1 ... 64 entries.  The entries are the library's to judge."""
     a = host_steps(v, name)

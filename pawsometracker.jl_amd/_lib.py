@@ -170,6 +170,16 @@ BACKGROUND_PROTOTYPES = {
 }
 BACKGROUND_SYMBOLS = tuple(BACKGROUND_PROTOTYPES)
 BG_MAX_SAMPLES = 64          # PDOG_BG_MAX_SAMPLES
+
+# the same for include/pawsome_shape.h, the fifth header pawsome_dog.h includes: how a target lies at a tracked position
+# (tests/test_shape_cpu.py holds this table against that header)
+SHAPE_PROTOTYPES = {
+    "pdog_shape": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _i, _i, _p, _p]),
+    "pdog_shape_derive": (_i, [_p, _p, _p]),
+    "pdog_shape_headings": (_i, [_p, _p, _i, _d, _p]),
+}
+SHAPE_SYMBOLS = tuple(SHAPE_PROTOTYPES)
+SHAPE_MAX_RADIUS = 127       # PDOG_SHAPE_MAX_RADIUS
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -215,7 +225,8 @@ def lib():
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
-                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES}.items():
+                                      **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES,
+                                      **SHAPE_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

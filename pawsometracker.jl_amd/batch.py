@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args, predict_args
+from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args, predict_args, shape_args
 
 
 def _targets_of(starts):
@@ -321,6 +321,32 @@ class BatchTracker(_lib.TrackerHandle):
             C.c_void_p(ij.data_ptr()), n, C.c_void_p(resp.data_ptr()) if want_resp else None,
             C.c_void_p(sub.data_ptr())))
         return (sub, resp) if want_resp else sub
+
+    def shapes(self, frames, ij, frame_index=None, radius=None, min_contrast=8, want_sums=False):
+        """How the target lies at tracked points (pdog_shape; this library's addition, the rule is stated in
+        include/pawsome_shape.h): frames, ij and frame_index as for measure.  Around every position the pixels within `radius`
+        (None: ceil(target_width), at most 127; otherwise 2 ... 127) that reach half the target's own contrast against the
+        patch's median form a mask — empty where that contrast stays below min_contrast (1 ... 255) — and the mask's moments
+        give the result, float64 cuda [n, 6]: (row, col) of its centroid, theta — the major axis, from +col towards +row, in
+        (-pi/2, pi/2] —, the full major and minor axes, and width, the equivalent diameter (the number to use as
+        target_width); all NaN for an empty mask.  With want_sums (shape, sums): sums int32 cuda [n, 8], the rule's integers
+        (n, Sy, Sx, Syy, Syx, Sxx, b, c).  Runs on torch's current stream like every detect*: behind a detect call it needs
+        no synchronisation in between."""
+        import torch
+        self.use_torch_stream()
+        radius, min_contrast = shape_args(radius, min_contrast)
+        device_frames(frames, "frames", 3, self._hw)
+        n = device_array(ij, "ij", torch.int32, (None, 2)).shape[0]
+        fi = frame_index_ptr(frame_index, n)
+        shape = torch.empty((n, 6), dtype=torch.float64, device=frames.device)
+        sums = torch.empty((n, 8), dtype=torch.int32, device=frames.device) if want_sums else None
+        if n == 0:              # (an empty tensor has no address to hand over)
+            return (shape, sums) if want_sums else shape
+        _lib.check(_lib.lib().pdog_shape(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
+            C.c_void_p(ij.data_ptr()), n, radius, min_contrast, C.c_void_p(sums.data_ptr()) if want_sums else None,
+            C.c_void_p(shape.data_ptr())))
+        return (shape, sums) if want_sums else shape
 
     def _clips_handle(self):
         """The pdog_clips handle behind clip_modes / track_clips: created on first use, closed with the tracker."""

@@ -4,8 +4,10 @@
 #include "pdog_host.hpp"
 #include "pdog_exclusive.hpp"
 #include "pdog_motion.hpp"
+#include "pdog_shape.hpp"
 #include "../../include/pawsome_exclusive.h"
 #include "../../include/pawsome_motion.h"
+#include "../../include/pawsome_shape.h"
 
 #include <algorithm>
 #include <cmath>
@@ -482,6 +484,23 @@ int pdog_assign_motion_host(int n_groups, int n_targets, int k, int min_distance
             mstate[4 * w] = c.vi; mstate[4 * w + 1] = c.vj; mstate[4 * w + 2] = c.n_held; mstate[4 * w + 3] = 0;
         }
     }
+    return PDOG_OK;
+}
+
+// ---- the shape rule's Float64 part on the host (include/pawsome_shape.h, steps 7 and 8; pdog_shape.hpp holds the arithmetic) ----
+int pdog_shape_derive(const int32_t sums[8], const int32_t ij[2], double out[6])
+{
+    if (!sums || !ij || !out) return fail(PDOG_E_ARG, "pdog_shape_derive: null pointer");
+    pdog::shape::derive(sums, ij[0], ij[1], out);
+    return PDOG_OK;
+}
+
+int pdog_shape_headings(const double *theta, const int32_t *ij, int n_steps, double min_step, double *out)
+{
+    if (n_steps < 0 || !(min_step >= 0)) return fail(PDOG_E_ARG, "pdog_shape_headings: n_steps < 0, or a min_step that is negative or NaN");
+    if (n_steps == 0) return PDOG_OK;
+    if (!theta || !ij || !out) return fail(PDOG_E_ARG, "pdog_shape_headings: null pointer");
+    pdog::shape::headings(theta, ij, n_steps, min_step, out);
     return PDOG_OK;
 }
 

@@ -90,6 +90,71 @@ def subpixel(resp5, ij):
     return float(out[0]), float(out[1])
 
 
+def _host(v, dtype):
+    """A tensor, array or sequence as a contiguous host array of `dtype`."""
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(v), dtype=dtype)
+
+
+def shape_derive(sums, ij):
+    """Step 7 of the shape rule on the host (pdog_shape_derive; include/pawsome_shape.h): sums — the eight integers
+    (n, Sy, Sx, Syy, Syx, Sxx, b, c) BatchTracker.shapes(want_sums=True) returns, [8] or [n, 8] — and ij, the 1-based
+    positions they were taken at (clamped into the frame), [2] or [n, 2] -> numpy float64 [6] or [n, 6]: row, col, theta,
+    major, minor, width; NaN where n is 0."""
+    s, p = _host(sums, np.int32), _host(ij, np.int32)
+    if s.shape[-1:] != (8,) or s.ndim not in (1, 2):
+        raise ValueError(f"sums: shape {s.shape}, expected (8,) or (n, 8)")
+    if p.shape != s.shape[:-1] + (2,):
+        raise ValueError(f"ij: shape {p.shape}, expected {s.shape[:-1] + (2,)}")
+    s2, p2 = s.reshape(-1, 8), p.reshape(-1, 2)
+    out = np.empty((len(s2), 6), np.float64)
+    fn = _lib.lib().pdog_shape_derive
+    for k in range(len(s2)):
+        _lib.check(fn(C.c_void_p(s2[k].ctypes.data), C.c_void_p(p2[k].ctypes.data), C.c_void_p(out[k].ctypes.data)))
+    return out.reshape(s.shape[:-1] + (6,))
+
+
+def headings(shape_or_theta, indices, min_step=1.0):
+    """Step 8 of the shape rule (pdog_shape_headings; include/pawsome_shape.h): theta's 180 degree ambiguity resolved with
+    the motion, per target over its steps.  shape_or_theta: the `shape` a track returned, [m, 6] or [n_targets, m, 6], or
+    its theta column alone, [m] or [n_targets, m]; indices: the positions, [m, 2] or [n_targets, m, 2].  A step of at least
+    min_step pixels points the heading along the motion, a shorter one keeps the side of the previous heading; NaN where
+    theta is.  Returns numpy float64 [m] or [n_targets, m], in (-pi, pi], from +col towards +row."""
+    if isinstance(min_step, bool) or not isinstance(min_step, (int, float, np.integer, np.floating)):
+        raise TypeError(f"min_step must be a real number, not {type(min_step).__name__}")
+    if not float(min_step) >= 0:
+        raise ValueError(f"min_step: {min_step} is not a distance >= 0")
+    ij = _host(indices, np.int32)
+    th = _host(shape_or_theta, np.float64)
+    if ij.ndim not in (2, 3) or ij.shape[-1] != 2:
+        raise ValueError(f"indices: shape {ij.shape}, expected (m, 2) or (n_targets, m, 2)")
+    if th.shape == ij.shape[:-1] + (6,):
+        th = np.ascontiguousarray(th[..., 2])
+    if th.shape != ij.shape[:-1]:
+        raise ValueError(f"shape_or_theta: shape {th.shape}, expected {ij.shape[:-1]} or {ij.shape[:-1] + (6,)}")
+    out = np.empty(th.shape, np.float64)
+    m = th.shape[-1]
+    th2, ij2, out2 = th.reshape(-1, m), ij.reshape(-1, m, 2), out.reshape(-1, m)
+    for t in range(len(th2)):
+        _lib.check(_lib.lib().pdog_shape_headings(C.c_void_p(th2[t].ctypes.data), C.c_void_p(ij2[t].ctypes.data), m, float(min_step),
+                                                  C.c_void_p(out2[t].ctypes.data)))
+    return out
+
+
+def _shape_keywords(shape, shape_radius, shape_min_contrast):
+    """The shape keywords of the track functions, judged before anything touches the device: (radius, min_contrast) as the
+    library takes them, or None without shape."""
+    from ._args import shape_args
+    if not isinstance(shape, bool):
+        raise TypeError("shape must be True or False")
+    if not shape:
+        if shape_radius is not None or shape_min_contrast is not None:
+            raise ValueError("shape_radius and shape_min_contrast belong to shape")
+        return None
+    return shape_args(shape_radius, 8 if shape_min_contrast is None else shape_min_contrast, "shape_")
+
+
 class _PaddedFrame:
     """Stands in for the PaddedView at :48: `.data` is the live frame buffer the
     caller overwrites in place each frame (:166); everything outside reads as `fillvalue`."""
@@ -154,6 +219,24 @@ class Tracker(_lib.TrackerHandle):
         v = [float(x) for x in out[0].cpu()]
         return ((v[5], v[6]), tuple(v[:5])) if want_resp else (v[5], v[6])
 
+    def shape(self, ij, radius=None, min_contrast=8, want_sums=False):
+        """How the target lies at the 1-based position ij on the current frame (`img.data`): (row, col, theta, major, minor,
+        width) as BatchTracker.shapes describes them (pdog_shape) — and, with want_sums, the rule's eight integers.  The
+        frame goes up through torch, the kernel runs on the tracker's own stream.  Synchronous, like the functor."""
+        import torch
+        from ._args import shape_args
+        radius, min_contrast = shape_args(radius, min_contrast)
+        f, p = _to_device(self.img.data, ij, self.device)
+        out = torch.empty((1, 6), dtype=torch.float64, device=f.device)
+        sums = torch.empty((1, 8), dtype=torch.int32, device=f.device)
+        torch.cuda.current_stream(f.device).synchronize()     # the upload is on torch's stream
+        _lib.check(_lib.lib().pdog_shape(self._h, C.c_void_p(f.data_ptr()), f.stride(0), f.stride(1), 1, None,
+                                         C.c_void_p(p.data_ptr()), 1, radius, min_contrast, C.c_void_p(sums.data_ptr()),
+                                         C.c_void_p(out.data_ptr())))
+        self.sync()
+        v = tuple(float(x) for x in out[0].cpu())
+        return (v, tuple(int(x) for x in sums[0].cpu())) if want_sums else v
+
 
 def get_guess(start_location, img, sar=1.0):
     """src/PawsomeTracker.jl:74-90: CartesianIndex -> Tuple; (x, y) -> round.((y, x/sar));
@@ -187,7 +270,7 @@ def get_start_ij_and_tracker(start_location, img, target_width, window_size, dar
 
 
 def track_frames(frames, target_width=25, start_location=None, window_size=None, darker_target=True,
-                 sar=1.0, device=0, diagnostic=None, subpixel=False):
+                 sar=1.0, device=0, diagnostic=None, subpixel=False, shape=False, shape_radius=None, shape_min_contrast=None):
     """The frame loop of track_one (src/PawsomeTracker.jl:159-169) on already-decoded GRAY8
     frames (decode stays with the host application): indices[1] from the bootstrap (:161),
     then indices[k] = trckr(indices[k-1]) per frame (:166-167, the intended loop).
@@ -196,24 +279,30 @@ def track_frames(frames, target_width=25, start_location=None, window_size=None,
     frames 2 ... n in order, the 360 x 640 uint8 numpy buffer dia(img, point) draws (src/diagnose.jl:30-38,
     rendered on the GPU by Diagnose); encoding it is the caller's business.
     With subpixel=True the return value is (indices, sub): sub holds one (row, col) float pair per frame, the first
-    frame included — Tracker.measure at each returned position (this library's addition; the indices are unchanged)."""
+    frame included — Tracker.measure at each returned position (this library's addition; the indices are unchanged).
+    With shape=True the result gains a trailing `shape`, behind sub where that is present: one (row, col, theta, major,
+    minor, width) per frame — Tracker.shape at each returned position with shape_radius (None: ceil(target_width)) and
+    shape_min_contrast (None: 8); ValueError for either without shape.  Everything else is what it is without the keyword."""
+    shp = _ShapeSink(shape, shape_radius, shape_min_contrast)
     sub = [] if subpixel else None
     if diagnostic is None:
-        ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, None, None, sub)
+        ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, None, None, sub, shp)
     else:
         from .diagnose import Diagnose
         with Diagnose(darker_target, device) as dia:
-            ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub)
-    return (ijs, sub) if subpixel else ijs
+            ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub, shp)
+    res = (ijs, sub) if subpixel else ijs
+    return shp.behind(res)
 
 
 def track_segments(segments, start_locations=None, target_width=25, window_size=None, darker_target=True,
-                   sar=1.0, device=0, diagnostic=None, subpixel=False):
+                   sar=1.0, device=0, diagnostic=None, subpixel=False, shape=False, shape_radius=None, shape_min_contrast=None):
     """track(files::AbstractVector; ...) (src/PawsomeTracker.jl:181-214) on already-decoded segments: `segments` is a
     list of frame iterables, `start_locations` one start location per segment (default all None).  A None after the
     first segment takes the previous segment's last position (coalesce(loc, end_location), :204-206).  One overlay
     trace spans every segment (one `Diagnose`, :201), across frame sizes.  Returns the concatenated positions — and,
-    with subpixel=True, (positions, sub) as track_frames does."""
+    with subpixel=True, (positions, sub) as track_frames does; with shape=True the trailing `shape` as track_frames does."""
+    shp = _ShapeSink(shape, shape_radius, shape_min_contrast)
     segments = list(segments)
     locs = [None] * len(segments) if start_locations is None else list(start_locations)
     if len(locs) != len(segments):
@@ -228,13 +317,13 @@ def track_segments(segments, start_locations=None, target_width=25, window_size=
         for seg, loc in zip(segments, locs):
             if loc is None and end is not None:
                 loc = ("ij", end)                                 # a CartesianIndex, :205
-            ijs = _track_one(seg, target_width, loc, window_size, darker_target, sar, device, dia, diagnostic, sub)
+            ijs = _track_one(seg, target_width, loc, window_size, darker_target, sar, device, dia, diagnostic, sub, shp)
             end = ijs[-1]                                         # :206
             out.extend(ijs)
     finally:
         if dia is not None:
             dia.close()
-    return (out, sub) if subpixel else out
+    return shp.behind((out, sub) if subpixel else out)
 
 
 def _overlay(dia, frame, ij, device):
@@ -242,7 +331,25 @@ def _overlay(dia, frame, ij, device):
     return dia(*_to_device(frame, ij, device))[0].cpu().numpy()
 
 
-def _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub=None):
+class _ShapeSink:
+    """The shape keywords of track_frames and track_segments: judged at once, then one Tracker.shape per returned position."""
+
+    def __init__(self, shape, shape_radius, shape_min_contrast):
+        self.args = _shape_keywords(shape, shape_radius, shape_min_contrast)
+        self.rows = []
+
+    def measure(self, trckr, ij):
+        if self.args is not None:
+            self.rows.append(trckr.shape(ij, self.args[0] or None, self.args[1]))
+
+    def behind(self, res):
+        """res with the shapes as its last element, if they were asked for."""
+        if self.args is None:
+            return res
+        return (res if isinstance(res, tuple) else (res,)) + (self.rows,)
+
+
+def _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, dia, diagnostic, sub=None, shp=None):
     if window_size is None:
         window_size = guess_window_size(target_width)            # :136
     window_size = fix_window_size(window_size)                   # :142
@@ -253,11 +360,15 @@ def _track_one(frames, target_width, start_location, window_size, darker_target,
     try:
         if sub is not None:
             sub.append(trckr.measure(ij))                        # (sub: one float pair per frame, appended in place)
+        if shp is not None:
+            shp.measure(trckr, ij)
         for frame in it:
             trckr.img.data[...] = frame                          # :166
             indices.append(trckr(indices[-1]))                   # :167
             if sub is not None:
                 sub.append(trckr.measure(indices[-1]))
+            if shp is not None:
+                shp.measure(trckr, indices[-1])
             if dia is not None:
                 diagnostic(_overlay(dia, trckr.img.data, indices[-1], device))   # :168
     finally:
@@ -378,8 +489,8 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, background=None, background_chunk=256, predict=False, motion=False, coast=None, min_response=None,
-                exclusive=False, min_ratio=None):
+                min_distance=None, shape=False, shape_radius=None, shape_min_contrast=None, background=None, background_chunk=256,
+                predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -432,11 +543,20 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     most `background_chunk` steps at a time in one reused buffer: chunk 0 starts from the bootstrap, every later chunk from the
     chunk before it (its last positions and, for motion and predict, its mstate), so the result does not depend on
     background_chunk.  subpixel measures on the subtracted frames; diagnostic draws on the original ones.  ValueError for
-    background_chunk without background and for K outside 1 ... 64."""
+    background_chunk without background and for K outside 1 ... 64.
+    `shape` = True measures HOW every target lies (this library's addition; include/pawsome_shape.h states the rule): the
+    result gains `shape`, float64 cuda [n_targets, m, 6], as its LAST element, behind sub and state where those are present —
+    BatchTracker.shapes at every returned position, held ones included, with `shape_radius` (None: ceil(target_width)) and
+    `shape_min_contrast` (None: 8): (row, col) of the blob's centroid, theta, the major and minor axes and the equivalent
+    width; NaN where no blob reaches the contrast.  It is measured on the frames the tracker saw: the subtracted ones under
+    background, chunk by chunk as subpixel is, and independent of background_chunk.  headings(shape, indices) turns theta into a
+    heading along the motion.  ValueError for shape_radius or shape_min_contrast without shape; every result without the
+    keyword is what it is today."""
     import torch
     from ._args import background_k, device_frames, exclusive_args, motion_args, peaks_args, predict_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
+    shape_kw = _shape_keywords(shape, shape_radius, shape_min_contrast)
     if isinstance(background_chunk, bool) or not isinstance(background_chunk, (int, np.integer)):
         raise TypeError("background_chunk must be an integer")
     if background_chunk < 1:
@@ -551,16 +671,20 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 finally:
                     bt4.close()
             # the loop from the second selected frame on, :161-167: every target over the same table
-            sub = None
+            sub = shp = None
             if bg is None:
                 out, state, _ = walk(bt, frames, table, starts, 1, None)
-                if subpixel:
+                if subpixel or shape_kw:
                     fi = torch.from_numpy(np.tile(table, nt)).to(dev)
+                if subpixel:
                     sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
+                if shape_kw:
+                    shp = bt.shapes(frames, out.view(-1, 2), fi, shape_kw[0] or None, shape_kw[1]).view(nt, m, 6)
             else:                        # the same over the subtracted frames, a buffer of them at a time
                 out = torch.zeros((nt, m, 2), dtype=torch.int32, device=dev)
                 state = torch.zeros((nt, m), dtype=torch.int32, device=dev) if exclusive or motion or predict else None
                 sub = torch.empty((nt, m, 2), dtype=torch.float64, device=dev) if subpixel else None
+                shp = torch.empty((nt, m, 6), dtype=torch.float64, device=dev) if shape_kw else None
                 mstate = None
                 for k0 in range(0, m, bstep):
                     nk = min(bstep, m - k0)
@@ -571,9 +695,13 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     out[:, k0:k0 + nk] = o
                     if state is not None:
                         state[:, k0:k0 + nk] = st
-                    if subpixel:
+                    if subpixel or shape_kw:
                         fi = torch.from_numpy(np.tile(np.arange(nk, dtype=np.int32), nt)).to(dev)
+                    if subpixel:
                         sub[:, k0:k0 + nk] = bt.measure(buf[:nk], o.reshape(-1, 2).contiguous(), fi).view(nt, nk, 2)
+                    if shape_kw:
+                        shp[:, k0:k0 + nk] = bt.shapes(buf[:nk], o.reshape(-1, 2).contiguous(), fi, shape_kw[0] or None,
+                                                       shape_kw[1]).view(nt, nk, 6)
             bt.sync()                    # what the kernels raised (PdogError) surfaces before the positions are handed out
             if diagnostic is not None:
                 from .diagnose import Diagnose
@@ -581,7 +709,9 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     dia.set_targets(nt)
                     _render_steps(dia, frames, table, out, chunk, diagnostic)
             res = (ts, out, sub) if subpixel else (ts, out)
-            return res + (state,) if exclusive or motion or predict else res
+            if exclusive or motion or predict:
+                res += (state,)
+            return res + (shp,) if shape_kw else res
         finally:
             if bt is not None:
                 bt.close()
