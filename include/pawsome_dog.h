@@ -166,6 +166,8 @@ int pdog_set_exact(pdog_tracker *t, int on);
  *   "no_fold" / "fold_always"  a single remainder column always / never goes to the remainder-column kernel
  *   "no_pad_skip"  the roll kernels run their full path also on sub-chunks (8 tile rows of a strip) that hold padding only
  *   "no_prune"     roll batches stay dense: no pre-pass, every strip computes every sub-chunk (pdog_get_prune_counts)
+ *   "no_range_end" pruned roll batches run full-length column-pass bodies to the end of every kept range (default: entered
+ *                  at the first tap block that still feeds an emitted output)
  *   "measure_global" pdog_measure reads the frame itself instead of staging each position's pixels in LDS (its path for l > 93)
  * Unknown key: PDOG_E_ARG.  Drains the tracker's stream. */
 int pdog_set_tuning(pdog_tracker *t, const char *key, int value);

@@ -200,9 +200,12 @@ struct LaunchGeo {
     // roll and thin kernels (dog_prune.hpp): on entry part_mask[b][slot] holds the slot's kept range of 8-row output blocks,
     // (first | one past the last << 32; a remainder column's word also carries the window's DC level, bits 24 … 31), and only
     // that range is computed (the struct's size does not change: this word was padding).  Non-zero: a pruned launch; the value
-    // is the number of consecutive jobs that go to one XCD (a power of two, prune_job_index).
+    // is the number of consecutive jobs that go to one XCD (a power of two, prune_job_index) in the bits of PRUNE_GROUP_MASK,
+    // and PRUNE_NO_RANGE_END beside it: the strips run full-length column-pass bodies to the end of a kept range
+    // (pdog_set_tuning "no_range_end"; dog_roll.hpp, roll_strip).
     int prune;
 };
+constexpr int PRUNE_GROUP_MASK = 0xffff, PRUNE_NO_RANGE_END = 1 << 30;
 
 constexpr int FOLD_GO = 5; // output rows per lane and pass of a folded remainder column (257 rows = 64 lanes × 5 + 1 …)
 // Column pass + peak of ONE window column whose row-pass outputs Rc[0 … n1 + L − 2] (+ FOLD_GO readable entries of padding) sit

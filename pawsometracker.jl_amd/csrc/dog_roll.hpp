@@ -55,6 +55,7 @@
 #include "dog_kernels.hpp"
 #include "dog_exact.hpp"
 #include "pdog_predict.hpp"
+#include "dog_roll_range.hpp" // ROLL_CH, ROLL_QB, the tap-block counts, prune_sc_hi and the range-end rule: host-testable
 #include <type_traits>
 
 namespace pdog {
@@ -62,7 +63,6 @@ namespace pdog {
 #ifndef PDOG_ROLL_LMAX
 #define PDOG_ROLL_LMAX 149
 #endif
-constexpr int ROLL_CH = 8;   // rows per sub-chunk (16 measured equal on cfg3: the kernel is VALU-bound, not latency-bound)
 constexpr int ROLL_P = 8;    // row-pass outputs per lane
 constexpr int ROLL_TW = 64;  // strip width = lanes
 constexpr int ROLL_PR = 65;  // R pitch (f2)
@@ -88,12 +88,7 @@ __host__ __device__ constexpr int roll_rs(int L) { return (8 * roll_sb(L) + 40 +
 __host__ __device__ constexpr int roll_row_base(int r, int L) { return r * roll_rs(L) + 4 * (((r & 1) ? 1 : 0) + ((r & 2) ? 8 : 0)); }
 __host__ __device__ constexpr size_t roll_lds_bytes(int L) { return (size_t)ROLL_CH * roll_rs(L) * 4 + (size_t)ROLL_CH * ROLL_PR * 8; }
 
-// KEPT RANGES (dog_prune.hpp; LaunchGeo::prune): a slot's pre-pass leaves the range [ba, bb) of 8-row output blocks that can
-// hold the window's peak or a near-tie.  Block j reads the input rows of sub-chunks j … j + prune_span(l) − 1; the range
-// needs sub-chunks ba … prune_sc_hi − 1.
-__host__ __device__ constexpr int prune_span(int L) { return (ROLL_CH + L - 1 + ROLL_CH - 1) / ROLL_CH; }
-__host__ __device__ constexpr int prune_tail(int L) { return (L - 1 + ROLL_CH - 1) / ROLL_CH; }
-__host__ __device__ constexpr int prune_sc_hi(int ba, int bb, int L, int nsub) { return bb > ba ? (bb + prune_tail(L) < nsub ? bb + prune_tail(L) : nsub) : ba; }
+// (KEPT RANGES: prune_span, prune_tail and prune_sc_hi are dog_roll_range.hpp's.)
 
 // Which entry of the job list workgroup `blk` of a PRUNE launch takes.  Consecutive workgroups go to consecutive XCDs, so
 // blk & 7 is the XCD and blk >> 3 the workgroup's turn on it: the list is dealt out in groups of G = 2^k consecutive entries
@@ -229,8 +224,7 @@ __device__ __forceinline__ void roll_row_pass(f2 (&acc)[NOUT == 9 ? ROLL_P + 2 :
 // its parity p = a & 1 (t ≡ p mod 2), so there are two pairings; T[-1] = T[l] = 0.
 //   table[((qb*2 + p)*2 + c)*ROLL_QB + m] = (Tc[t], Tc[t-1]),  t = p + 2*(ROLL_QB*qb + m),
 //   c = 0: s·g+, c = 1: −s·g−
-constexpr int ROLL_QB = 2; // tap pairs per block (2 parities x 2 channels x QB pairs = 16 SGPRs, double-buffered)
-__host__ __device__ constexpr int roll_col_blocks(int L) { return ((L + 1) / 2 + ROLL_QB - 1) / ROLL_QB; }
+// (ROLL_QB = 2 tap pairs per block and roll_col_blocks: dog_roll_range.hpp)
 __host__ __device__ constexpr int roll_col_table_len(int L) { return roll_col_blocks(L) * 4 * ROLL_QB; } // in f2
 
 // Column pass body for sub-chunk phase SC (rows a ≡ CH*SC + i mod S).  rv[i] = (R+, R−)[row i][x].
@@ -240,12 +234,11 @@ __host__ __device__ constexpr int roll_col_table_len(int L) { return roll_col_bl
 // a … a+7 of sub-chunk sc only need taps t ≤ a+7, i.e. tap blocks 0 … 2sc+1 — the rest of the scatter would land in
 // slots whose outputs do not exist (20 % of the column pass's FMAs over the first and last l−1 rows).  Up there the
 // phase equals the sub-chunk number, so the shortened bodies are static instances with no branch inside.
-__host__ __device__ constexpr int roll_prologue_blocks(int sc) { return 2 * sc + 2; }
+// (roll_prologue_blocks(sc) = 2 sc + 2, roll_prologue_len: dog_roll_range.hpp)
 // Bottom edge: rows a = 8 sc … need tap blocks qb ≥ qlo(sc) = 2 sc − c0, c0 = (n1 + 2) ÷ 4.  With the phase sc mod NBODY
 // the pair (phase, qlo) of every epilogue sub-chunk is fixed by c0 mod 2·NBODY: the window's height class.
 __host__ __device__ constexpr int roll_epi_c0(int n1) { return (n1 + 2) / 4; }
 __host__ __device__ constexpr int roll_epi_class(int n1, int L) { return roll_epi_c0(n1) % (2 * (roll_slots(L) / ROLL_CH)); }
-__host__ __device__ constexpr int roll_prologue_len(int L) { return (roll_col_blocks(L) - 2 + 1) / 2; } // sub-chunks with fewer blocks than the full body
 // The shortened bodies at the START of a run of sub-chunks (a window's top; a kept range's first sub-chunk, roll_strip):
 // sub-chunk j of the run, rows a = 8j … 8j + 7 counted from its first row, runs tap blocks 0 … roll_prologue_blocks(j) − 1
 // (all of them from j = roll_prologue_len on).  True iff those blocks hold every tap t of every output y = a − t ≥ 0 of the
@@ -268,21 +261,49 @@ __host__ __device__ constexpr bool roll_start_covers(int L)
 #define PDOG_ROLL_L(LT) static_assert(roll_start_covers(LT), "a shortened prologue body leaves out a tap of an output inside the range");
 #include "roll_lengths.def"
 #undef PDOG_ROLL_L
+// … and at the END of a kept range (dog_roll_range.hpp): entering a body at block roll_end_qlo leaves out no tap of an output
+// the loop still emits, and a prologue body that is entered late keeps at least one block.
+#define PDOG_ROLL_L(LT)                                                                                                     \
+    static_assert(roll_end_covers(LT), "the range-end entry leaves out a tap of an emitted output, or enters too early");   \
+    static_assert(roll_end_meets_prologue(LT), "a prologue body would be entered at or past its own last block");
+#include "roll_lengths.def"
+#undef PDOG_ROLL_L
 // QLO > 0: an EPILOGUE body, blocks QLO … only: the last input rows a > n1−1 have no output below row n1−1 to feed,
 // rows a … a+7 only need taps t ≥ a − (n1−1).  Down there sub-chunk and phase are tied through the window height, so
 // these bodies exist per HEIGHT CLASS (roll_epi_class) — instances for the common window sizes only.
-template <int L, int SC, int QHI = roll_col_blocks(L), int QLO = 0>
-__device__ __forceinline__ void roll_col_body(f2 (&acc2)[roll_slots(L) / 2], const f2 (&rv)[ROLL_CH], tap_ptr table)
+// ENTRY: the body of a PRUNE instance, entered at the wave-uniform RUN-TIME block qlo < QHI (the END of a kept range,
+// dog_roll_range.hpp: blocks below roll_end_qlo only feed outputs past the last one the loop emits; qlo is roll_end_entry's,
+// a multiple of roll_entry_step(L) — one entry point per 4 or 8 blocks, for the compile time's sake).  A switch jumps into the
+// unrolled block sequence and falls through: a skipped block has no FMAs, no tap loads, no pin_acc and no sched_barrier, and
+// every block from qlo on is the code it is without the entry — the entry block's taps are loaded by the run-time index
+// ahead of the switch into the registers the block before it would have filled.  Skipping block 0 skips the tt == 0
+// multiply that restarts slots: those slots belong to outputs past y_end, and nothing reads them again.
+template <int L, int SC, int QHI = roll_col_blocks(L), int QLO = 0, bool ENTRY = false>
+__device__ __forceinline__ void roll_col_body(f2 (&acc2)[roll_slots(L) / 2], const f2 (&rv)[ROLL_CH], tap_ptr table, int qlo = 0)
 {
     constexpr int S = roll_slots(L), CH = ROLL_CH, QB = ROLL_QB, NQB = QHI;
     static_assert(QHI >= 1 && QHI <= roll_col_blocks(L) && QLO >= 0 && QLO < QHI, "tap-block bounds out of range");
     static_assert(S % 2 == 0 && (CH * SC) % 2 == 0, "pairing needs even slot counts");
+    static_assert(!ENTRY || QLO == 0, "a run-time entry replaces the static first block");
     f2 tn[4 * QB];
     tap_ptr tb = pin_taps(table);
 #pragma unroll
-    for (int j = 0; j < 4 * QB; ++j) tn[j] = tb[QLO * 4 * QB + j];
+    for (int j = 0; j < 4 * QB; ++j) tn[j] = tb[(ENTRY ? qlo : QLO) * 4 * QB + j];
+    // ENTRY: the R values as a copy that every block re-derives through an empty asm.  fma_bcast's (r, r) operand is an op_sel
+    // broadcast only where the splat and the FMA share a basic block; with the entry a body is several blocks, the splats
+    // of the 16 R values were built once ahead of them — 32 v_mov_b32 per sub-chunk and 32 VGPRs held, 2.4 % of the headline
+    // step with qlo pinned to 0.  A value that is new in every block keeps its splat there.  (Every other instance reads rv
+    // itself: with the copy the response-writing instances of l = 17 … 29 took two VGPRs more.)
+    f2 rw[ENTRY ? CH : 1];
+    if constexpr (ENTRY) {
 #pragma unroll
-    for (int qb = QLO; qb < NQB; ++qb) {
+        for (int i = 0; i < CH; ++i) rw[i] = rv[i];
+    }
+    auto block = [&](const int qb) __attribute__((always_inline)) {
+        if constexpr (ENTRY) {
+#pragma unroll
+            for (int i = 0; i < CH; ++i) pin_acc(rw[i]);
+        }
         f2 t[4 * QB];
 #pragma unroll
         for (int j = 0; j < 4 * QB; ++j) t[j] = tn[j];
@@ -303,7 +324,9 @@ __device__ __forceinline__ void roll_col_body(f2 (&acc2)[roll_slots(L) / 2], con
                     const int tt = par + 2 * (QB * qb + m); // taps (tt, tt-1)
                     if (tt - 1 <= L - 1) {
                         const int slot = ((amod - tt) % S + S) % S; // even
-                        const float r = c ? rv[i].y : rv[i].x;
+                        float r;
+                        if constexpr (ENTRY) r = c ? rw[i].y : rw[i].x;
+                        else r = c ? rv[i].y : rv[i].x;
                         // An even row's pair (T[0], T[−1] = 0) is the FIRST term of outputs (a, a+1) — the slots the
                         // sub-chunk S rows earlier emitted: a multiply starts them from scratch (no reset instructions;
                         // output a+1 starts at ±0 and meets its own first term, row a+1's T[0], later in this block).
@@ -325,6 +348,44 @@ __device__ __forceinline__ void roll_col_body(f2 (&acc2)[roll_slots(L) / 2], con
             }
         }
         __builtin_amdgcn_sched_barrier(0);
+    };
+    if constexpr (ENTRY) {
+        static_assert(roll_col_blocks(ROLL_LMAX) <= 38, "extend the entry switch");
+#define PDOG_BLK(k)                                                                                                          \
+    if constexpr ((k) < NQB) block(k);
+#define PDOG_BLK4(k) PDOG_BLK(k) PDOG_BLK((k) + 1) PDOG_BLK((k) + 2) PDOG_BLK((k) + 3)
+#define PDOG_ENT4(k)                                                                                                         \
+    [[fallthrough]];                                                                                                          \
+    case k:                                                                                                                   \
+        PDOG_BLK4(k)
+#define PDOG_ENT8(k) PDOG_ENT4(k) PDOG_BLK4((k) + 4)
+        // one case per roll_entry_step(L) blocks; qlo is a multiple of it (roll_end_entry)
+        if constexpr (roll_entry_step(L) == 4) {
+            switch (qlo) {
+            case 0:
+                PDOG_BLK4(0)
+                PDOG_ENT4(4) PDOG_ENT4(8) PDOG_ENT4(12) PDOG_ENT4(16) PDOG_ENT4(20)
+                break;
+            default: break; // (never taken: qlo is a multiple of the step, roll_end_entry, and lies below QHI, roll_end_meets_prologue)
+            }
+            static_assert(roll_entry_step(L) != 4 || roll_col_blocks(L) <= 24, "extend the entry switch");
+        } else {
+            static_assert(roll_entry_step(L) == 4 || roll_entry_step(L) == 8, "one case per 4 or 8 blocks");
+            switch (qlo) {
+            case 0:
+                PDOG_BLK4(0) PDOG_BLK4(4)
+                PDOG_ENT8(8) PDOG_ENT8(16) PDOG_ENT8(24) PDOG_ENT8(32)
+                break;
+            default: break; // (never taken, as above)
+            }
+        }
+#undef PDOG_ENT8
+#undef PDOG_ENT4
+#undef PDOG_BLK4
+#undef PDOG_BLK
+    } else {
+#pragma unroll
+        for (int qb = QLO; qb < NQB; ++qb) block(qb);
     }
 }
 
@@ -478,13 +539,24 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
     // withheld from the peak anyway (the triangle the prologue bodies leave out at a window's top; roll_start_covers above
     // checks the blocks for every length).  The bits do not change: every output from y_lo on still receives its terms
     // t = 0, 1, … in order, in another register.  ybase, pad_sc, the staging rows and the counts keep the absolute number.
-    // (The END of a range still runs full-length bodies: the rows past 8·bb it feeds are emitted whole and harmless.) ----
+    // BODIES THAT MATCH THE RANGE'S END (dog_roll_range.hpp).  The last output the loop emits is y_end = min(8·sc_hi − l, n1 − 1)
+    // and no slot is read after it, so in sub-chunk sc only the taps t ≥ 8·sc − y_end + i of row i have an emitted output to
+    // feed: the column-pass bodies of a PRUNE instance — the NBODY full ones and the shortened prologue bodies, which a short
+    // range meets in the same sub-chunks — are entered at the wave-uniform run-time block roll_end_qlo(8·sc − y_end), rounded
+    // down to the entry step (roll_end_entry; roll_col_body, ENTRY): most of the triangle the height-class instances leave
+    // out statically at a window's bottom (at l = 17 and 21 the step leaves a range inside the window nothing to skip).  The dead blocks are those of the last
+    // ⌊(l − 3) / 8⌋ sub-chunks of every range, and more of one that the window's bottom cuts off.  The bits do not
+    // change: every emitted output still receives all its terms in order (roll_end_covers, asserted per length above;
+    // tests/range_end_main.cpp counts the pairs one by one), the rows past 8·bb the loop emits included; the slots that lose
+    // terms — or their restarting multiply, with block 0 — belong to outputs past y_end.  Padding-only sub-chunks
+    // (roll_col_zero) have nothing to skip.  pdog_set_tuning "no_range_end" pins qlo = 0 through y_end (LaunchGeo::prune). ----
     static_assert(!PRUNE || (!RESP && ABL == 0 && EPI < 0), "kept ranges: the plain instances only");
-    int sc_lo = 0, sc_hi = nsub, y_lo = 0;
+    int sc_lo = 0, sc_hi = nsub, y_lo = 0, y_end = 0;
     if constexpr (PRUNE) {
         sc_lo = prune_ba;
         sc_hi = prune_sc_hi(prune_ba, prune_bb, L, nsub);
         y_lo = prune_ba * CH;
+        y_end = (g.prune & PRUNE_NO_RANGE_END) ? CH * nsub : roll_end_y(sc_hi, L, g.n1); // (8·nsub: tm ≤ 0 for every sub-chunk)
     }
     uint32_t pre[SB / 4];
     load16(sc_lo * CH + srow, pre);
@@ -557,7 +629,7 @@ __device__ __forceinline__ void roll_strip(const LaunchGeo &g, const f2 *__restr
         auto emit = [&](auto SCc, auto QHIc, auto QLOc) {
             constexpr int SC = decltype(SCc)::value, QHI = decltype(QHIc)::value, QLO = decltype(QLOc)::value;
             if (pad_sc) roll_col_zero<L, SC>(acc2); // (harmless in a shortened body: the slots it resets there have no output)
-            else if (!(ABL & 1)) roll_col_body<L, SC, QHI, QLO>(acc2, rv, tcol);
+            else if (!(ABL & 1)) roll_col_body<L, SC, QHI, QLO, PRUNE>(acc2, rv, tcol, PRUNE ? roll_end_entry(roll_end_qlo(roll_end_tm(sc, y_end)), L) : 0);
             // outputs y = a − (l−1) for the 8 rows of this sub-chunk are complete.  A lane owns ONE
             // column and meets its rows in increasing y (= increasing column-major index), so a strict
             // '>' keeps the first maximum of the lane (findmax, :59); ties between lanes and strips
@@ -683,7 +755,7 @@ __global__ __launch_bounds__(64, roll_waves(LT)) void dog_roll_kernel(const Laun
         // upper bound; the workgroups past the list's end return, and they all sit at the END of the grid — the kept waves,
         // all of nearly one length, start back to back and fill the SIMDs, where one wave per (window, strip) in index
         // order interleaved them with as many waves that returned at once.  Results go to [b][s] whatever the list's order.
-        logical = prune_job_index((int)blockIdx.x, g.prune);
+        logical = prune_job_index((int)blockIdx.x, g.prune & PRUNE_GROUP_MASK);
         const int count = min(g.jobs[0].b, g.nblocks);
         if (logical >= count) return;
         const PruneJob job = g.jobs[1 + logical];

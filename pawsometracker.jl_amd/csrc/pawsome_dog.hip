@@ -89,6 +89,7 @@ struct Switches {
     bool fold_always = false;             // … always into the last strip, also below 8 strips per window
     bool no_pad_skip = false;             // roll kernels: sub-chunks that hold padding only run the full path (dog_roll.hpp, "padding rows")
     bool no_prune = false;                // roll batches stay dense: no pre-pass, no kept ranges (dog_prune.hpp)
+    bool no_range_end = false;            // pruned roll batches: full-length column-pass bodies to the end of a kept range (dog_roll_range.hpp)
     bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
     bool measure_global = false;          // pdog_measure reads the frame itself instead of staging each position's pixel tile in LDS
     bool fault_inject = false;            // tests: one sub-window of a tiled chain never delivers its second frame's partial (the device-side waits must give up)
@@ -127,6 +128,7 @@ Switches read_switches()
     w.fold_always = on("PDOG_FOLD_ALWAYS");
     w.no_pad_skip = on("PDOG_NO_PAD_SKIP");
     w.no_prune = on("PDOG_NO_PRUNE");
+    w.no_range_end = on("PDOG_NO_RANGE_END");
     w.no_roll_map = on("PDOG_NO_ROLL_MAP");
     w.no_host_dc = on("PDOG_NO_HOST_DC");
     w.tiled_force = on("PDOG_TILED_FORCE");
@@ -1248,7 +1250,8 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         pg.jobs = t->d_prune_jobs.get();
         hipLaunchKernelGGL(t->fw < 8 ? dog_prune_kernel<true> : dog_prune_kernel<false>, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
         HIP_TRY(hipGetLastError());
-        g.prune = kPruneXcdGroup;
+        static_assert((kPruneXcdGroup & ~PRUNE_GROUP_MASK) == 0, "the group size shares its word with PRUNE_NO_RANGE_END");
+        g.prune = kPruneXcdGroup | (t->sw.no_range_end ? PRUNE_NO_RANGE_END : 0);
         grid = round_up(g.nblocks, 8 * kPruneXcdGroup); // (prune_job_index maps whole groups)
     }
     if (fold) {
@@ -1636,6 +1639,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "fold_always") t->sw.fold_always = on;
     else if (k == "no_pad_skip") t->sw.no_pad_skip = on;
     else if (k == "no_prune") t->sw.no_prune = on;
+    else if (k == "no_range_end") t->sw.no_range_end = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h
