@@ -168,6 +168,18 @@ def shape_args(radius, min_contrast, prefix=""):
     return int(radius), int(min_contrast)
 
 
+def blob_args(radius, min_contrast, connectivity, prefix=""):
+    """What pdog_blob takes beside its arrays: shape_args' two and the connectivity, the integer 4 (edge neighbours) or 8
+    (edge and corner neighbours).  Returns (radius, min_contrast, connectivity) as the library takes them."""
+    radius, min_contrast = shape_args(radius, min_contrast, prefix)
+    name = prefix + "connectivity"
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)):
+        raise TypeError(f"{name} must be the integer 4 or 8, not {type(connectivity).__name__}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"{name}: {connectivity} is neither 4 nor 8")
+    return radius, min_contrast, int(connectivity)
+
+
 def host_samples(v, name):
     """The sample list of a background estimate: host_steps' row, of 1 ... 64 entries.  The entries are the library's to judge."""
     a = host_steps(v, name)

@@ -180,6 +180,13 @@ SHAPE_PROTOTYPES = {
 }
 SHAPE_SYMBOLS = tuple(SHAPE_PROTOTYPES)
 SHAPE_MAX_RADIUS = 127       # PDOG_SHAPE_MAX_RADIUS
+
+# the same for include/pawsome_blob.h, a header of its own that includes pawsome_dog.h: the shape of the connected blob under a
+# tracked position (tests/test_blob_cpu.py holds this table against that header)
+BLOB_PROTOTYPES = {
+    "pdog_blob": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
+}
+BLOB_SYMBOLS = tuple(BLOB_PROTOTYPES)
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -226,7 +233,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
                                       **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES,
-                                      **SHAPE_PROTOTYPES}.items():
+                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -9,7 +9,7 @@ collective, one gather of the int32 (row, col) pairs to rank 0.
 import ctypes as C
 
 from . import _lib
-from ._args import device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args, predict_args, shape_args
+from ._args import blob_args, device_array, device_frames, exclusive_args, frame_index_ptr, host_i32, host_table, motion_args, peaks_args, predict_args, shape_args
 
 
 def _targets_of(starts):
@@ -346,6 +346,31 @@ class BatchTracker(_lib.TrackerHandle):
             self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
             C.c_void_p(ij.data_ptr()), n, radius, min_contrast, C.c_void_p(sums.data_ptr()) if want_sums else None,
             C.c_void_p(shape.data_ptr())))
+        return (shape, sums) if want_sums else shape
+
+    def blobs(self, frames, ij, frame_index=None, radius=None, min_contrast=8, connectivity=8, want_sums=False):
+        """shapes() with the mask restricted to the CONNECTED BLOB under every position (pdog_blob; the rule is stated in
+        include/pawsome_blob.h): of the mask only the component that holds the darkest (brightest) pixel of the 3 x 3 under the
+        position is measured, pixels being neighbours across an edge (`connectivity` 4) or an edge or a corner (8).  A second
+        object inside the patch is then left out; two objects that touch are still one blob.  Returns float64 cuda [n, 6] as
+        shapes() does.  With want_sums (shape, sums): sums int32 cuda [n, 10], (n, Sy, Sx, Syy, Syx, Sxx, b, c, n_mask, n_rim):
+        the first eight are shapes()'s integers over the blob — shape_derive(sums[..., :8], ij) gives the floats —, n_mask
+        is the whole mask's pixel count (n_mask > n: something else in the patch reaches half the target's contrast) and
+        n_rim counts the blob pixels on the patch's rim (n_rim > 0: the blob is cut by the radius)."""
+        import torch
+        self.use_torch_stream()
+        radius, min_contrast, connectivity = blob_args(radius, min_contrast, connectivity)
+        device_frames(frames, "frames", 3, self._hw)
+        n = device_array(ij, "ij", torch.int32, (None, 2)).shape[0]
+        fi = frame_index_ptr(frame_index, n)
+        shape = torch.empty((n, 6), dtype=torch.float64, device=frames.device)
+        sums = torch.empty((n, 10), dtype=torch.int32, device=frames.device) if want_sums else None
+        if n == 0:              # (an empty tensor has no address to hand over)
+            return (shape, sums) if want_sums else shape
+        _lib.check(_lib.lib().pdog_blob(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
+            C.c_void_p(ij.data_ptr()), n, radius, min_contrast, connectivity,
+            C.c_void_p(sums.data_ptr()) if want_sums else None, C.c_void_p(shape.data_ptr())))
         return (shape, sums) if want_sums else shape
 
     def _clips_handle(self):

@@ -1,5 +1,5 @@
 // dog_shape.hpp — the kernel of the shape rule (include/pawsome_shape.h states it; pdog_shape.hpp holds its Float64 part).
-// pawsome_shape.hip alone includes this file.
+// pawsome_shape.hip includes this file, and dog_blob.hpp for the steps it shares (shape_stage_tile ... shape_contrast).
 //
 // shape_kernel: ONE workgroup of 256 threads per position, for every radius (no tiers: the loops below scale with R).
 //   1. The patch's bounding rows, D = 2R + 1 rows of D bytes, go into LDS as rows of W = ceil(D / 4) dwords, the PaddedView
@@ -49,6 +49,87 @@ __device__ __forceinline__ int shape_wave_sum(int v)
     return v;
 }
 
+// Steps 1 - 4, shared with the blob kernel (dog_blob.hpp), which measures the same patch against the same b and c.  The
+// geometry goes in BY VALUE and the loop bounds are handed over: with it by reference, or with D and W recomputed inside,
+// shape_kernel's SGPR figure moved from the 64 it had before the steps were functions (profiles/blob_kernel_regs.txt).
+// 1. the tile: D rows of W dwords from (i0, j0), the 0-based frame coordinates of its first pixel
+__device__ __forceinline__ void shape_stage_tile(const ShapeGeo g, const uint8_t *__restrict__ frame, int i0, int j0, uint32_t fill,
+                                                 uint32_t *tile, int tid, int D, int W)
+{
+    const int wb = g.colbits - 2, items = D << wb; // W <= 2^wb
+#pragma unroll 4
+    for (int e = tid; e < items; e += kShapeThreads) {
+        const int r = e >> wb, k = e & ((1 << wb) - 1);
+        if (k >= W) continue;
+        const int gi = i0 + r, c0 = j0 + 4 * k;
+        const bool row_in = gi >= 0 && gi < g.fh;
+        const uint8_t *rowp = frame + (long long)min(max(gi, 0), g.fh - 1) * g.row_stride;
+        uint32_t word = 0;
+        if (g.fw >= 4) {
+            const int cj = min(max(c0, 0), g.fw - 4);
+            uint32_t v;
+            __builtin_memcpy(&v, rowp + cj, 4);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int col = c0 + b;
+                const bool in = row_in && col >= 0 && col < g.fw; // then 0 <= col - cj <= 3
+                const uint32_t px = in ? (v >> (8 * ((col - cj) & 3))) & 0xffu : fill;
+                word |= px << (8 * b);
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int col = c0 + b;
+                const bool in = row_in && col >= 0 && col < g.fw;
+                const uint32_t px = in ? (uint32_t)rowp[min(max(col, 0), g.fw - 1)] : fill;
+                word |= px << (8 * b);
+            }
+        }
+        tile[r * W + k] = word;
+    }
+}
+
+// 2. the histogram of the disc (hist zeroed, and a barrier passed, before)
+__device__ __forceinline__ void shape_histogram(const ShapeGeo g, const uint8_t *px, uint32_t *hist, int tid, int R, int D, int P,
+                                                int cmask, int items, int R2)
+{
+    for (int e = tid; e < items; e += kShapeThreads) {
+        const int r = e >> g.colbits, c = e & cmask;
+        const int dy = r - R, dx = c - R;
+        if (c < D && dy * dy + dx * dx <= R2) atomicAdd(&hist[px[r * P + c]], 1u);
+    }
+}
+
+// 3. the lower median, by every wave for itself: the number of bins whose inclusive prefix is <= rank
+__device__ __forceinline__ int shape_median(const uint32_t *hist, int lane, int rank)
+{
+    const uint4 h4 = *(const uint4 *)&hist[4 * lane];
+    const int own = (int)(h4.x + h4.y + h4.z + h4.w);
+    int incl = own;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += t;
+    }
+    const int p0 = incl - own + (int)h4.x, p1 = p0 + (int)h4.y, p2 = p1 + (int)h4.z;
+    return shape_wave_sum((p0 <= rank) + (p1 <= rank) + (p2 <= rank) + (incl <= rank));
+}
+
+// 4. the target's contrast, from the staged 3 x 3
+__device__ __forceinline__ int shape_contrast(const uint8_t *px, int R, int P, int b, int darker)
+{
+    int c = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int p = px[(R + dy) * P + R + dx];
+            c = max(c, darker ? b - p : p - b);
+        }
+    return c;
+}
+
+#ifndef PDOG_SHAPE_STEPS_ONLY // (dog_blob.hpp takes the steps above and leaves the kernel to pawsome_shape.hip's unit)
 static __global__ __launch_bounds__(kShapeThreads) void shape_kernel(const ShapeGeo g)
 {
     __shared__ __attribute__((aligned(16))) uint32_t hist[256];
@@ -60,77 +141,19 @@ static __global__ __launch_bounds__(kShapeThreads) void shape_kernel(const Shape
     const int i = min(max(g.ij[2 * pos], 1), g.fh), j = min(max(g.ij[2 * pos + 1], 1), g.fw);
     const long long fidx = g.frame_index ? (long long)g.frame_index[pos] : pos;
     const uint8_t *__restrict__ frame = g.frames + fidx * g.frame_stride;
+
     const int i0 = i - 1 - R, j0 = j - 1 - R; // 0-based frame coordinates of the tile's first pixel
     const uint32_t fill = (uint32_t)g.fill & 0xffu;
 
     hist[tid] = 0;
-    // 1. the tile
-    {
-        const int wb = g.colbits - 2, items = D << wb; // W <= 2^wb
-#pragma unroll 4
-        for (int e = tid; e < items; e += kShapeThreads) {
-            const int r = e >> wb, k = e & ((1 << wb) - 1);
-            if (k >= W) continue;
-            const int gi = i0 + r, c0 = j0 + 4 * k;
-            const bool row_in = gi >= 0 && gi < g.fh;
-            const uint8_t *rowp = frame + (long long)min(max(gi, 0), g.fh - 1) * g.row_stride;
-            uint32_t word = 0;
-            if (g.fw >= 4) {
-                const int cj = min(max(c0, 0), g.fw - 4);
-                uint32_t v;
-                __builtin_memcpy(&v, rowp + cj, 4);
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int col = c0 + b;
-                    const bool in = row_in && col >= 0 && col < g.fw; // then 0 <= col - cj <= 3
-                    const uint32_t px = in ? (v >> (8 * ((col - cj) & 3))) & 0xffu : fill;
-                    word |= px << (8 * b);
-                }
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int col = c0 + b;
-                    const bool in = row_in && col >= 0 && col < g.fw;
-                    const uint32_t px = in ? (uint32_t)rowp[min(max(col, 0), g.fw - 1)] : fill;
-                    word |= px << (8 * b);
-                }
-            }
-            tile[r * W + k] = word;
-        }
-    }
+    shape_stage_tile(g, frame, i0, j0, fill, tile, tid, D, W);
     __syncthreads();
     const uint8_t *px = (const uint8_t *)tile;
     const int cmask = (1 << g.colbits) - 1, items = D << g.colbits, R2 = R * R;
-    // 2. the histogram of the disc
-    for (int e = tid; e < items; e += kShapeThreads) {
-        const int r = e >> g.colbits, c = e & cmask;
-        const int dy = r - R, dx = c - R;
-        if (c < D && dy * dy + dx * dx <= R2) atomicAdd(&hist[px[r * P + c]], 1u);
-    }
+    shape_histogram(g, px, hist, tid, R, D, P, cmask, items, R2);
     __syncthreads();
-    // 3. the lower median: the number of bins whose inclusive prefix is <= rank
-    int b;
-    {
-        const uint4 h4 = *(const uint4 *)&hist[4 * lane];
-        const int own = (int)(h4.x + h4.y + h4.z + h4.w);
-        int incl = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        const int p0 = incl - own + (int)h4.x, p1 = p0 + (int)h4.y, p2 = p1 + (int)h4.z;
-        b = shape_wave_sum((p0 <= g.rank) + (p1 <= g.rank) + (p2 <= g.rank) + (incl <= g.rank));
-    }
-    // 4. the target's contrast
-    int c = 0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int p = px[(R + dy) * P + R + dx];
-            c = max(c, g.darker ? b - p : p - b);
-        }
+    const int b = shape_median(hist, lane, g.rank);
+    const int c = shape_contrast(px, R, P, b, g.darker);
     // 5. the sums over the mask
     int n = 0, sy = 0, sx = 0, syy = 0, syx = 0, sxx = 0;
     if (c >= g.min_contrast) {
@@ -190,5 +213,7 @@ static __global__ __launch_bounds__(kShapeThreads) void shape_kernel(const Shape
         }
     }
 }
+
+#endif
 
 } // namespace pdog

@@ -142,17 +142,30 @@ def headings(shape_or_theta, indices, min_step=1.0):
     return out
 
 
-def _shape_keywords(shape, shape_radius, shape_min_contrast):
-    """The shape keywords of the track functions, judged before anything touches the device: (radius, min_contrast) as the
-    library takes them, or None without shape."""
-    from ._args import shape_args
+def _shape_keywords(shape, shape_radius, shape_min_contrast, shape_connectivity=None):
+    """The shape keywords of the track functions, judged before anything touches the device: (radius, min_contrast,
+    connectivity) as the library takes them — connectivity None: the shape rule, 4 or 8: the blob rule —, or None without
+    shape."""
+    from ._args import blob_args, shape_args
     if not isinstance(shape, bool):
         raise TypeError("shape must be True or False")
     if not shape:
         if shape_radius is not None or shape_min_contrast is not None:
             raise ValueError("shape_radius and shape_min_contrast belong to shape")
+        if shape_connectivity is not None:
+            raise ValueError("shape_connectivity belongs to shape")
         return None
-    return shape_args(shape_radius, 8 if shape_min_contrast is None else shape_min_contrast, "shape_")
+    mc = 8 if shape_min_contrast is None else shape_min_contrast
+    if shape_connectivity is None:
+        return shape_args(shape_radius, mc, "shape_") + (None,)
+    return blob_args(shape_radius, mc, shape_connectivity, "shape_")
+
+
+def _shapes_or_blobs(bt, frames, ij, fi, kw):
+    """BatchTracker.shapes, or .blobs where the keywords name a connectivity: float64 cuda [n, 6]."""
+    if kw[2] is None:
+        return bt.shapes(frames, ij, fi, kw[0] or None, kw[1])
+    return bt.blobs(frames, ij, fi, kw[0] or None, kw[1], kw[2])
 
 
 class _PaddedFrame:
@@ -237,6 +250,24 @@ class Tracker(_lib.TrackerHandle):
         v = tuple(float(x) for x in out[0].cpu())
         return (v, tuple(int(x) for x in sums[0].cpu())) if want_sums else v
 
+    def blob(self, ij, radius=None, min_contrast=8, connectivity=8, want_sums=False):
+        """shape() over the connected blob under the position (pdog_blob; include/pawsome_blob.h): (row, col, theta, major,
+        minor, width) as BatchTracker.blobs describes them — and, with want_sums, the rule's ten integers.  Synchronous, like
+        the functor."""
+        import torch
+        from ._args import blob_args
+        radius, min_contrast, connectivity = blob_args(radius, min_contrast, connectivity)
+        f, p = _to_device(self.img.data, ij, self.device)
+        out = torch.empty((1, 6), dtype=torch.float64, device=f.device)
+        sums = torch.empty((1, 10), dtype=torch.int32, device=f.device)
+        torch.cuda.current_stream(f.device).synchronize()     # the upload is on torch's stream
+        _lib.check(_lib.lib().pdog_blob(self._h, C.c_void_p(f.data_ptr()), f.stride(0), f.stride(1), 1, None,
+                                        C.c_void_p(p.data_ptr()), 1, radius, min_contrast, connectivity,
+                                        C.c_void_p(sums.data_ptr()), C.c_void_p(out.data_ptr())))
+        self.sync()
+        v = tuple(float(x) for x in out[0].cpu())
+        return (v, tuple(int(x) for x in sums[0].cpu())) if want_sums else v
+
 
 def get_guess(start_location, img, sar=1.0):
     """src/PawsomeTracker.jl:74-90: CartesianIndex -> Tuple; (x, y) -> round.((y, x/sar));
@@ -270,7 +301,8 @@ def get_start_ij_and_tracker(start_location, img, target_width, window_size, dar
 
 
 def track_frames(frames, target_width=25, start_location=None, window_size=None, darker_target=True,
-                 sar=1.0, device=0, diagnostic=None, subpixel=False, shape=False, shape_radius=None, shape_min_contrast=None):
+                 sar=1.0, device=0, diagnostic=None, subpixel=False, shape=False, shape_radius=None, shape_min_contrast=None,
+                 shape_connectivity=None):
     """The frame loop of track_one (src/PawsomeTracker.jl:159-169) on already-decoded GRAY8
     frames (decode stays with the host application): indices[1] from the bootstrap (:161),
     then indices[k] = trckr(indices[k-1]) per frame (:166-167, the intended loop).
@@ -282,8 +314,10 @@ def track_frames(frames, target_width=25, start_location=None, window_size=None,
     frame included — Tracker.measure at each returned position (this library's addition; the indices are unchanged).
     With shape=True the result gains a trailing `shape`, behind sub where that is present: one (row, col, theta, major,
     minor, width) per frame — Tracker.shape at each returned position with shape_radius (None: ceil(target_width)) and
-    shape_min_contrast (None: 8); ValueError for either without shape.  Everything else is what it is without the keyword."""
-    shp = _ShapeSink(shape, shape_radius, shape_min_contrast)
+    shape_min_contrast (None: 8); ValueError for either without shape.  Everything else is what it is without the keyword.
+    shape_connectivity = 4 or 8 measures `shape` over the connected blob under the position (Tracker.blob; include/pawsome_blob.h)
+    instead; None is the shape rule as before; ValueError without shape."""
+    shp = _ShapeSink(shape, shape_radius, shape_min_contrast, shape_connectivity)
     sub = [] if subpixel else None
     if diagnostic is None:
         ijs = _track_one(frames, target_width, start_location, window_size, darker_target, sar, device, None, None, sub, shp)
@@ -296,13 +330,15 @@ def track_frames(frames, target_width=25, start_location=None, window_size=None,
 
 
 def track_segments(segments, start_locations=None, target_width=25, window_size=None, darker_target=True,
-                   sar=1.0, device=0, diagnostic=None, subpixel=False, shape=False, shape_radius=None, shape_min_contrast=None):
+                   sar=1.0, device=0, diagnostic=None, subpixel=False, shape=False, shape_radius=None, shape_min_contrast=None,
+                   shape_connectivity=None):
     """track(files::AbstractVector; ...) (src/PawsomeTracker.jl:181-214) on already-decoded segments: `segments` is a
     list of frame iterables, `start_locations` one start location per segment (default all None).  A None after the
     first segment takes the previous segment's last position (coalesce(loc, end_location), :204-206).  One overlay
     trace spans every segment (one `Diagnose`, :201), across frame sizes.  Returns the concatenated positions — and,
-    with subpixel=True, (positions, sub) as track_frames does; with shape=True the trailing `shape` as track_frames does."""
-    shp = _ShapeSink(shape, shape_radius, shape_min_contrast)
+    with subpixel=True, (positions, sub) as track_frames does; with shape=True the trailing `shape` as track_frames does
+    (shape_connectivity as there)."""
+    shp = _ShapeSink(shape, shape_radius, shape_min_contrast, shape_connectivity)
     segments = list(segments)
     locs = [None] * len(segments) if start_locations is None else list(start_locations)
     if len(locs) != len(segments):
@@ -334,13 +370,17 @@ def _overlay(dia, frame, ij, device):
 class _ShapeSink:
     """The shape keywords of track_frames and track_segments: judged at once, then one Tracker.shape per returned position."""
 
-    def __init__(self, shape, shape_radius, shape_min_contrast):
-        self.args = _shape_keywords(shape, shape_radius, shape_min_contrast)
+    def __init__(self, shape, shape_radius, shape_min_contrast, shape_connectivity=None):
+        self.args = _shape_keywords(shape, shape_radius, shape_min_contrast, shape_connectivity)
         self.rows = []
 
     def measure(self, trckr, ij):
-        if self.args is not None:
+        if self.args is None:
+            return
+        if self.args[2] is None:
             self.rows.append(trckr.shape(ij, self.args[0] or None, self.args[1]))
+        else:
+            self.rows.append(trckr.blob(ij, self.args[0] or None, self.args[1], self.args[2]))
 
     def behind(self, res):
         """res with the shapes as its last element, if they were asked for."""
@@ -489,8 +529,8 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, shape=False, shape_radius=None, shape_min_contrast=None, background=None, background_chunk=256,
-                predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
+                min_distance=None, shape=False, shape_radius=None, shape_min_contrast=None, shape_connectivity=None, background=None,
+                background_chunk=256, predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -551,12 +591,15 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     width; NaN where no blob reaches the contrast.  It is measured on the frames the tracker saw: the subtracted ones under
     background, chunk by chunk as subpixel is, and independent of background_chunk.  headings(shape, indices) turns theta into a
     heading along the motion.  ValueError for shape_radius or shape_min_contrast without shape; every result without the
-    keyword is what it is today."""
+    keyword is what it is today.
+    `shape_connectivity` = 4 or 8 measures `shape` over the CONNECTED BLOB under every position instead
+    (BatchTracker.blobs; include/pawsome_blob.h states the rule): a second object inside the radius is left out.  None is the
+    shape rule, bit for bit as before.  ValueError without shape."""
     import torch
     from ._args import background_k, device_frames, exclusive_args, motion_args, peaks_args, predict_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
-    shape_kw = _shape_keywords(shape, shape_radius, shape_min_contrast)
+    shape_kw = _shape_keywords(shape, shape_radius, shape_min_contrast, shape_connectivity)
     if isinstance(background_chunk, bool) or not isinstance(background_chunk, (int, np.integer)):
         raise TypeError("background_chunk must be an integer")
     if background_chunk < 1:
@@ -679,7 +722,7 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 if subpixel:
                     sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
                 if shape_kw:
-                    shp = bt.shapes(frames, out.view(-1, 2), fi, shape_kw[0] or None, shape_kw[1]).view(nt, m, 6)
+                    shp = _shapes_or_blobs(bt, frames, out.view(-1, 2), fi, shape_kw).view(nt, m, 6)
             else:                        # the same over the subtracted frames, a buffer of them at a time
                 out = torch.zeros((nt, m, 2), dtype=torch.int32, device=dev)
                 state = torch.zeros((nt, m), dtype=torch.int32, device=dev) if exclusive or motion or predict else None
@@ -700,8 +743,7 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     if subpixel:
                         sub[:, k0:k0 + nk] = bt.measure(buf[:nk], o.reshape(-1, 2).contiguous(), fi).view(nt, nk, 2)
                     if shape_kw:
-                        shp[:, k0:k0 + nk] = bt.shapes(buf[:nk], o.reshape(-1, 2).contiguous(), fi, shape_kw[0] or None,
-                                                       shape_kw[1]).view(nt, nk, 6)
+                        shp[:, k0:k0 + nk] = _shapes_or_blobs(bt, buf[:nk], o.reshape(-1, 2).contiguous(), fi, shape_kw).view(nt, nk, 6)
             bt.sync()                    # what the kernels raised (PdogError) surfaces before the positions are handed out
             if diagnostic is not None:
                 from .diagnose import Diagnose
