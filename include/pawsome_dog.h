@@ -168,6 +168,10 @@ int pdog_set_exact(pdog_tracker *t, int on);
  *   "no_prune"     roll batches stay dense: no pre-pass, every strip computes every sub-chunk (pdog_get_prune_counts)
  *   "no_range_end" pruned roll batches run full-length column-pass bodies to the end of every kept range (default: entered
  *                  at the first tap block that still feeds an emitted output)
+ *   "fenced_publish" the pre-pass of pruned roll batches counts per workgroup and orders its arrivals acquire-release at
+ *                  device scope (default: one relaxed atomic per workgroup on a packed word; a batch of 2^20 windows or
+ *                  more, or whose kept strips or (slot, sub-chunk) pairs could exceed 2^20 / 2^24, takes this form anyway).
+ *                  Results and pdog_get_prune_counts are the same either way
  *   "measure_global" pdog_measure reads the frame itself instead of staging each position's pixels in LDS (its path for l > 93)
  * Unknown key: PDOG_E_ARG.  Drains the tracker's stream. */
 int pdog_set_tuning(pdog_tracker *t, const char *key, int value);

@@ -203,9 +203,12 @@ struct LaunchGeo {
     // is the number of consecutive jobs that go to one XCD (a power of two, prune_job_index) in the bits of PRUNE_GROUP_MASK,
     // and PRUNE_NO_RANGE_END beside it: the strips run full-length column-pass bodies to the end of a kept range
     // (pdog_set_tuning "no_range_end"; dog_roll.hpp, roll_strip).
+    // The pre-pass itself receives the word with PRUNE_FENCED_PUBLISH alone, or zero: set, its workgroups meet through the
+    // acquire-release arrival and per-workgroup counts (a batch whose counts do not fit the packed word, or pdog_set_tuning
+    // "fenced_publish"; dog_prune.hpp, the publish block).
     int prune;
 };
-constexpr int PRUNE_GROUP_MASK = 0xffff, PRUNE_NO_RANGE_END = 1 << 30;
+constexpr int PRUNE_GROUP_MASK = 0xffff, PRUNE_NO_RANGE_END = 1 << 30, PRUNE_FENCED_PUBLISH = 1 << 29;
 
 constexpr int FOLD_GO = 5; // output rows per lane and pass of a folded remainder column (257 rows = 64 lanes × 5 + 1 …)
 // Column pass + peak of ONE window column whose row-pass outputs Rc[0 … n1 + L − 2] (+ FOLD_GO readable entries of padding) sit

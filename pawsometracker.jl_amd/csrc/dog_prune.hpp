@@ -54,6 +54,7 @@
 #pragma once
 #include "dog_roll.hpp"
 #include "dog_prune_words.hpp"
+#include "dog_prune_publish.hpp"
 
 namespace pdog {
 
@@ -62,8 +63,8 @@ struct PruneGeo {
     double kinv;              // 255 / ‖K‖₂ with ‖K‖₂ rounded up
     float tmax;               // T_max (header comment)
     int darker;               // sign of the cell sums that point at a target
-    unsigned long long *stat; // [0] kept, [1] total (slot, sub-chunk) pairs since the tracker was created, [2] of the batch in flight: arrivals | jobs appended << 32
-    uint64_t *host;           // Mailbox::prune_pub, one host-coherent word: the low halves of [0] and ([1] << 32) as the last workgroup of a batch saw them
+    unsigned long long *stat; // [0] kept, [1] total (slot, sub-chunk) pairs since the tracker was created, [2] of the batch in flight: arrivals, jobs appended, pairs kept (dog_prune_publish.hpp; PRUNE_FENCED_PUBLISH: arrivals | jobs appended << 32)
+    uint64_t *host;           // Mailbox::prune_pub, one host-coherent word: the low half of [0] and ([1] << 32) as the last workgroup of a batch left them
     PruneJob *jobs;           // the job list: the header, then room for n · nstrips entries
 };
 
@@ -577,26 +578,51 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
             njobs += __builtin_popcountll(__builtin_amdgcn_ballot_w64(job));
         }
         kept = wave_sum(kept);
-        // One returning atomic per workgroup, as before: stat[2] takes the arrival in its low half and the window's job count in
-        // its high half, and returns how many workgroups arrived before this one and how many jobs they appended — the place of
-        // this window's entries in the list.  The last workgroup of the batch publishes the pair counts where the host sees
-        // them without a copy or a wait (the way dog_finish_kernel publishes its flagged count: one plain store per batch;
-        // every workgroup's additions to stat[0] and stat[1] precede its arrival), writes the batch's job count to the list's
-        // header, where the strips read it, and zeroes stat[2] for the next batch.  The entries themselves are read by the
-        // next kernel in the stream: no order among them and the arrivals is needed.  (Tried: arrival and kept pairs in ONE
-        // atomic per workgroup instead of three on neighbouring words: the kernel's time did not move.  A separate running job
-        // count, a second returning atomic per workgroup: the kernel 5 % slower.)
+        // ONE returning atomic per workgroup, relaxed: stat[2] is the packed word of dog_prune_publish.hpp (arrivals, jobs
+        // appended, pairs kept) and the add returns the state before this workgroup — how many arrived before it, the place of
+        // this window's entries in the list, and what the earlier windows kept.  The last workgroup of the batch so holds the
+        // batch's job count and kept pairs in registers (the returned fields plus its own; the batch's total is geometry,
+        // n · nslots · nsub) and reads nobody else's memory: it alone adds the two sums to the cumulative stat[0] and stat[1],
+        // publishes what those adds return plus the sums where the host sees it without a copy or a wait (the way
+        // dog_finish_kernel publishes its flagged count: one plain store per batch), writes the batch's job count to the
+        // list's header, where the strips read it, and zeroes stat[2] for the next batch.
+        // WHY NO ORDERING IS NEEDED.  The read-modify-writes on one address have a single total order whatever their memory
+        // order, so every workgroup sees the exact sum of those before it and exactly one sees n − 1 arrivals.  The list
+        // entries, part_mask and the empty strips' Peak are read by later kernels in the stream, and stat[0] / stat[1] by
+        // pdog_get_prune_counts after a drain: the kernel boundary orders them.  The zeroing store follows the same thread's
+        // add on the same address, and nobody adds after the last arriver.
+        // (Before: every workgroup added its counts to stat[0] and stat[1] and the arrival was acquire-release at agent scope,
+        // so that the last one might load those two words.  On this part that ordering is cache maintenance — a write-back of
+        // the XCD's L2 ahead of the atomic and an invalidate after it, once per workgroup, 4096 times per cfg3 step, under
+        // everybody else's tile loads; profiles/publish_ab.txt.  That form remains behind PRUNE_FENCED_PUBLISH for batches
+        // whose counts do not fit the packed fields (pp_fits) and for pdog_set_tuning "fenced_publish".  Tried there: arrival
+        // and kept pairs in one atomic instead of three on neighbouring words, the fence kept: the kernel's time did not move.
+        // A separate running job count, a second returning atomic per workgroup: the kernel 5 % slower.)
         unsigned base = 0;
         if (lane == 0) {
-            __hip_atomic_fetch_add(pg.stat, (unsigned long long)kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(pg.stat + 1, (unsigned long long)(g.nslots * nsub), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long v = __hip_atomic_fetch_add(pg.stat + 2, 1ull | ((unsigned long long)njobs << 32), __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            base = (unsigned)(v >> 32);
-            if ((unsigned)v == gridDim.x - 1) {
-                __hip_atomic_store(pg.stat + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long k = __hip_atomic_load(pg.stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), tt = __hip_atomic_load(pg.stat + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(pg.host, (k & 0xffffffffull) | (tt << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(&pg.jobs[0].b, (int)(base + (unsigned)njobs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (g.prune & PRUNE_FENCED_PUBLISH) {
+                __hip_atomic_fetch_add(pg.stat, (unsigned long long)kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(pg.stat + 1, (unsigned long long)(g.nslots * nsub), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long v = __hip_atomic_fetch_add(pg.stat + 2, 1ull | ((unsigned long long)njobs << 32), __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+                base = (unsigned)(v >> 32);
+                if ((unsigned)v == gridDim.x - 1) {
+                    __hip_atomic_store(pg.stat + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long k = __hip_atomic_load(pg.stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), tt = __hip_atomic_load(pg.stat + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(pg.host, pp_host_word(k, tt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(&pg.jobs[0].b, (int)(base + (unsigned)njobs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            } else {
+                const unsigned long long v = __hip_atomic_fetch_add(pg.stat + 2, (unsigned long long)pp_increment((uint32_t)njobs, (uint32_t)kept), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const PpArrival a = pp_arrive(v, (uint32_t)njobs, (uint32_t)kept, gridDim.x);
+                base = a.base;
+                if (a.last) {
+                    __hip_atomic_store(pg.stat + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long total = (unsigned long long)gridDim.x * (unsigned long long)(g.nslots * nsub);
+                    const unsigned long long k = __hip_atomic_fetch_add(pg.stat, (unsigned long long)a.kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + a.kept;
+                    const unsigned long long tt = __hip_atomic_fetch_add(pg.stat + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + total;
+                    __hip_atomic_store(pg.host, pp_host_word(k, tt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(&pg.jobs[0].b, (int)a.jobs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
         }
         base = __builtin_amdgcn_readfirstlane(base);

@@ -90,6 +90,7 @@ struct Switches {
     bool no_pad_skip = false;             // roll kernels: sub-chunks that hold padding only run the full path (dog_roll.hpp, "padding rows")
     bool no_prune = false;                // roll batches stay dense: no pre-pass, no kept ranges (dog_prune.hpp)
     bool no_range_end = false;            // pruned roll batches: full-length column-pass bodies to the end of a kept range (dog_roll_range.hpp)
+    bool fenced_publish = false;          // pre-pass: per-workgroup counts and an acquire-release arrival also where the packed word fits (dog_prune.hpp, the publish block)
     bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
     bool measure_global = false;          // pdog_measure reads the frame itself instead of staging each position's pixel tile in LDS
     bool fault_inject = false;            // tests: one sub-window of a tiled chain never delivers its second frame's partial (the device-side waits must give up)
@@ -129,6 +130,7 @@ Switches read_switches()
     w.no_pad_skip = on("PDOG_NO_PAD_SKIP");
     w.no_prune = on("PDOG_NO_PRUNE");
     w.no_range_end = on("PDOG_NO_RANGE_END");
+    w.fenced_publish = on("PDOG_FENCED_PUBLISH");
     w.no_roll_map = on("PDOG_NO_ROLL_MAP");
     w.no_host_dc = on("PDOG_NO_HOST_DC");
     w.tiled_force = on("PDOG_TILED_FORCE");
@@ -328,7 +330,7 @@ struct pdog_tracker {
     // kept ranges on the roll family's batch path (dog_prune.hpp; pdog_policy.hpp)
     PrunePolicy prune_policy;
     double K_norm = 0;                       // ‖K‖₂ of the dense kernel, rounded up (dog_kernel_norm_up)
-    DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] arrivals of the pre-pass in flight | jobs it has appended << 32
+    DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] the pre-pass in flight: arrivals, jobs appended, pairs kept (dog_prune_publish.hpp)
     DeviceBuffer<PruneJob> d_prune_jobs;     // the kept strips of the batch in flight: the header, then up to n·nstrips entries (dog_prune.hpp, "the job list")
     int last_n = 0, last_nslots = 0;         // windows and partial slots per window of the last launch_strips batch (pdog_get_batch_maxima)
     DeviceBuffer<float> d_map; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
@@ -1241,6 +1243,10 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     if (prune) { // the pre-pass leaves every slot's kept range in part_mask, ahead of the strips and (through the fork) the thin kernel
         PruneGeo pg;
         pg.g = g;
+        // (decided per launch: a batch whose arrivals, jobs or kept pairs could overflow their fields of the packed word keeps
+        // the fenced publish; dog_prune_publish.hpp)
+        const int nsub = (t->n1 + t->L - 1 + ROLL_CH - 1) / ROLL_CH;
+        pg.g.prune = (t->sw.fenced_publish || !pp_fits(n, g.nstrips, g.nslots, nsub)) ? PRUNE_FENCED_PUBLISH : 0;
         pg.kinv = 255.0 / t->K_norm;
         pg.tmax = std::max(g.ex.T, g.ex.T_rescan);
         pg.darker = t->darker;
@@ -1640,6 +1646,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "no_pad_skip") t->sw.no_pad_skip = on;
     else if (k == "no_prune") t->sw.no_prune = on;
     else if (k == "no_range_end") t->sw.no_range_end = on;
+    else if (k == "fenced_publish") t->sw.fenced_publish = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
     else if (k == "measure_global") t->sw.measure_global = on;
     else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h

@@ -45,7 +45,11 @@ private:
 // profiles/prepass_profile_this.txt.  The constant has not followed yet: bench data at ±40 levels keeps 76 % of its pairs,
 // right at the share that ratio would give, and whether pruning pays there is unmeasured — profiles/prepass_ab.txt.
 // With clamped loads and the next cell's loads in flight: 0.302 ms, 23 % — profiles/prepass_latency_ab.txt.
-// With the job list, which the pre-pass also files: 0.306 ms, still 23 % — profiles/compact_ab.txt.)
+// With the job list, which the pre-pass also files: 0.306 ms, still 23 % — profiles/compact_ab.txt.
+// With the relaxed publish: 0.148 ms, 11 %.  And the ±40-level question is now measured — profiles/publish_ab.txt: with the
+// constant at 11 those batches, 76 % kept, run pruned and take 1.510 ms where the dense path takes 1.364.  What decides at such a
+// share is the PRUNE instance on three quarters of the sub-chunks against the dense instance on all of them, not the pre-pass:
+// the constant stays, and stands for that.)
 // The pre-pass publishes its cumulative kept / total counts in one word (Mailbox::prune_pub); when the pairs counted since the
 // last look kept more than the break-even share, the next kPruneProbeEvery batches run dense, then one batch probes again.
 constexpr int kPrunePrePct = 36;
