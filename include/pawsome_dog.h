@@ -166,6 +166,8 @@ int pdog_set_exact(pdog_tracker *t, int on);
  *   "no_fold" / "fold_always"  a single remainder column always / never goes to the remainder-column kernel
  *   "no_pad_skip"  the roll kernels run their full path also on sub-chunks (8 tile rows of a strip) that hold padding only
  *   "no_prune"     roll batches stay dense: no pre-pass, every strip computes every sub-chunk (pdog_get_prune_counts)
+ *   "no_refine"    pruned roll batches run the ranges of the pre-pass's first stage as they are (default: each narrowed by a
+ *                  second bound per 8 x 8 output cell; pawsome_refine.h).  Results and pdog_get_prune_counts are the same
  *   "no_range_end" pruned roll batches run full-length column-pass bodies to the end of every kept range (default: entered
  *                  at the first tap block that still feeds an emitted output)
  *   "fenced_publish" the pre-pass of pruned roll batches counts per workgroup and orders its arrivals acquire-release at
@@ -433,5 +435,7 @@ int pdog_diag_render(pdog_diag *d, void *hip_stream, const uint8_t *d_frames, in
 #include "pawsome_background.h"
 /* how a target lies at a tracked position — orientation, axes, width: pdog_shape, pdog_shape_derive, pdog_shape_headings */
 #include "pawsome_shape.h"
+/* test hook of the pre-pass's second stage, the ranges the pruned strips run: pdog_get_prune_jobs */
+#include "pawsome_refine.h"
 
 #endif /* PAWSOME_DOG_H */

@@ -14,7 +14,7 @@ extern "C" {
 
 /* Batches on the rolling-accumulator kernels first bound, per window, which 8-row blocks of which 64-column strips can hold
  * the peak or a near-tie of it, and compute only those (positions and exact mode's decisions are unchanged by construction).
- * out[0] / out[1]: (strip, 8-row sub-chunk) pairs computed / present, summed over the batches that ran the bounding pass
+ * out[0] / out[1]: (strip, 8-row sub-chunk) pairs kept by the first-stage hull / present, summed over the batches that ran the bounding pass
  * since the tracker was created (batches that ask for the response map, pdog_set_exact(t, 2), "no_prune" and batches the
  * library found not worth bounding run dense and count nothing).  Drains the stream. */
 int pdog_get_prune_counts(pdog_tracker *t, uint64_t out[2]);

@@ -187,6 +187,13 @@ BLOB_PROTOTYPES = {
     "pdog_blob": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
 }
 BLOB_SYMBOLS = tuple(BLOB_PROTOTYPES)
+
+# the same for include/pawsome_refine.h, the sixth header pawsome_dog.h includes: the ranges the pruned strips run, a test hook
+# (tests/test_prune_refine_cpu.py holds this table against that header)
+REFINE_PROTOTYPES = {
+    "pdog_get_prune_jobs": (_i, [_p, _i, _p, _pi]),
+}
+REFINE_SYMBOLS = tuple(REFINE_PROTOTYPES)
 DEFAULT_STOP = 86399.999     # PDOG_DEFAULT_STOP: DEFAULT_MAX_DURATION_SECONDS, src/PawsomeTracker.jl:19
 
 
@@ -233,7 +240,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
                                       **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES,
-                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES}.items():
+                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES, **REFINE_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -347,6 +354,17 @@ class TrackerHandle(Handle):
         out = np.empty(int(n), np.float32)
         check(lib().pdog_get_batch_maxima(self._h, int(n), C.c_void_p(out.ctypes.data)))
         return out
+
+    def prune_jobs(self):
+        """Test hook (not stable ABI): the strips the last batch that ran the bounding pre-pass left to compute, numpy int32 [m][4] of
+        (window, strip, first 8-row block, one past the last block) in the order they were filed — pdog_get_prune_jobs."""
+        import numpy as np
+        count = C.c_int()
+        check(lib().pdog_get_prune_jobs(self._h, 0, None, C.byref(count)))
+        out = np.empty((count.value, 4), np.int32)
+        if count.value:
+            check(lib().pdog_get_prune_jobs(self._h, count.value, C.c_void_p(out.ctypes.data), C.byref(count)))
+        return out[:count.value]
 
     def kernel_for_batch(self, n):
         """Variant id of the kernel family a batch of n windows runs on (300 fused, 400 tiled, 200 two-pass, else info().variant)."""

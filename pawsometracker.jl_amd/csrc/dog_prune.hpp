@@ -34,6 +34,32 @@
 // window's refinement still finds it; every pixel the refinement no longer rescans has f(q) < f(p*) and could not have won.
 // For columns that hold a pixel within T of M the masks of kept strips are unchanged.
 //
+// THE CELL BOUND, a second stage inside the first stage's hull.  One inequality per block against everything the block reads
+// is loose: a block that sees a disc only through the kernel's outermost rows stays, and so does a neighbouring strip that sees
+// it through its outermost columns.  Cut the tile into 8 × 8 cells, as the energy pass does.  Output cell (yb, xb) is window rows
+// 8yb … 8yb + 7, columns 8xb … 8xb + 7; its output (y, x) = (8yb + i, 8xb + j) reads tile rows y … y + l − 1, that is the input
+// cells (yb + dy, xb + dx), dy, dx < NS = prune_span(l), and lays on cell (dy, dx) exactly the kernel rows
+// rows(i, dy) = [8dy − i, 8dy − i + 8) ∩ [0, l) and the like columns: the NS² boxes tile K.  Cauchy–Schwarz per input cell gives
+//     255·|f(y, x)| ≤ Σ_{dy,dx} ‖K[rows(i, dy), cols(j, dx)]‖₂ · sqrt(Ec[yb + dy][xb + dx])
+//                  ≤ Σ_{dy,dx} W[dy][dx] · sqrt(Ec[yb + dy][xb + dx]) =: B(yb, xb),
+// Ec = Σ v² over the input cell (fill and DC level as in the energies, zero outside the tile) and W[dy][dx] the largest of the
+// 64 partial norms.  An output cell is excluded iff B < 255·(L − 2δ(V) − T_max): the first stage's own threshold, only the left
+// side is new.  A block of a slot stays iff the first stage keeps it AND an output cell that meets the slot's columns (a strip at
+// c0 of w columns: cells c0 >> 3 … (c0 + w − 1) >> 3, nine where the strip is shifted off the grid; a remainder column: its one
+// cell) is not excluded; the refined range is the contiguous hull of those blocks, a sub-range of the first stage's, maybe empty.
+// WHY NOTHING CHANGES: an excluded pixel q lies in an excluded cell or outside the first stage's hull; either way
+// |f(q)| ≤ bound/255 < L − 2δ(V) − T_max, the inequality the argument above starts from, which then carries over word for word.
+// The cell that holds L's best pixel p has B ≥ 255·|f(p)| ≥ 255·(L − δ(V)) and is never excluded: L ≤ M stands, and no window's
+// refined ranges are all empty while its first-stage ranges are not.
+// ARITHMETIC: exact and the same on every machine, every rounding towards keeping.  r = ⌈16·√Ec⌉ as an integer (pw_root16: the
+// f32 estimate corrected by integer comparisons), 16 bits per cell in LDS; Wq = ⌈2¹²·W/‖K‖₂⌉ from the host (pdog_math.cpp,
+// dog_refine_weights); Σ Wq·r in 64-bit integers, any order; the threshold ⌊2¹⁶·q·(1 − 2⁻³⁰)⌋ with the first stage's
+// q = (L − 2δ(V) − T_max)·255/‖K‖₂ (B·‖K‖₂ ≤ Σ Wq·r·‖K‖₂/2¹⁶).  tests/prune_refine_restatement.py states it in NumPy and the
+// kernel's job list equals it entry for entry.  Nothing to do where the first stage excludes nothing (thr ≤ 0, an infinite T_max).
+// The first stage, its counts (stat[0] / stat[1], the packed word's `kept`, the host word) and the policy are as before: the
+// refined range goes into the range words, the job list and the empty strips' Peak.  Where the roots would push the dynamic LDS
+// past the host's limit, or NS > PRUNE_REFINE_MAX_SPAN, the launch passes wq = null and the first stage stands alone.
+//
 // WHERE IT STOPS PAYING: where the background's energy under the kernel reaches the target's response (heavy noise or
 // texture, noise-only and flat windows: nothing is excluded and the pre-pass is paid for nothing).  launch_strips reads the
 // kept / total counts this kernel publishes and stops running it on such batches (pawsome_dog.hip, "pruning policy").
@@ -66,6 +92,7 @@ struct PruneGeo {
     unsigned long long *stat; // [0] kept, [1] total (slot, sub-chunk) pairs since the tracker was created, [2] of the batch in flight: arrivals, jobs appended, pairs kept (dog_prune_publish.hpp; PRUNE_FENCED_PUBLISH: arrivals | jobs appended << 32)
     uint64_t *host;           // Mailbox::prune_pub, one host-coherent word: the low half of [0] and ([1] << 32) as the last workgroup of a batch left them
     PruneJob *jobs;           // the job list: the header, then room for n · nstrips entries
+    const uint32_t *wq;       // the second stage's weights (pdog_math.cpp, dog_refine_weights) as [NS][prune_refine_pitch(NS)], zeros behind each row, four more at the end; null: the first stage alone
 };
 
 constexpr int PRUNE_NT = 256;
@@ -73,8 +100,12 @@ constexpr int PRUNE_B = 8; // the L pixels: PRUNE_B × PRUNE_B outputs
 constexpr int PRUNE_PHASES = 9; // phase stamps of the diagnostic build: stat[4 … 4 + PRUNE_PHASES), then the workgroups that stamped
 // The segment sums (S) are dead once the energies are formed and the L block's buffers (R, patch) live only after that: they
 // share one region.  The patch carries 8 bytes of slack: its row pass reads whole dwords, up to 3 bytes past a row's last pixel.
-struct PruneLds { size_t cell, E, segd, strd, S, R, patch, total; };
-__host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots)
+// The second stage adds the cells' roots (16 bits each, a zero row and a zero column behind them: an output cell reads at most one
+// cell past the tile either way; what a zero weight of the padded table meets beyond that is never counted) and the refined hulls.
+constexpr int PRUNE_REFINE_MAX_SPAN = 32; // a row of NS products Wq·r ≤ 4097·32640 stays below 2³² up to here (l ≤ 249)
+__host__ __device__ inline int prune_refine_pitch(int NS) { return (NS + 3) / 4 * 4; } // a row of the weight table: whole groups of four
+struct PruneLds { size_t cell, E, segd, strd, S, R, patch, root, hull2, total; };
+__host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots, bool refine = false)
 {
     const size_t NA = n1 + L - 1, nsub = (NA + ROLL_CH - 1) / ROLL_CH, ncx = (size_t)(n2 + L - 1 + 7) / 8;
     const size_t PH = PRUNE_B + L - 1, PP = (PH + 3) / 4 * 4, nseg = 2 * (size_t)nslots + 1;
@@ -88,6 +119,11 @@ __host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots)
     o.patch = o.R + PH * PRUNE_B * sizeof(f2);
     const size_t endS = o.S + nsub * nseg * 8, endL = o.patch + PH * PP + 8;
     o.total = ((endS > endL ? endS : endL) + 15) / 16 * 16;
+    o.root = o.hull2 = o.total;
+    if (refine) {
+        o.hull2 = o.root + ((nsub + 1) * (ncx + 1) * 2 + 8 + 3) / 4 * 4; // (8: the last group of a row reads up to three roots past the row's end)
+        o.total = (o.hull2 + (size_t)nslots * 8 + 15) / 16 * 16;
+    }
     return o;
 }
 
@@ -116,7 +152,8 @@ __host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots)
 // amdgpu_waves_per_eu(7) — 72 VGPRs, five spilled, scratch loads in the cell loop: slower in every run,
 // profiles/prepass_latency_ab.txt.  A second cell in flight would be sixteen more.)  With the wave that files the job list at
 // the kernel's end the allocator took 82, five waves per SIMD: amdgpu_waves_per_eu(6) holds it to 79 with nothing spilled
-// (profiles/compact_kernel_regs.txt).
+// (profiles/compact_kernel_regs.txt).  With the second stage: 80, still six waves and nothing in scratch; fifteen of its scalars
+// pass through VGPR lanes (profiles/refine_kernel_regs.txt).
 // NARROW: the instance for frames narrower than one clamped load (below), which keeps the byte path; every other frame runs
 // the instance without it.
 template <bool NARROW>
@@ -128,7 +165,8 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
     const int L = g.L, hw = L / 2, H = L / 2;
     const int NA = g.n1 + L - 1, TWin = g.n2 + L - 1, nsub = (NA + CH - 1) / CH, ncx = (TWin + 7) / 8, TQ2 = 2 * ncx;
     const int nseg = 2 * g.nslots + 1;
-    const PruneLds lo = prune_lds(g.n1, g.n2, L, g.nslots);
+    const bool refine = pg.wq != nullptr; // (workgroup-uniform: a kernel argument)
+    const PruneLds lo = prune_lds(g.n1, g.n2, L, g.nslots, refine);
     int *cell = reinterpret_cast<int *>(smem + lo.cell);           // [nsub][ncx] Σ v over 8 × 8-pixel cells of the tile
     unsigned *E = reinterpret_cast<unsigned *>(smem + lo.E);       // [nslots][nsub]
     short *segd = reinterpret_cast<short *>(smem + lo.segd);       // [2ncx] a dword's segment; −1: it straddles a cut or lies past the tile
@@ -136,8 +174,11 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
     unsigned *S = reinterpret_cast<unsigned *>(smem + lo.S);       // [nsub][nseg] (Σ p², Σ p)
     f2 *R = reinterpret_cast<f2 *>(smem + lo.R);                   // [PB + l − 1][PB] row-pass outputs of the L pixels
     uint8_t *patch = smem + lo.patch;                              // their input pixels
+    unsigned short *root = reinterpret_cast<unsigned short *>(smem + lo.root); // [nsub + 1][ncx + 1] ⌈16·√Ec⌉ of the cells (second stage)
+    const int rp = ncx + 1;
     __shared__ int s_sum[NW], s_pmax[NW], s_pmin[NW], s_cv[NW], s_ci[NW], s_cellbest, s_nstr;
     __shared__ double s_emax;
+    __shared__ long long s_tq;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
@@ -242,6 +283,10 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
             cell_load(band0, it0 - band0 * ncx, cur);
         }
         for (int i = tid; i < nsub * nseg * 2; i += NT) S[i] = 0;
+        if (refine) { // the zero row and column behind the cells' roots
+            for (int i = tid; i <= nsub; i += NT) root[i * rp + ncx] = 0;
+            for (int i = tid; i < ncx; i += NT) root[nsub * rp + i] = 0;
+        }
         int sum = 0;
 #pragma unroll
         for (int j = 0; j < DCN; ++j) sum += sin[j] ? sv[j] : g.fill;
@@ -304,7 +349,9 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
                 }
             }
         }
-        cell[band * ncx + cx] = pw_sum(s1a + s1b, nr * min(TWin - col0, 8), dc);
+        const int npx = nr * min(TWin - col0, 8);
+        cell[band * ncx + cx] = pw_sum(s1a + s1b, npx, dc);
+        if (refine) root[band * rp + cx] = (unsigned short)pw_root16(pw_energy(s2a + s2b, s1a + s1b, npx, dc));
         const int sda = segd[2 * cx], sdb = segd[2 * cx + 1];
         unsigned *Sb = S + 2 * band * nseg;
         if (sda == sdb) {
@@ -522,7 +569,10 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
             const double dV = 0.5 * (double)g.ex.T * ((double)V * (1.0 / 255.0)) * 1.00001;
             const double thr = (double)Lv - 2.0 * dV - (double)pg.tmax;
             const double q = thr * pg.kinv;
-            s_emax = (thr > 0.0 && pg.tmax < __builtin_huge_valf()) ? q * q * (1.0 - 0x1p-30) : -1.0; // −1: nothing can be excluded
+            const bool can = thr > 0.0 && pg.tmax < __builtin_huge_valf();
+            s_emax = can ? q * q * (1.0 - 0x1p-30) : -1.0; // −1: nothing can be excluded
+            // the second stage's threshold on Σ Wq·r, whose unit is ‖K‖₂ / 2¹⁶: rounded down, the same hair low
+            s_tq = can ? (long long)(q * 65536.0 * (1.0 - 0x1p-30)) : -1ll;
         }
     }
     __syncthreads();
@@ -544,15 +594,63 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
     }
     __syncthreads();
     PRUNE_STAMP(7); // hulls
+    // ---- the second stage (header comment, "the cell bound"): inside a slot's hull, a lane per (block, output cell that meets the
+    // slot's columns) sums the NS × NS weighted roots, in integers; a block with a cell at or above the threshold stays, and the
+    // refined range is the hull of those.  A PASS is four blocks of a strip, sixteen lanes each (nine cells at most, where the
+    // strip is shifted off the cells' grid), or 64 blocks of a remainder column (one cell); the window's passes are dealt out to
+    // its four waves in turn (cfg3: two kept strips of eight blocks, a pass per wave).  The weights are wave-uniform and come
+    // four at a time as one scalar load, the next group requested before this one is used (a load per term, waited for at
+    // once, left l = 109 at −29.5 % of the parent's step where this form reaches −38.4 %, profiles/refine_ab.txt); their rows are padded to whole groups with zeros, which meet the roots of the next
+    // row.  A row's products fit 32 bits (PRUNE_REFINE_MAX_SPAN) and Wq, r fit 24 ----
+    int *hull2 = hull;
+    if (refine && s_tq >= 0) {
+        hull2 = reinterpret_cast<int *>(smem + lo.hull2);
+        for (int sl = tid; sl < g.nslots; sl += NT) { hull2[2 * sl] = 0x7fffffff; hull2[2 * sl + 1] = 0; }
+        __syncthreads();
+        const unsigned long long tq = (unsigned long long)s_tq;
+        const uint4 *__restrict__ wq4 = reinterpret_cast<const uint4 *>(pg.wq);
+        const int Q = prune_refine_pitch(NS) / 4;
+        int turn = 0;
+        for (int sl = 0; sl < g.nslots; ++sl) {
+            const int bb = __builtin_amdgcn_readfirstlane(hull[2 * sl + 1]), ba = bb == 0 ? 0 : __builtin_amdgcn_readfirstlane(hull[2 * sl]);
+            if (bb <= ba) continue;
+            int c0, c1;
+            slot_cols(sl, c0, c1);
+            const int xb0 = c0 >> 3, ncell = ((c0 + (sl < g.nstrips ? ws : 1) - 1) >> 3) - xb0 + 1;
+            const bool one = ncell == 1;
+            const int c = one ? 0 : (lane & 15), jj = one ? lane : lane >> 4;
+            for (int j0 = ba; j0 < bb; j0 += one ? 64 : 4, ++turn) {
+                if ((turn & (NW - 1)) != wave) continue;
+                const int j = j0 + jj;
+                if (j < bb && c < ncell) {
+                    const unsigned short *rr = root + j * rp + xb0 + c;
+                    unsigned long long B = 0;
+                    uint4 w = wq4[0];
+                    for (int dy = 0; dy < NS; ++dy, rr += rp) {
+                        uint32_t row = 0;
+                        for (int q = 0; q < Q; ++q) {
+                            const uint4 wn = wq4[dy * Q + q + 1]; // (the table ends with a group of zeros)
+                            row += pw_mul24(w.x, rr[4 * q]) + pw_mul24(w.y, rr[4 * q + 1]) + pw_mul24(w.z, rr[4 * q + 2]) + pw_mul24(w.w, rr[4 * q + 3]);
+                            w = wn;
+                        }
+                        B += row;
+                    }
+                    if (B >= tq) { atomicMin(&hull2[2 * sl], j); atomicMax(&hull2[2 * sl + 1], j + 1); }
+                }
+            }
+        }
+        __syncthreads();
+    }
     // ---- the window's slots are filed by its first wave, 64 at a time: the range words, the finished partial of a strip with
     // an empty hull, and the window's kept strips as consecutive entries of the job list (header comment) ----
     if (wave == 0) {
         int kept = 0, njobs = 0;
+        // (what the strips run is the refined range; `kept`, the count the policy reads, stays the first stage's)
         auto slot_hull = [&](int sl, int &ba, int &bb) {
             ba = bb = 0;
             if (sl < g.nslots) {
-                bb = hull[2 * sl + 1];
-                ba = bb == 0 ? 0 : hull[2 * sl];
+                bb = hull2[2 * sl + 1];
+                ba = bb == 0 ? 0 : hull2[2 * sl];
             }
             return sl < g.nstrips && bb > ba; // a job
         };
@@ -573,7 +671,8 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
                     g.part_idx[o] = pk.idx;
                     g.part_sec[o] = pk.second;
                 }
-                kept += prune_sc_hi(ba, bb, L, nsub) - ba;
+                const int b1 = hull[2 * sl + 1], a1 = b1 == 0 ? 0 : hull[2 * sl];
+                kept += prune_sc_hi(a1, b1, L, nsub) - a1;
             }
             njobs += __builtin_popcountll(__builtin_amdgcn_ballot_w64(job));
         }

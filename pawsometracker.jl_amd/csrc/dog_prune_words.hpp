@@ -70,7 +70,11 @@ PW_HD uint32_t pw_pk_min(uint32_t a, uint32_t b)
 {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(pw_us2, a), __builtin_bit_cast(pw_us2, b)));
 }
+PW_HD uint32_t pw_mul24(uint32_t a, uint32_t b) { return __umul24(a, b); } // a, b < 2²⁴
+PW_HD float pw_sqrt_est(float x) { return __builtin_amdgcn_sqrtf(x); }
 #else
+PW_HD uint32_t pw_mul24(uint32_t a, uint32_t b) { return a * b; }
+PW_HD float pw_sqrt_est(float x) { return __builtin_sqrtf(x); }
 PW_HD uint32_t pw_dot4(uint32_t a, uint32_t b, uint32_t c)
 {
     for (int i = 0; i < 4; ++i) c += ((a >> (8 * i)) & 0xffu) * ((b >> (8 * i)) & 0xffu);
@@ -133,6 +137,19 @@ PW_HD int pw_pmin(const PwAcc &a)
 
 // Σ (p − dc)² of n pixels from their moments (RANGE above)
 PW_HD uint32_t pw_energy(uint32_t s2, uint32_t s1, int n, int dc) { return (s2 + (uint32_t)n * (uint32_t)(dc * dc)) - 2u * (uint32_t)dc * s1; }
+// ⌈16·√e⌉ exactly, for the energy of one 8 × 8 cell (e ≤ 64·255² < 2²⁴: exact as a float, 256·e < 2³²).  The estimate
+// 16·sqrt((float)e) is within 0.01 of the true value whichever square root forms it (one rounding of the device's
+// instruction or of the host's is below 2e-7 relative, of at most 32640), so its integer part t is at most the answer
+// (an integer above t − 0.01) and at least the answer − 2 (which is below t + 2.01); two compare-and-steps reach the
+// smallest r with r² ≥ 256·e.
+PW_HD uint32_t pw_root16(uint32_t e)
+{
+    const uint32_t e256 = e << 8;
+    uint32_t r = (uint32_t)(16.0f * pw_sqrt_est((float)e));
+    r += pw_mul24(r, r) < e256;
+    r += pw_mul24(r, r) < e256;
+    return r;
+}
 // Σ (p − dc)
 PW_HD int pw_sum(uint32_t s1, int n, int dc) { return (int)s1 - n * dc; }
 // max |p − dc| from the extremes (0 when nothing was counted)

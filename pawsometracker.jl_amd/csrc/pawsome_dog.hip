@@ -89,6 +89,7 @@ struct Switches {
     bool fold_always = false;             // … always into the last strip, also below 8 strips per window
     bool no_pad_skip = false;             // roll kernels: sub-chunks that hold padding only run the full path (dog_roll.hpp, "padding rows")
     bool no_prune = false;                // roll batches stay dense: no pre-pass, no kept ranges (dog_prune.hpp)
+    bool no_refine = false;               // pruned roll batches: the first-stage hulls as they are, no bound per output cell (dog_prune.hpp, "the cell bound")
     bool no_range_end = false;            // pruned roll batches: full-length column-pass bodies to the end of a kept range (dog_roll_range.hpp)
     bool fenced_publish = false;          // pre-pass: per-workgroup counts and an acquire-release arrival also where the packed word fits (dog_prune.hpp, the publish block)
     bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
@@ -331,6 +332,8 @@ struct pdog_tracker {
     PrunePolicy prune_policy;
     double K_norm = 0;                       // ‖K‖₂ of the dense kernel, rounded up (dog_kernel_norm_up)
     DeviceBuffer<unsigned long long> d_prune_stat; // [0] kept, [1] total (slot, sub-chunk) pairs, [2] the pre-pass in flight: arrivals, jobs appended, pairs kept (dog_prune_publish.hpp)
+    DeviceBuffer<uint32_t> d_refine_wq;      // the second stage's weights (dog_refine_weights), rows padded as dog_prune_kernel reads them
+    int last_prune_n = 0, last_prune_nstrips = 0; // the last batch that ran the pre-pass (pdog_get_prune_jobs)
     DeviceBuffer<PruneJob> d_prune_jobs;     // the kept strips of the batch in flight: the header, then up to n·nstrips entries (dog_prune.hpp, "the job list")
     int last_n = 0, last_nslots = 0;         // windows and partial slots per window of the last launch_strips batch (pdog_get_batch_maxima)
     DeviceBuffer<float> d_map; // exact mode on the two-pass path: the batch's FP32 responses, where the refinement finds its candidates
@@ -1254,7 +1257,12 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
         pg.host = &t->h_pinned.device()->prune_pub;
         if (int rc = t->d_prune_jobs.reserve((size_t)g.nblocks + 1, &t->stream)) return rc;
         pg.jobs = t->d_prune_jobs.get();
-        hipLaunchKernelGGL(t->fw < 8 ? dog_prune_kernel<true> : dog_prune_kernel<false>, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots).total, t->stream, pg, tr, tc);
+        // the second stage, where its roots fit the pre-pass's LDS beside the rest (else the first stage alone, not a dense batch)
+        const bool refine = !t->sw.no_refine && prune_span(t->L) <= PRUNE_REFINE_MAX_SPAN && prune_lds(t->n1, t->n2, t->L, g.nslots, true).total <= kPruneMaxLds;
+        pg.wq = refine ? t->d_refine_wq.get() : nullptr;
+        hipLaunchKernelGGL(t->fw < 8 ? dog_prune_kernel<true> : dog_prune_kernel<false>, dim3(n), dim3(PRUNE_NT), prune_lds(t->n1, t->n2, t->L, g.nslots, refine).total, t->stream, pg, tr, tc);
+        t->last_prune_n = n;
+        t->last_prune_nstrips = g.nstrips;
         HIP_TRY(hipGetLastError());
         static_assert((kPruneXcdGroup & ~PRUNE_GROUP_MASK) == 0, "the group size shares its word with PRUNE_NO_RANGE_END");
         g.prune = kPruneXcdGroup | (t->sw.no_range_end ? PRUNE_NO_RANGE_END : 0);
@@ -1488,6 +1496,14 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
             t->F_sym_int = ef.sym_int; t->F_sym_sep = ef.sym_sep; t->F_ring = ef.ring; t->F_rescan = ef.rescan;
         }
         t->K_norm = dog_kernel_norm_up(gp, gm);
+        {
+            const std::vector<uint32_t> wq = dog_refine_weights(gp, gm, t->K_norm);
+            if ((int)wq.size() != prune_span(t->L) * prune_span(t->L)) return fail(PDOG_E_ARG, "pdog_create: the second stage's weight table has another span than the kernels");
+            const int ns = prune_span(t->L), pitch = prune_refine_pitch(ns);
+            std::vector<uint32_t> tab((size_t)ns * pitch + 4, 0u); // rows padded to whole groups of four, a group of zeros behind the last
+            for (int dy = 0; dy < ns; ++dy) std::copy(wq.begin() + (size_t)dy * ns, wq.begin() + (size_t)(dy + 1) * ns, tab.begin() + (size_t)dy * pitch);
+            if (int rc = upload(t->d_refine_wq, tab)) return rc;
+        }
         if (int rc = t->d_prune_stat.reserve(4 + PRUNE_PHASES + 1, nullptr, true)) return rc; // [4 …]: phase cycles of the pre-pass and the workgroups that stamped (diagnostic build)
         if (int rc = t->d_ref_stat.reserve(16, nullptr, true)) return rc; // [4..7] unused, [8..15]: phase cycles of the refinement (diagnostic build)
         {
@@ -1645,6 +1661,7 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "fold_always") t->sw.fold_always = on;
     else if (k == "no_pad_skip") t->sw.no_pad_skip = on;
     else if (k == "no_prune") t->sw.no_prune = on;
+    else if (k == "no_refine") t->sw.no_refine = on;
     else if (k == "no_range_end") t->sw.no_range_end = on;
     else if (k == "fenced_publish") t->sw.fenced_publish = on;
     else if (k == "fault_inject") t->sw.fault_inject = on;
@@ -1690,6 +1707,28 @@ int pdog_get_prune_counts(pdog_tracker *t, uint64_t out[2])
                      ph[PRUNE_PHASES], ph[0] / wg, ph[1] / wg, ph[2] / wg, ph[3] / wg, ph[4] / wg, ph[5] / wg, ph[6] / wg, ph[7] / wg, ph[8] / wg);
     }
 #endif
+    return PDOG_OK;
+}
+
+int pdog_get_prune_jobs(pdog_tracker *t, int capacity, int32_t *h_out, int *count)
+{
+    if (!t || !count || capacity < 0 || (capacity > 0 && !h_out)) return fail(PDOG_E_ARG, "pdog_get_prune_jobs: bad argument");
+    if (int rc = drain_and_check(t, "pdog_get_prune_jobs")) return rc;
+    if (t->last_prune_n <= 0) return fail(PDOG_E_ARG, "pdog_get_prune_jobs: no batch of this tracker ran the bounding pass");
+    PruneJob head;
+    HIP_TRY(hipMemcpy(&head, t->d_prune_jobs.get(), sizeof head, hipMemcpyDeviceToHost));
+    const long long room = (long long)t->last_prune_n * t->last_prune_nstrips;
+    if (head.b < 0 || head.b > room) return fail(PDOG_E_RANGE, "pdog_get_prune_jobs: the list's count lies outside the list");
+    *count = head.b;
+    const int m = std::min(head.b, capacity);
+    std::vector<PruneJob> jobs((size_t)m);
+    if (m) HIP_TRY(hipMemcpy(jobs.data(), t->d_prune_jobs.get() + 1, sizeof(PruneJob) * (size_t)m, hipMemcpyDeviceToHost));
+    for (int i = 0; i < m; ++i) {
+        h_out[4 * i] = jobs[i].b;
+        h_out[4 * i + 1] = jobs[i].s_dc & 0xffff;
+        h_out[4 * i + 2] = jobs[i].ba;
+        h_out[4 * i + 3] = jobs[i].bb;
+    }
     return PDOG_OK;
 }
 

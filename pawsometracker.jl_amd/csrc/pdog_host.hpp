@@ -37,6 +37,17 @@ void dense_dog_kernel(const double *gp, const double *gm, int l, bool darker, do
 struct ExactFactors { double sym_int, sym_sep, ring, rescan; };
 ExactFactors exact_factors(const std::vector<double> &gp, const std::vector<double> &gm); // exact mode's FP32 error-bound factors
 double dog_kernel_norm_up(const std::vector<double> &gp, const std::vector<double> &gm);  // ‖K‖₂ of the dense kernel, rounded up (dog_prune.hpp's bound)
+// The pre-pass's second stage (dog_prune.hpp, "the cell bound"): Σ K² of the box of the dense kernel that an output at offset
+// (i, j) of its 8 × 8 cell takes from the input cell (dy, dx) cells further on, and the integer weights of the NS × NS input
+// cells, NS = refine_span(l) (= prune_span(l), dog_roll_range.hpp), in units of ‖K‖₂ / 2¹², rounded up.
+inline int refine_span(int l) { return (8 + l - 1 + 7) / 8; }
+struct RefineBoxes {
+    int ns;
+    std::vector<double> A, B, C; // [d][i]: Σ g₊², Σ g₋², Σ g₊g₋ over the kernel rows [8d − i, 8d − i + 8) ∩ [0, l)
+    RefineBoxes(const std::vector<double> &gp, const std::vector<double> &gm, bool f32); // f32: the taps rounded to float first
+    double norm2(int dy, int i, int dx, int j) const;
+};
+std::vector<uint32_t> dog_refine_weights(const std::vector<double> &gp, const std::vector<double> &gm, double norm_up);
 // A frame table (include/pawsome_video.h) checked on the host, before anything is launched: every entry below n_frames,
 // negative entries only as the tail of a row.  out_len[c] = steps of clip c (its row's leading non-negative entries),
 // *max_len the longest.  PDOG_E_ARG in `who`'s name, outputs undefined, otherwise.

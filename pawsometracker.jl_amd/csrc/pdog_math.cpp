@@ -124,6 +124,58 @@ double dog_kernel_norm_up(const std::vector<double> &gp, const std::vector<doubl
     return (double)std::nextafter((float)n, 2.0f); // (the float nearest to n may lie below it; its successor does not)
 }
 
+// The weights of the pre-pass's second stage (dog_prune.hpp, "the cell bound").  With the tile cut into 8 × 8 cells, an output
+// at offset (i, j) inside its own cell takes from the input cell (dy, dx) cells further on the kernel rows
+// [8dy − i, 8dy − i + 8) ∩ [0, l) and the like columns.  K = g₊⊗g₊ − g₋⊗g₋, so the Σ K² of such a box is
+// A_r·A_c + B_r·B_c − 2·C_r·C_c with A, B, C the sums of g₊², g₋² and g₊g₋ over the row and the column range: prefix sums.
+RefineBoxes::RefineBoxes(const std::vector<double> &gp, const std::vector<double> &gm, bool f32) : ns(refine_span((int)gp.size()))
+{
+    const int l = (int)gp.size();
+    std::vector<double> pp(l + 1, 0.0), mm(l + 1, 0.0), pm(l + 1, 0.0);
+    for (int k = 0; k < l; ++k) {
+        const double a = f32 ? (double)(float)gp[k] : gp[k], b = f32 ? (double)(float)gm[k] : gm[k];
+        pp[k + 1] = pp[k] + a * a;
+        mm[k + 1] = mm[k] + b * b;
+        pm[k + 1] = pm[k] + a * b;
+    }
+    A.resize((size_t)ns * 8); B.resize((size_t)ns * 8); C.resize((size_t)ns * 8);
+    for (int d = 0; d < ns; ++d)
+        for (int i = 0; i < 8; ++i) {
+            const int lo = std::min(std::max(8 * d - i, 0), l), hi = std::min(std::max(8 * d - i + 8, 0), l);
+            A[d * 8 + i] = pp[hi] - pp[lo];
+            B[d * 8 + i] = mm[hi] - mm[lo];
+            C[d * 8 + i] = pm[hi] - pm[lo];
+        }
+}
+double RefineBoxes::norm2(int dy, int i, int dx, int j) const
+{
+    double ab = A[dy * 8 + i] * A[dx * 8 + j];
+    const double bb = B[dy * 8 + i] * B[dx * 8 + j], cc = C[dy * 8 + i] * C[dx * 8 + j];
+    ab = ab + bb;
+    return ab - 2.0 * cc;
+}
+// Wq[dy][dx] = ⌈2¹²·W/‖K‖₂⌉, W² the largest box sum over the 64 offsets and over the f32-rounded and the Float64 taps (as
+// dog_kernel_norm_up takes the larger norm), plus 1e-14·‖K‖₂² — a box sum is a difference of products near 1e-4 and may come
+// out 1e-20 low; the slack is 4e-4 of a weight's unit at most.  Every rounding errs upwards.  tests/prune_refine_restatement.py
+// restates this function operation for operation (no product here is fused with an addition: the reference arithmetic of
+// this file is compiled for a target without FMA).
+std::vector<uint32_t> dog_refine_weights(const std::vector<double> &gp, const std::vector<double> &gm, double norm_up)
+{
+    const RefineBoxes f32(gp, gm, true), f64(gp, gm, false);
+    const int ns = f32.ns;
+    std::vector<uint32_t> wq((size_t)ns * ns);
+    for (int dy = 0; dy < ns; ++dy)
+        for (int dx = 0; dx < ns; ++dx) {
+            double w2 = 0.0;
+            for (const RefineBoxes *t : {&f32, &f64})
+                for (int i = 0; i < 8; ++i)
+                    for (int j = 0; j < 8; ++j) w2 = std::max(w2, t->norm2(dy, i, dx, j));
+            w2 = w2 + 1e-14 * (norm_up * norm_up);
+            wq[(size_t)dy * ns + dx] = (uint32_t)std::ceil(4096.0 * (std::sqrt(w2) / norm_up));
+        }
+    return wq;
+}
+
 // One window's padded tile, (n1+l-1) rows of `pitch` bytes: the frame rectangle the functor reads, with the
 // PaddedView fill (:48) materialised wherever the rectangle leaves the frame.  Tile row a, column b is the
 // padded frame at 1-based (g1 - r1 - l÷2 + a, g2 - r2 - l÷2 + b).
