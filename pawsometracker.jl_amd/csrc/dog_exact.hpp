@@ -134,19 +134,8 @@ __device__ __forceinline__ void peak64_wave_reduce(Peak64 &p)
 //      (exact_pixel: dense l×l, sequential, kernel column-major order); a single survivor needs no evaluation at all.
 // More candidates than the list holds (plateaus: every response exactly equal) → stage 2 is skipped and every
 // candidate goes through stage 3 as it is found (right, only slow).
-constexpr int REFINE_CAP = 512;    // candidate list entries
-constexpr int REFINE_BLKCAP = 256; // column blocks listed for the rescan (more ⇒ every block is rescanned)
-__host__ __device__ constexpr int refine_tile_pitch(int ncol, int L) { return (ncol + L - 1 + 3) / 4 * 4; }
-// dynamic LDS of a refinement: fixed part (table p/255.0, candidate list, reductions), row-pass block (f2 for stage 1,
-// reused as 2 doubles per element for stage 2), optional pixel tile
-__host__ __device__ constexpr size_t refine_fixed_bytes() { return 256 * 8 + REFINE_CAP * 12 + 16 * 8 + 16 * 4 + 32 + REFINE_BLKCAP * 4 + 32; }
-__host__ __device__ constexpr size_t refine_r_bytes(int n1, int L, int cbw) { return (size_t)(n1 + L - 1) * cbw * 16; }
-__host__ __device__ constexpr size_t refine_tile_bytes(int rows, int L, int cbw) { return ((size_t)rows * refine_tile_pitch(cbw, L) + 15) / 16 * 16; }
-// tile_rows: rows of the block's pixel tile resident at a time (n1 + l − 1 = all of them)
-__host__ __device__ constexpr size_t refine_lds_bytes(int n1, int L, int cbw, int tile_rows)
-{
-    return refine_fixed_bytes() + refine_r_bytes(n1, L, cbw) + refine_tile_bytes(tile_rows, L, cbw);
-}
+// (REFINE_CAP, REFINE_BLKCAP, refine_tile_pitch and the refinement's dynamic LDS, refine_fixed_bytes … refine_lds_bytes, are
+// dog_layout.hpp's.)
 
 // bits [a, b) of a 64-column strip's lane mask (clipped to the strip)
 __device__ __forceinline__ unsigned long long column_bits(int a, int b)

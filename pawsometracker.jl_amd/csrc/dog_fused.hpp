@@ -44,14 +44,7 @@ struct FusedPredictGeo : FusedTableGeo { PredictCtl pred; }; // … walked as pr
 template <bool TABLE, bool PRED>
 using fused_geo_t = std::conditional_t<PRED, FusedPredictGeo, std::conditional_t<TABLE, FusedTableGeo, FusedGeo>>;
 
-constexpr int FUSED_NT = 1024, FUSED_PMAX = 8, FUSED_U = 8;
-
-// LDS pitches (odd ⇒ conflict-free strided reads) with room for the sliding windows of the last, partly masked
-// output group of up to FUSED_PMAX outputs and their one-block prefetch
-__host__ __device__ constexpr int fused_pitch_a(int n2, int L) { return ((n2 + FUSED_PMAX - 1) / FUSED_PMAX * FUSED_PMAX + L + FUSED_U + 1) | 1; }
-__host__ __device__ constexpr int fused_pitch_v(int n1, int L) { return ((n1 + FUSED_PMAX - 1) / FUSED_PMAX * FUSED_PMAX + L + 24 + 1) | 1; } // + 24: the compile-time-l column pass reads whole 16-tap blocks
-__host__ __device__ constexpr size_t fused_a_bytes(int n1, int n2, int L) { return ((size_t)(n1 + L - 1) * fused_pitch_a(n2, L) * 4 + 15) / 16 * 16; }
-__host__ __device__ constexpr size_t fused_lds_bytes(int n1, int n2, int L) { return fused_a_bytes(n1, n2, L) + (size_t)n2 * fused_pitch_v(n1, L) * 8; }
+// (FUSED_NT, FUSED_PMAX, FUSED_U and the LDS pitches and byte counts fused_pitch_a … fused_lds_bytes are dog_layout.hpp's.)
 
 // PR outputs of one tile row: out[o] = Σ_k (g₊[k], g₋[k]) · in[o+k], symmetric pairs first (k ascending), centre last.
 // (The register-ring windows that removed the shifts from the two-pass kernels were measured here too: SLOWER — 10.8 →
@@ -144,17 +137,7 @@ __device__ __forceinline__ void fused_col_task(const f2 *a, int L, tap_ptr taps,
 // The tile then lives in the roll kernel's layout: rows on a pitch of whole bank rows, skewed by {0, 1, 8, 9} 16-byte slots
 // by (row & 3), so that the b128 reads of a lane group (rows r, r+1 × 8 output groups) are conflict free.  Same operation
 // order per output as the runtime-length tasks above: the two kernels' responses are bit-identical.
-__host__ __device__ constexpr bool fused_has_instance(int L) { return L % 4 == 1 && L >= 29 && L <= 101; } // lat_lengths.def
-__host__ __device__ constexpr int fusedc_pitch_a(int n2, int L) { return (8 * ((n2 + 7) / 8) + L + 39 + 63) / 64 * 64; }
-__host__ __device__ constexpr size_t fusedc_a_bytes(int n1, int n2, int L) { return ((size_t)(n1 + L - 1) * fusedc_pitch_a(n2, L) + 64) * 4; }
-__host__ __device__ constexpr size_t fusedc_lds_bytes(int n1, int n2, int L) { return fusedc_a_bytes(n1, n2, L) + (size_t)n2 * fused_pitch_v(n1, L) * 8; }
-// outputs per row-pass task of the compile-time-l instances: 8, or 4 where that loads the busiest SIMD less (waves of 64 tasks,
-// four SIMDs; ≈51 / ≈53 instructions per output)
-__host__ __device__ constexpr int fusedc_row_outputs(int NA, int n2)
-{
-    const int w8 = (NA * ((n2 + 7) / 8) + 63) / 64, w4 = (NA * ((n2 + 3) / 4) + 63) / 64;
-    return ((w4 + 3) / 4) * 212 < ((w8 + 3) / 4) * 408 ? 4 : 8;
-}
+// (fused_has_instance, the layout's sizes fusedc_pitch_a … fusedc_lds_bytes and fusedc_row_outputs are dog_layout.hpp's.)
 __device__ __forceinline__ int fusedc_row_base(int r, int pitch) { return r * pitch + 4 * ((r & 1) + ((r & 2) ? 8 : 0)); }
 
 // P outputs of one window column, l known: taps in blocks of 8 (one s_load_dwordx16 each, requested a block ahead), the window

@@ -25,10 +25,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pdog_mailbox.hpp"
+#include "dog_layout.hpp" // round_up, pitch_a, pitch_r, ring_rows — and every other kernel header's size formulas: host-testable
 
 namespace pdog {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
+static_assert(sizeof(f2) == 8, "dog_layout.hpp counts an f2 element as 8 bytes");
 // Filter taps are read through the CONSTANT address space: a load from it with a
 // uniform address is always selected as a scalar load (s_load → SGPR operand).
 typedef const f2 __attribute__((address_space(4))) *tap_ptr;
@@ -249,20 +251,7 @@ __device__ __forceinline__ Peak fold_column_peak(const f2 *Rc, int n1, int L, ta
     return tp;
 }
 
-__host__ __device__ constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
-// LDS row pitches.  A (f32 input tile) is read by lanes that sit in consecutive
-// rows (ds_read_b32, 32 banks): an odd pitch spreads them over all banks.
-__host__ __device__ constexpr int pitch_a(int cols) { return cols | 1; }
-// R ring (f2 per element) is written row-per-lane (ds_write_b64) and read
-// column-per-lane (ds_read_b64, conflict free for any pitch); pitch in f2 units
-// with 2*pitch ≡ 2 (mod 32) would be ideal for the writes; odd is a good compromise.
-__host__ __device__ constexpr int pitch_r(int tw) { return tw | 1; }
-__host__ __device__ constexpr int ring_rows(int CH, int L, int Q)
-{
-    // rows a col-pass span can touch: CH new + L-1 halo + (Q-1) slack when the
-    // chunk cadence leaves a partial Q-group behind; multiple of 4 for the wrap logic
-    return round_up(CH + L - 1 + (((CH % Q) == 0 && ((L - 1) % Q) == 0) ? 0 : Q - 1), 4);
-}
+// (round_up, the LDS row pitches pitch_a and pitch_r, and ring_rows are dog_layout.hpp's.)
 
 // The fixed 32×32 sample grid over the window's padded tile that decides the DC level (see dog_window_kernel):
 // thread `tid` of `nthreads` adds up its share; callers reduce and finish with dc_from_sum.

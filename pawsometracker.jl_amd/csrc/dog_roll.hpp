@@ -63,10 +63,8 @@ namespace pdog {
 #ifndef PDOG_ROLL_LMAX
 #define PDOG_ROLL_LMAX 149
 #endif
-constexpr int ROLL_P = 8;    // row-pass outputs per lane
-constexpr int ROLL_TW = 64;  // strip width = lanes
-constexpr int ROLL_PR = 65;  // R pitch (f2)
-constexpr int ROLL_LMIN = 17, ROLL_LMAX = PDOG_ROLL_LMAX; // kernel lengths with a roll instance (l = 4m+1): the (l + 7 rounded up to 8)
+// (ROLL_P, ROLL_TW, ROLL_PR and ROLL_LMIN are dog_layout.hpp's.)
+constexpr int ROLL_LMAX = PDOG_ROLL_LMAX;     // kernel lengths with a roll instance (l = 4m+1): the (l + 7 rounded up to 8)
                                               // accumulator slots, the row-pass windows and the loop state fit 168 VGPRs up to l = 81 (three waves
                                               // per SIMD) and 256 from there to l = 149 (two; roll_lengths.def builds every length, none spills:
                                               // profiles/pad_skip_kernel_regs.txt); longer kernels go to dog_twopass.hpp
@@ -79,14 +77,8 @@ __host__ __device__ constexpr bool roll_folds(int L) { return L == 65; }
 // accumulator slots: the l outputs in flight plus the sub-chunk being emitted, rounded so that the
 // slot ↔ tap mapping repeats after a whole number of sub-chunks
 __host__ __device__ constexpr int roll_slots(int L) { return (L - 1 + ROLL_CH + ROLL_CH - 1) / ROLL_CH * ROLL_CH; }
-// staging: 8 lanes per input row, each SB (multiple of 4) bytes.  A rows are 16-byte aligned and their bases are
-// skewed by {0,1,8,9} 16-byte slots (row & 3) on a pitch that is a multiple of 256 B: the row pass reads ds_read_b128
-// quads at (row base + 8·group + 4·q) floats, and with that skew the 16 lanes of every b128 lane group
-// (MI355X_MICROARCH.md, LDS) land on 16 distinct slots of the 256-B bank row — conflict-free.
-__host__ __device__ constexpr int roll_sb(int L) { return ((ROLL_TW + L - 1 + 7) / 8 + 3) / 4 * 4; }
-__host__ __device__ constexpr int roll_rs(int L) { return (8 * roll_sb(L) + 40 + 63) / 64 * 64; } // A row pitch in floats (36 of skew + the 129th column of a folded strip)
+// (staging: roll_sb, roll_rs and roll_lds_bytes are dog_layout.hpp's; a row's base carries the skew described there.)
 __host__ __device__ constexpr int roll_row_base(int r, int L) { return r * roll_rs(L) + 4 * (((r & 1) ? 1 : 0) + ((r & 2) ? 8 : 0)); }
-__host__ __device__ constexpr size_t roll_lds_bytes(int L) { return (size_t)ROLL_CH * roll_rs(L) * 4 + (size_t)ROLL_CH * ROLL_PR * 8; }
 
 // (KEPT RANGES: prune_span, prune_tail and prune_sc_hi are dog_roll_range.hpp's.)
 
@@ -994,8 +986,8 @@ static __global__ void dog_chain_table_init_kernel(const int *__restrict__ start
 
 #endif // PDOG_ROLL_INST_ONLY
 
-// dynamic LDS of dog_thin_kernel: the R column (f2 per input row) and the column's input patch as bytes
-__host__ __device__ constexpr size_t thin_lds_bytes(int n1, int L) { return ((size_t)(n1 + L - 1) * sizeof(f2) + 15) / 16 * 16 + (size_t)(n1 + L - 1) * ((L + 3) / 4 * 4); }
+// (dynamic LDS of dog_thin_kernel: thin_lds_bytes, dog_layout.hpp)
+static_assert(sizeof(f2) == 8, "thin_lds_bytes counts the R column's f2 elements as 8 bytes");
 
 // ---- thin remainder ----
 // A window whose width is 64·k + r with small r (257 = 4·64 + 1) would need a whole extra strip for

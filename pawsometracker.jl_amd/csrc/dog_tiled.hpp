@@ -50,7 +50,7 @@ struct TiledGeo {
 };
 struct TiledTableGeo : TiledGeo { ClipTable tab; }; // clips over a frame table (dog_roll.hpp): n clips of up to chain_len steps
 
-constexpr int TILED_SLOT_CAP = 256; // sub-windows per window the combining wave handles (4 per lane)
+// (TILED_SLOT_CAP, the sub-windows per window the combining wave handles, is dog_layout.hpp's.)
 
 // LT > 0: the compile-time-l tasks and tile layout of dog_fused.hpp (fusedc_*), same values bit for bit.
 // TABLE: the instances that walk a frame table — a template flag and a kernel argument of their own, for the reason given in dog_fused.hpp.

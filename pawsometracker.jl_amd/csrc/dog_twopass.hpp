@@ -53,8 +53,7 @@ struct TwoPassGeo {
 // Every output still sees the same operations in the same order: equal inputs give bit-equal outputs, flat windows tie exactly.
 // FLUSH instances serve kernel lengths from TWOPASS_FLUSH_L on (the plain instances keep 70–96 VGPRs instead of 118–150 and serve the
 // short kernels' small batches, where the plain chains' bound already flags next to nothing).
-constexpr int TWOPASS_FLUSH_L = 101;
-__host__ __device__ constexpr int twopass_ring(int P, int U) { return ((P + 2 * U - 1 + U - 1) / U) * U; } // register-ring slots = taps per trip
+// (TWOPASS_FLUSH_L = 101 and twopass_ring, the register-ring slots = taps per trip, are dog_layout.hpp's.)
 
 static __global__ __launch_bounds__(64) void dog_dc_kernel(const LaunchGeo g, int *__restrict__ dc, int *__restrict__ vmax)
 {
@@ -71,7 +70,7 @@ static __global__ __launch_bounds__(64) void dog_dc_kernel(const LaunchGeo g, in
 }
 
 // ---- row pass (u8 rows → RT) ----
-constexpr int HP_ROWS = 16; // rows per workgroup in both passes
+// (HP_ROWS = 16, the rows per workgroup in both passes, is dog_layout.hpp's.)
 // DCIN: the workgroup derives the window's DC level itself (the same 1024 integer samples, 4 per thread) instead of
 // reading the result of dog_dc_kernel: one launch less where launches are what a small batch costs.
 // One row-pass workgroup's work: tile rows 16·rb … of the window whose RT block is `b_local`, read from `frame` around

@@ -8,6 +8,7 @@
 #include "pdog_host.hpp"
 #include "pdog_mailbox.hpp"
 #include "pdog_policy.hpp"
+#include "pdog_plan.hpp"
 #include "dog_kernels.hpp"
 #include "dog_roll.hpp"
 #include "dog_prune.hpp"
@@ -69,45 +70,7 @@ PDOG_EPI_CLASSES(PDOG_EPI_DECL)
 
 namespace {
 
-// Run-time configuration.  The PRODUCT build reads four RESOURCE limits from the environment, once, when a tracker is
-// created (never on the launch path: a functor call's whole budget is ≈23 µs).  Everything that selects a code path is
-// either API (pdog_set_exact, pdog_set_variant, pdog_set_tuning — explicit, per tracker) or exists only in the diagnostic
-// build (make diag, -DPDOG_ABLATIONS), which also reads the tuning switches from the environment for tools/.
-struct Switches {
-    // resource limits (environment, product build)
-    size_t scratch_cap = (size_t)6 << 30; // PDOG_SCRATCH_MB: HBM scratch of the two-pass intermediate; larger batches go in chunks
-    size_t map_cap = (size_t)4 << 30;     // PDOG_MAP_MB: largest FP32 response map the two-pass path keeps for exact mode (beyond: candidates are recomputed)
-    int host_threads = 0;                 // PDOG_HOST_THREADS (0: min(16, cores))
-    int ingest_chunk = 0;                 // PDOG_INGEST_CHUNK (0: ≈32 MB of tiles)
-    // path selection (pdog_set_tuning; the tests exercise every alternative path of the product through it)
-    bool host_copy = false;               // functor: upload the tile with copy commands and synchronise the stream instead of the in-place tile + ticket
-    bool host_sync = false;               // functor: in-place tile, but wait with hipStreamSynchronize instead of polling the ticket
-    bool twopass_4l = false;              // two-pass path always in its four-launch form
-    bool no_tiled = false;                // single large windows stay on the two-pass launches
-    bool no_roll_map = false;             // hard batches on the roll / ring kernels keep recomputing their candidates
-    bool no_fold = false;                 // a single remainder column always goes to dog_thin_kernel
-    bool fold_always = false;             // … always into the last strip, also below 8 strips per window
-    bool no_pad_skip = false;             // roll kernels: sub-chunks that hold padding only run the full path (dog_roll.hpp, "padding rows")
-    bool no_prune = false;                // roll batches stay dense: no pre-pass, no kept ranges (dog_prune.hpp)
-    bool no_refine = false;               // pruned roll batches: the first-stage hulls as they are, no bound per output cell (dog_prune.hpp, "the cell bound")
-    bool no_range_end = false;            // pruned roll batches: full-length column-pass bodies to the end of a kept range (dog_roll_range.hpp)
-    bool fenced_publish = false;          // pre-pass: per-workgroup counts and an acquire-release arrival also where the packed word fits (dog_prune.hpp, the publish block)
-    bool no_fused_c = false;              // the fused kernel's runtime-length instance also where a compile-time-l instance exists
-    bool measure_global = false;          // pdog_measure reads the frame itself instead of staging each position's pixel tile in LDS
-    bool fault_inject = false;            // tests: one sub-window of a tiled chain never delivers its second frame's partial (the device-side waits must give up)
-    // tuning and diagnosis (diagnostic build only)
-    bool host_trace = false, hpass16 = false, ingest_no_nt = false, ingest_trace = false, fused_diag = false;
-    bool tiled_force = false;             // the tiled kernel also for windows the fused kernel serves
-    bool no_host_dc = false;              // the functor's kernels sample the DC level themselves
-    int tiled_sub = 0;                    // sub-window edge of the tiled kernel (0: chosen per geometry)
-    int tp_ph1 = 0, tp_php = 0;           // outputs per task of the two-pass kernels (0: per geometry)
-    int v_after = 64;                     // exact mode, map path: first-scan candidates beyond which the window's own |pixel − dc| bound is computed
-    int h1_u = 4;                         // taps per block of the two-pass row pass (4, or 8)
-    int hp_u = 8;                         // taps per block of the two-pass column pass (8 or 16)
-    int tiled_batch = 2;                  // windows per batch up to which the tiled kernel is used
-    int fused_pr = 0, fused_pc = 0;       // outputs per task of the fused kernel (0: chosen per geometry)
-    int lds_pad = 0;                      // occupancy experiments
-};
+// (struct Switches: pdog_plan.hpp.)  Read once, when a tracker is created, never on the launch path.
 Switches read_switches()
 {
     Switches w;
@@ -172,75 +135,98 @@ int raise_lds_limit(const void *fn, size_t bytes)
     return PDOG_OK;
 }
 
-// ---- compiled kernel specialisations ----
-// path ids that pdog_kernel_for_batch reports beside the variant ids: the fused, two-pass and tiled kernel families
-constexpr int kPathFused = 300, kPathTwoPass = 200, kPathTiled = 400;
+// ---- compiled kernel specialisations: the kernels of kVariantShapes' rows (pdog_plan.hpp), row for row ----
 typedef void (*kernel_fn)(const LaunchGeo, const f2 *, const f2 *);
-struct Variant {
-    int id, P, XG, Q, CH, LT, NT;
-    kernel_fn fn, fn_resp; // fn_resp also writes the dense response (parity checks)
-    bool roll;             // dog_roll.hpp (one wave per 64-column strip) instead of dog_kernels.hpp
-    kernel_fn thin, thin_resp; // remainder-column kernel of the roll variants (may be null)
-    int twopass = 0;           // dog_twopass.hpp: vertical pass → HBM → horizontal pass (Q = this value)
-    typedef void (*chain_fn)(const ChainGeo, const f2 *, const f2 *);
-    chain_fn chain = nullptr;  // persistent serial-chain kernel of the roll variants
-    typedef void (*chain_table_fn)(const ChainTableGeo, const f2 *, const f2 *);
-    chain_table_fn chain_table = nullptr; // … its instance that walks a frame table
-    bool fused = false;        // dog_fused.hpp: one workgroup per window, whole tile in LDS
-    kernel_fn fn_prune = nullptr; // the roll instance that honours kept ranges (dog_prune.hpp)
-    typedef void (*chain_predict_fn)(const ChainPredictGeo, const f2 *, const f2 *);
+typedef void (*chain_fn)(const ChainGeo, const f2 *, const f2 *);
+typedef void (*chain_table_fn)(const ChainTableGeo, const f2 *, const f2 *);
+typedef void (*chain_predict_fn)(const ChainPredictGeo, const f2 *, const f2 *);
+struct VariantKernels {
+    int id = -1;                              // the row of kVariantShapes these kernels are the instances of
+    kernel_fn fn = nullptr, fn_resp = nullptr; // the batch kernel; fn_resp also writes the dense response (parity checks).  Null: two-pass and fused rows, whose kernels are picked per launch
+    kernel_fn thin = nullptr, thin_resp = nullptr; // remainder-column kernel of the roll variants (may be null)
+    chain_fn chain = nullptr;                 // persistent serial-chain kernel of the roll variants
+    chain_table_fn chain_table = nullptr;     // … its instance that walks a frame table
+    kernel_fn fn_prune = nullptr;             // the roll instance that honours kept ranges (dog_prune.hpp)
     chain_predict_fn chain_predict = nullptr; // the chain kernel's instance that walks a table as predicted chains
-    int tw() const { return P * XG; }
-    int ring(int L) const { return LT ? ring_rows(CH, LT, Q) : ring_rows(CH, L, Q); }
-    int pa(int L) const { return pitch_a(tw() + L - 1); }
-    size_t lds(int L) const
-    {
-        if (twopass || fused) return 0; // sized per window at launch
-        if (roll) return roll_lds_bytes(LT);
-        return (size_t)round_up(CH * pa(L) * 4, 16) + (size_t)ring(L) * pitch_r(tw()) * sizeof(f2);
-    }
 };
-#define PDOG_VARIANT(id, P, XG, Q, CH, LT, NT) \
-    Variant { id, P, XG, Q, CH, LT, NT, (kernel_fn)dog_window_kernel<P, XG, Q, CH, LT, NT, false>, \
-              (kernel_fn)dog_window_kernel<P, XG, Q, CH, LT, NT, true>, false, nullptr, nullptr }
-#define PDOG_ROLL_VARIANT(id, LT) \
-    Variant { id, ROLL_P, ROLL_TW / ROLL_P, ROLL_CH, ROLL_CH, LT, 64, (kernel_fn)dog_roll_kernel<LT, false>, \
-              (kernel_fn)dog_roll_kernel<LT, true>, true, (kernel_fn)dog_thin_kernel<LT, false>, \
-              (kernel_fn)dog_thin_kernel<LT, true>, 0, dog_chain_kernel<LT>, dog_chain_kernel<LT, true>, false, \
-              (kernel_fn)dog_roll_kernel<LT, false, 0, -1, true>, dog_chain_kernel<LT, true, true> }
+// the instance's template arguments are the row's numbers
+constexpr bool shape_is(int id, Family family, int P, int XG, int Q, int CH, int LT, int NT, bool full_set)
+{
+    const VariantShape *s = find_variant(id);
+    return s && s->family == family && s->P == P && s->XG == XG && s->Q == Q && s->CH == CH && s->LT == LT && s->NT == NT && s->full_set == full_set;
+}
+template <int ID, int P, int XG, int Q, int CH, int LT, int NT>
+VariantKernels ring_kernels()
+{
+    static_assert(shape_is(ID, Family::Ring, P, XG, Q, CH, LT, NT, false), "kVariantShapes describes another instance under this id");
+    VariantKernels k;
+    k.id = ID;
+    k.fn = (kernel_fn)dog_window_kernel<P, XG, Q, CH, LT, NT, false>;
+    k.fn_resp = (kernel_fn)dog_window_kernel<P, XG, Q, CH, LT, NT, true>;
+    return k;
+}
+template <int LT>
+VariantKernels roll_kernels()
+{
+    constexpr int ID = LT == 65 ? 100 : 100 + LT;
+    static_assert(shape_is(ID, Family::Roll, ROLL_P, ROLL_TW / ROLL_P, ROLL_CH, ROLL_CH, LT, 64, true), "kVariantShapes describes another instance under this id");
+    VariantKernels k;
+    k.id = ID;
+    k.fn = (kernel_fn)dog_roll_kernel<LT, false>;
+    k.fn_resp = (kernel_fn)dog_roll_kernel<LT, true>;
+    k.thin = (kernel_fn)dog_thin_kernel<LT, false>;
+    k.thin_resp = (kernel_fn)dog_thin_kernel<LT, true>;
+    k.chain = dog_chain_kernel<LT>;
+    k.chain_table = dog_chain_kernel<LT, true>;
+    k.fn_prune = (kernel_fn)dog_roll_kernel<LT, false, 0, -1, true>;
+    k.chain_predict = dog_chain_kernel<LT, true, true>;
+    return k;
+}
+// a row whose kernels are picked per launch (two-pass, fused), or an ablation's strip kernels alone
+VariantKernels bare_kernels(int id, kernel_fn fn = nullptr, kernel_fn fn_resp = nullptr)
+{
+    VariantKernels k;
+    k.id = id;
+    k.fn = fn;
+    k.fn_resp = fn_resp;
+    return k;
+}
 
-const Variant kVariants[] = {
+const VariantKernels kVariants[] = {
     // runtime-L (any target_width)
-    PDOG_VARIANT(0, 4, 8, 8, 32, 0, 256),
-    PDOG_VARIANT(1, 8, 8, 8, 32, 0, 256),
-    PDOG_VARIANT(2, 11, 8, 8, 32, 0, 256),
+    ring_kernels<0, 4, 8, 8, 32, 0, 256>(),
+    ring_kernels<1, 8, 8, 8, 32, 0, 256>(),
+    ring_kernels<2, 11, 8, 8, 32, 0, 256>(),
     // l = 65 (target_width 25, the reference default)
-    PDOG_VARIANT(10, 11, 8, 16, 32, 65, 256),
-    PDOG_VARIANT(11, 11, 8, 8, 24, 65, 256),
-    PDOG_VARIANT(12, 8, 8, 16, 32, 65, 256),
-    PDOG_VARIANT(13, 8, 8, 8, 32, 65, 256),
-    PDOG_VARIANT(14, 11, 8, 8, 32, 65, 256),
-    // rolling-accumulator kernel: one instance per kernel length l = 4m+1 of roll_lengths.def (target_width ≈ 5 … 39); id = 100 + l, l = 65 → 100
-#define PDOG_ROLL_L(LT) PDOG_ROLL_VARIANT((LT) == 65 ? 100 : 100 + (LT), LT),
+    ring_kernels<10, 11, 8, 16, 32, 65, 256>(),
+    ring_kernels<11, 11, 8, 8, 24, 65, 256>(),
+    ring_kernels<12, 8, 8, 16, 32, 65, 256>(),
+    ring_kernels<13, 8, 8, 8, 32, 65, 256>(),
+    ring_kernels<14, 11, 8, 8, 32, 65, 256>(),
+    // rolling-accumulator kernel: one instance per kernel length of roll_lengths.def
+#define PDOG_ROLL_L(LT) roll_kernels<LT>(),
 #include "roll_lengths.def"
 #undef PDOG_ROLL_L
-    // any l: two launches with the intermediate in HBM (long kernels, target_width ≳ 40)
-    Variant { kPathTwoPass, 13, 16, 16, 16, 0, 256, nullptr, nullptr, false, nullptr, nullptr, 16 },
-    // any l, windows whose padded tile fits in LDS: one workgroup per window, one launch (latency path)
-    Variant { kPathFused, 1, 1, 1, 1, 0, FUSED_NT, nullptr, nullptr, false, nullptr, nullptr, 0, nullptr, nullptr, true },
+    bare_kernels(kPathTwoPass), // h1_kernel_for, hpass8_kernel_for
+    bare_kernels(kPathFused),   // kLatInstances
 #ifdef PDOG_ABLATIONS
-    Variant { 101, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 1>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
-    Variant { 102, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 2>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
-    Variant { 103, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 3>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
-    Variant { 104, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 12>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
-    Variant { 105, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 15>, (kernel_fn)dog_roll_kernel<65, true>, true, nullptr, nullptr },
-    Variant { 106, ROLL_P, 8, ROLL_CH, ROLL_CH, 65, 64, (kernel_fn)dog_roll_kernel<65, false, 0>, (kernel_fn)dog_roll_kernel<65, false, 16>, true, nullptr, nullptr },
+    bare_kernels(101, (kernel_fn)dog_roll_kernel<65, false, 1>, (kernel_fn)dog_roll_kernel<65, true>),
+    bare_kernels(102, (kernel_fn)dog_roll_kernel<65, false, 2>, (kernel_fn)dog_roll_kernel<65, true>),
+    bare_kernels(103, (kernel_fn)dog_roll_kernel<65, false, 3>, (kernel_fn)dog_roll_kernel<65, true>),
+    bare_kernels(104, (kernel_fn)dog_roll_kernel<65, false, 12>, (kernel_fn)dog_roll_kernel<65, true>),
+    bare_kernels(105, (kernel_fn)dog_roll_kernel<65, false, 15>, (kernel_fn)dog_roll_kernel<65, true>),
+    bare_kernels(106, (kernel_fn)dog_roll_kernel<65, false, 0>, (kernel_fn)dog_roll_kernel<65, false, 16>),
 #endif
     // l = 29 (target_width 10, the reference test default)
-    PDOG_VARIANT(20, 8, 8, 4, 32, 29, 256),
+    ring_kernels<20, 8, 8, 4, 32, 29, 256>(),
 };
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-constexpr size_t kMaxLds = 160 * 1024;
+static_assert(sizeof(kVariants) / sizeof(kVariants[0]) == kNumVariants, "a row of kernels per row of kVariantShapes");
+// (looked up once per plan, by apply_plan; the rows stand in the same order, and each names its shape)
+const VariantKernels *kernels_of(const VariantShape &s)
+{
+    const VariantKernels &k = kVariants[&s - kVariantShapes];
+    return k.id == s.id ? &k : nullptr;
+}
 // The fused kernel's interior staging path keeps 32-bit byte offsets from the tile's first pixel (dog_fused.hpp, rs32): at most
 // (NA - 1) * row_stride + 4 * FUSED_NT.  A fused instance only runs where its tile of NA rows fits LDS (fused_lds_bytes >=
 // fused_a_bytes = NA * pitch * 4, the pitch smallest for a one-column window under the shortest kernel, l = 5), which bounds NA;
@@ -248,42 +234,8 @@ constexpr size_t kMaxLds = 160 * 1024;
 constexpr long long kFusedMaxRows = (long long)(kMaxLds / (4 * (size_t)fused_pitch_a(1, 5)));
 static_assert(fused_a_bytes(1, 1, 5) >= 5 * fused_pitch_a(1, 5) * 4 && fused_pitch_a(1, 5) <= fusedc_pitch_a(1, 5), "the tile's LDS bytes are at least rows * pitch * 4");
 static_assert(kFusedMaxRows * (long long)PDOG_MAX_ROW_STRIDE + 4 * FUSED_NT < (1LL << 32), "PDOG_MAX_ROW_STRIDE: the fused kernel's 32-bit offsets would wrap");
-constexpr int kThinMax = 6; // remainder columns done by dog_thin_kernel instead of one more strip
 
-bool has_roll_instance(int L)
-{
-    for (int i = 0; i < kNumVariants; ++i)
-        if (kVariants[i].roll && kVariants[i].LT == L && kVariants[i].id >= 100 && kVariants[i].id < 300) return true;
-    return false;
-}
-
-const Variant *find_variant(int id)
-{
-    for (int i = 0; i < kNumVariants; ++i)
-        if (kVariants[i].id == id) return &kVariants[i];
-    return nullptr;
-}
-
-// ---- what make_plan derives per kernel family, and what a family keeps between launches ----
-// what the fused and tiled kernels share: the instance and, for the tile one workgroup works on, pitches and task sizes (plan_tile)
-struct TilePlan {
-    bool c = false; // the compile-time-l instance (lat_lengths.def) and its wider tile layout
-    int pitchA = 0, pitchV = 0, pr = 0, pc = 0, cshift = 0;
-};
-// fused kernel (dog_fused.hpp): one workgroup per window, the whole tile in LDS
-struct FusedPlan : TilePlan {
-    bool ok = false;               // the window's tile fits in LDS: the fused kernel takes small batches and short chains
-    int resident = 0;              // workgroups the device keeps resident (the grid is capped there: a workgroup walks several windows); 0: launch_fused asks
-    size_t lds = 0;                // dynamic LDS: the tile + RT, or the scratch of the refinement it may run in the same memory
-    int ref_cbw = 1, ref_rows = 8; // refinement geometry inside the kernel (its scratch is the kernel's own LDS)
-};
-// tiled kernel (dog_tiled.hpp): one large window cut into sub-windows, a workgroup each, one launch per batch / clip
-struct TiledPlan : TilePlan {
-    bool ok = false;
-    int sn1 = 0, sn2 = 0, ns1 = 0, ns2 = 0;
-    int ref_cbw = 1, ref_rows = 8, resident = 0; // refinement scratch geometry; workgroups the device keeps resident
-    size_t lds = 0;
-};
+// ---- what a kernel family keeps between launches (what make_plan derives per family: FusedPlan, TiledPlan, pdog_plan.hpp) ----
 struct TiledRun {
     DeviceBuffer<int> d_ctl; // [cap][4]: current guess (2), partial arrivals, frame flag; then the abort word
     int ctl_cap() const { return (int)(d_ctl.capacity() / 4); }
@@ -309,17 +261,14 @@ struct pdog_tracker {
     hipEvent_t ev_switch = nullptr; // orders a new stream behind the work queued on the previous one (pdog_set_stream)
     int fh = 0, fw = 0, r1 = 0, r2 = 0, n1 = 0, n2 = 0, L = 0, fill = 0, darker = 0;
     double tw = 0, sigma = 0;
-    const Variant *var = nullptr;
-    int nstrips = 0;
-    int nthin = 0, thin_x0 = 0; // window columns handled by the thin-remainder kernel
-    bool forced_variant = false;   // pdog_set_variant pinned the kernel: no batch-size switching
-    bool small_twopass = false;    // two-pass kernels are set up and may take over small batches
-    FusedPlan fused;
-    int hp_rows = HP_ROWS;         // RT rows (window columns) per column-pass workgroup: 16 (P = 13) or 8 (P = 7)
+    // Everything derived from the geometry, the switches and the pinned variant (pdog_plan.hpp); apply_plan alone assigns it,
+    // with the kernels of plan.shape and what the device answered for the plan: the workgroups it keeps resident of the fused
+    // kernel (the grid is capped there: a workgroup walks several windows; 0: launch_fused asks) and of the tiled kernel
+    Plan plan;
+    const VariantKernels *kern = nullptr;
+    int fused_resident = 0, tiled_resident = 0;
     DeviceBuffer<int32_t> d_chain_tmp; // [2][n_clips][2]: current guesses / step results of multi-clip chains
     pdog::StagedTable table;       // chains over a frame table (pdog_detect_chains_indexed): the validated table as the path that runs wants it
-    int tp_ph1 = 13, tp_php = 7;   // outputs per task of the two-pass row / column pass (pick_twopass_p)
-    TiledPlan tiled;
     TiledRun tiled_run;
     // two-pass path scratch
     DeviceBuffer<f2> d_V;
@@ -347,12 +296,10 @@ struct pdog_tracker {
     DeviceBuffer<f2> d_taps_row, d_taps_col;
     DeviceBuffer<f2> d_taps_roll; // paired column-tap table of dog_roll.hpp
     DeviceBuffer<f2> d_fold_r;    // [n][n1 + l − 1] row-pass outputs of a folded remainder column (LaunchGeo::fold_r)
-    // the kernels' partials, [n][part_slots] each (ensure_capacity): part_slots is the most slots per window any variant or
-    // the tiled kernel writes, so that a later pdog_set_variant never reallocates
+    // the kernels' partials, [n][plan.part_slots] each (ensure_capacity)
     DeviceBuffer<float> d_part_val, d_part_sec;
     DeviceBuffer<unsigned long long> d_part_mask;
     DeviceBuffer<int> d_part_idx;
-    int part_slots = 1;
     // exact mode (dog_exact.hpp): windows whose two best FP32 responses lie within 2δ are re-decided in the
     // reference's own Float64 arithmetic
     bool exact = true;
@@ -364,7 +311,6 @@ struct pdog_tracker {
     DeviceBuffer<RefineParams> d_rp;  // {K64, g64, dir, T64} for the kernels that refine inline
     double exact_T64 = 0.0;           // 2δ64: separable Float64 against the reference's dense Float64
     DeviceBuffer<unsigned long long> d_ref_stat;
-    int ref_cbw = 1, ref_rows = 8;    // refinement: window columns per block; rows of the block's pixel tile resident in LDS at a time
     // host-path staging (pdog_detect_host / chain seed)
     DeviceBuffer<uint8_t> d_frame;
     DeviceBuffer<int32_t> d_small; // [0..1] guess, [2..3] result
@@ -451,8 +397,8 @@ const LatInstances &lat_instances(int L, bool compile_time)
         if (row.L == L) return row;
     return runtime_length;
 }
-const LatInstances &fused_instances(const pdog_tracker *t) { return lat_instances(t->L, t->fused.c); }
-const LatInstances &tiled_instances(const pdog_tracker *t) { return lat_instances(t->L, t->tiled.c); }
+const LatInstances &fused_instances(const pdog_tracker *t) { return lat_instances(t->L, t->plan.fused.c); }
+const LatInstances &tiled_instances(const pdog_tracker *t) { return lat_instances(t->L, t->plan.tiled.c); }
 int raise_lds_limits(const void *const (&fns)[3], size_t bytes)
 {
     for (const void *fn : fns)
@@ -460,22 +406,8 @@ int raise_lds_limits(const void *const (&fns)[3], size_t bytes)
     return PDOG_OK;
 }
 
-// LDS row pitches of the two-pass kernels: the sliding windows (and their one-block prefetch) of the last,
-// partly masked group of 13 outputs must stay inside the zero-padded row.  nout outputs, l taps.
-// `quantum` = outputs one round of a workgroup covers (groups × outputs per task); + l rounded up to a block of 16 taps + one block of prefetch
-int twopass_pitch_q(int nout, int L, int quantum) { return (round_up(nout, quantum) + L + 48) | 1; }
-int twopass_pitch(int nout, int L, int rows = HP_ROWS) { return twopass_pitch_q(nout, L, rows == 8 ? 32 * 7 : 16 * 13); }
-
-// Outputs per task (P) of the two-pass ROW pass, per geometry.  A workgroup covers 16 × P outputs per round: a 257-wide
-// window on P = 13 (208 per round) ran a second round 24 % full.  Measured per launch (4096 windows, same session):
-//   257 wide, l = 109:  P = 5 1.94 ms, 7 1.83, 9 1.84, 11 2.20, 13 2.39, 17 2.18   (96 VGPRs at P = 9, 155 at 13)
-//   205 wide, l = 293:  P = 5 4.35 ms, 7 4.17, 9 4.11, 11 4.61, 13 3.97            (13: one round, 98 % full)
-// ⇒ P = 9 unless P = 13 fills its rounds better.  4-tap blocks (70 / 96 VGPRs instead of 94 / 155) gave another 2–5 %:
-//   257 wide, l = 109:  P = 9 1.80 ms, 11 1.94, 13 2.17, 17 1.86;   205 wide, l = 293:  P = 9 4.20 ms, 13 3.95, 17 4.64
-// COLUMN pass (32 × P outputs per round, 8 taps per block: 76 VGPRs against 125 with 16-tap blocks, −8 % on every config):
-//   257 tall, l = 109:  P = 5 2.13 ms, 7 2.36, 9 1.96, 13 2.37
-//   205 tall, l = 293:  P = 5 3.44 ms, 7 2.50, 9 2.57, 13 3.45
-// ⇒ P = 7 unless P = 9 fills its rounds better.
+// (the two-pass kernels' LDS row pitches: twopass_pitch_q, twopass_pitch, dog_layout.hpp; their outputs per task: pick_h1_outputs,
+// pick_hpass_outputs, pdog_plan.hpp)
 typedef void (*tp_fn)(TwoPassGeo, const f2 *);
 // flush: the blocked-accumulation instances (dog_twopass.hpp), for kernel lengths from TWOPASS_FLUSH_L on.  The product build
 // holds the default block sizes only (row pass 4 taps, column pass 8); the diagnostic build adds the 8- / 16-tap instances.
@@ -528,143 +460,10 @@ tp_fn hpass8_kernel_for(int P, bool resp, bool fin, int U, bool flush)
 #undef PDOG_HP8
 #undef PDOG_HP8F
 }
-tp_fn h1_kernel(const pdog_tracker *t, bool dcin) { return h1_kernel_for(t->tp_ph1, dcin, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L); }
-tp_fn hpass8_kernel(const pdog_tracker *t, bool resp, bool fin) { return hpass8_kernel_for(t->tp_php, resp, fin, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L); }
-int pick_h1_outputs(int nout)
-{
-    auto fill = [&](int p) { return (double)nout / (double)(round_up(nout, 16 * p)); };
-    return fill(13) > fill(9) + 0.05 ? 13 : 9;
-}
-int pick_hpass_outputs(int nout)
-{
-    auto fill = [&](int p) { return (double)nout / (double)(round_up(nout, 32 * p)); };
-    return fill(9) > fill(7) + 0.05 ? 9 : 7;
-}
-int refine_slice_rows(int NA, int L, int cbw, size_t budget)
-{
-    return (int)std::max<size_t>(8, std::min<size_t>((size_t)NA, budget / (size_t)refine_tile_pitch(cbw, L)));
-}
+tp_fn h1_kernel(const pdog_tracker *t, bool dcin) { return h1_kernel_for(t->plan.tp_ph1, dcin, t->sw.h1_u, t->L >= TWOPASS_FLUSH_L); }
+tp_fn hpass8_kernel(const pdog_tracker *t, bool resp, bool fin) { return hpass8_kernel_for(t->plan.tp_php, resp, fin, t->sw.hp_u, t->L >= TWOPASS_FLUSH_L); }
 int ensure_capacity(pdog_tracker *t, int n);
-enum KernelFamily : int { kFamRoll, kFamRing, kFamFused, kFamTwoPass8, kFamTwoPass16 };
 ExactCtl exact_ctl(const pdog_tracker *t, KernelFamily fam);
-
-// Outputs per task of the fused / tiled kernels: fewest rounds of 1024 tasks, then least work per task (≈ P outputs + a fixed cost)
-int pick_outputs_per_task(int lines, int nout, std::initializer_list<int> ps, double fixed)
-{
-    int best = 0;
-    double best_cost = 0;
-    for (int p : ps) {
-        const long long tasks = (long long)lines * ((nout + p - 1) / p);
-        const double cost = (double)((tasks + FUSED_NT - 1) / FUSED_NT) * (p + fixed);
-        if (!best || cost < best_cost) { best = p; best_cost = cost; }
-    }
-    return best;
-}
-
-// Pitches and task sizes of a tile of n1 × n2 outputs (the window, or a sub-window of it) under the instance p.c names.
-void plan_tile(TilePlan &p, int n1, int n2, int L)
-{
-    p.pitchA = p.c ? fusedc_pitch_a(n2, L) : fused_pitch_a(n2, L);
-    p.pitchV = fused_pitch_v(n1, L);
-    for (p.cshift = 0; (1 << p.cshift) < (n2 + L - 1 + 3) / 4;) ++p.cshift;
-    p.pr = p.c ? fusedc_row_outputs(n1 + L - 1, n2) : pick_outputs_per_task(n1 + L - 1, n2, {3, 4, 5, 6, 8}, 2.0);
-    p.pc = pick_outputs_per_task(n2, n1, {2, 3, 4, 6, 8}, 1.5);
-}
-
-// The fused kernel for this geometry: its instance, its LDS and the refinement's share of it, whether it fits (the one place
-// that decides), and what a launch copies into FusedGeo.  `resident` is left for make_plan.
-FusedPlan plan_fused(const pdog_tracker *t)
-{
-    const int NA = t->n1 + t->L - 1, TWin = t->n2 + t->L - 1;
-    FusedPlan f;
-    f.c = fused_has_instance(t->L) && fusedc_lds_bytes(t->n1, t->n2, t->L) <= kMaxLds - 1024 && !t->sw.no_fused_c;
-    // inside the fused kernel the refinement's scratch is that kernel's own LDS (tile + RT, free by then): the widest block that
-    // fits it with the whole pixel tile resident (a window whose tile fits as floats has room for it as bytes)
-    const size_t tile = f.c ? fusedc_lds_bytes(t->n1, t->n2, t->L) : fused_lds_bytes(t->n1, t->n2, t->L);
-    f.ref_cbw = 1;
-    f.ref_rows = NA;
-    for (int cbw = std::min(8, t->n2); cbw >= 1; --cbw)
-        if (refine_lds_bytes(t->n1, t->L, cbw, NA) <= tile) { f.ref_cbw = cbw; break; }
-    if (refine_lds_bytes(t->n1, t->L, 1, NA) > kMaxLds - 1024) f.ref_rows = refine_slice_rows(NA, t->L, 1, 24576);
-    f.lds = std::max(tile, refine_lds_bytes(t->n1, t->L, f.ref_cbw, f.ref_rows));
-    f.ok = f.lds <= kMaxLds - 1024 && TWin <= 4 * FUSED_NT && t->fw >= 4;
-    plan_tile(f, t->n1, t->n2, t->L);
-    if (t->sw.fused_pr) { f.pr = t->sw.fused_pr; f.pc = t->sw.fused_pc; } // tuning switch PDOG_FUSED_P
-    return f;
-}
-
-// Tiled kernel (dog_tiled.hpp): windows too large for the fused kernel, cut into sub-windows of ≈48 rows/columns (a
-// 257×257 window: 6×6 of 43×43, each a tile of 107×107 like the default 45×45 window of the fused kernel).
-// A kernel whose own LDS (`base` bytes, at least the refinement's smallest form) doubles as the refinement's scratch: the
-// widest block of window columns whose fixed part plus 8 tile rows fits, then the tallest slice of its pixel tile (the whole
-// tile if possible) — exact mode then costs the kernel no occupancy.
-void fit_refine_scratch(const pdog_tracker *t, size_t base, int *ref_cbw, int *ref_rows)
-{
-    const int NA = t->n1 + t->L - 1;
-    *ref_cbw = 1;
-    *ref_rows = 8;
-    for (int cbw = std::min(t->n2, t->ref_cbw); cbw >= 1; --cbw) {
-        const size_t fixed_r = refine_lds_bytes(t->n1, t->L, cbw, 0);
-        if (fixed_r + (size_t)8 * refine_tile_pitch(cbw, t->L) > base) continue;
-        *ref_cbw = cbw;
-        *ref_rows = (int)std::min<size_t>((size_t)NA, (base - fixed_r) / (size_t)refine_tile_pitch(cbw, t->L));
-        while (*ref_rows > 8 && refine_lds_bytes(t->n1, t->L, cbw, *ref_rows) > base) --*ref_rows;
-        return;
-    }
-}
-int plan_tiled(pdog_tracker *t)
-{
-    TiledPlan &p = t->tiled = TiledPlan();
-    // partial slots per window: the most over all variants, so that a later pdog_set_variant never reallocates …
-    t->part_slots = (t->n2 + 7) / 8;
-    for (int i = 0; i < kNumVariants; ++i)
-        if (!kVariants[i].fused) t->part_slots = std::max(t->part_slots, (t->n2 + kVariants[i].tw() - 1) / kVariants[i].tw() + kThinMax);
-    if ((t->fused.ok && !t->sw.tiled_force) || t->sw.no_tiled || t->fw < 4) return PDOG_OK;
-    // Sub-window edge: ≈32 measured best for a 257×257 window (81 workgroups: 13.9 µs per frame; 48: 15.3), but beyond
-    // ≈128 workgroups the partial exchange costs more than smaller tiles save (513×513: 121 workgroups of 47 → 17.8 µs,
-    // 169 of 40 → 21.9); long kernels need smaller sub-windows for their halo to fit LDS.
-    int sn1 = 0, sn2 = 0, ns1 = 0, ns2 = 0;
-    size_t need = 0;
-    bool found = false;
-    const int user = t->sw.tiled_sub;
-    p.c = fused_has_instance(t->L) && !t->sw.no_fused_c;
-    // (round 3, with the one-round-trip exchange: 129×129 at 24 → 36 workgroups 8.6–8.8 µs against 9.2–9.7 at 32 → 25; 257×257 at 20 / 24 /
-    // 32: 9.8–10.1 / 10.2 / 10.2–10.5 — kept at 32 so that three clips stay resident; 513×513 at 36 → 225 workgroups 12.2–12.6 against 13.0 at 48)
-    bool small_first = true;
-    for (int target : {24, 32, 40, 48, 56, 64, 24, 16}) {
-        const bool probe24 = small_first && target == 24; // small windows first try 24: only while that keeps the clip at ≤ 48 workgroups
-        small_first = false;
-        if (user) target = user;
-        ns1 = (t->n1 + target - 1) / target;
-        ns2 = (t->n2 + target - 1) / target;
-        sn1 = (t->n1 + ns1 - 1) / ns1;
-        sn2 = (t->n2 + ns2 - 1) / ns2;
-        ns1 = (t->n1 + sn1 - 1) / sn1;
-        ns2 = (t->n2 + sn2 - 1) / sn2;
-        need = p.c ? fusedc_lds_bytes(sn1, sn2, t->L) : fused_lds_bytes(sn1, sn2, t->L);
-        const bool fits = need <= kMaxLds - 1024 && sn2 + t->L - 1 <= 4 * FUSED_NT && (long long)t->n1 * t->n2 < (1 << 24) && // (a partial's index shares a word with 8 tag bits)
-                          (long long)ns1 * ns2 <= (target >= 32 && !user ? 128 : TILED_SLOT_CAP);
-        if (fits && !(probe24 && !user && (long long)ns1 * ns2 > 48)) { found = true; break; }
-        if (user) break;
-    }
-    if (!found) return PDOG_OK;
-    // the refinement's scratch is the kernel's own LDS: at least its smallest form must fit; then the widest block that does
-    const size_t base = std::max(need, refine_lds_bytes(t->n1, t->L, 1, 8));
-    if (base > kMaxLds - 1024) return PDOG_OK;
-    fit_refine_scratch(t, base, &p.ref_cbw, &p.ref_rows);
-    p.sn1 = sn1; p.sn2 = sn2; p.ns1 = ns1; p.ns2 = ns2;
-    p.lds = base;
-    plan_tile(p, sn1, sn2, t->L);
-    if (int rc = raise_lds_limits(tiled_instances(t).tiled, base)) return rc;
-    int per_cu = 0, cus = 0, coop = 0; // chains need every workgroup of a clip resident at once: a cooperative launch, if the device has them
-    if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, t->device) == hipSuccess && coop &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tiled_instances(t).tiled[kLatPlain], FUSED_NT, base) == hipSuccess && per_cu >= 1 &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess)
-        p.resident = per_cu * cus;
-    t->part_slots = std::max(t->part_slots, 2 * ns1 * ns2); // … and the tiled kernel's partials: two sets per window
-    p.ok = true;
-    return PDOG_OK;
-}
 
 // What a launch works on.  A caller sets the fields it uses; the rest keep these defaults.
 struct Request {
@@ -711,20 +510,14 @@ void use_partials(const pdog_tracker *t, LaunchGeo &g)
     g.part_mask = t->d_part_mask.get();
 }
 
-// What launch_tiled takes: n windows, or n clips of chain_len > 1 frames with every sub-window's workgroup resident at once.
-bool tiled_serves(const pdog_tracker *t, int n, int chain_len)
-{
-    return t->tiled.ok && n >= 1 && (chain_len <= 1 || (long long)n * t->tiled.ns1 * t->tiled.ns2 <= t->tiled.resident);
-}
-
 // req.n windows (chain_len = 1: independent; ordinary launch) or req.n clips of chain_len frames (cooperative launch: the
 // workgroups of a clip wait for each other's partials frame by frame).  *launched = false: not taken, the caller goes on.
 int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
 {
     *launched = false;
     const int n = req.n, chain_len = req.chain_len;
-    if (!tiled_serves(t, n, chain_len)) return PDOG_OK;
-    const TiledPlan &p = t->tiled;
+    if (!tiled_serves(t->plan, t->tiled_resident, n, chain_len)) return PDOG_OK;
+    const TiledPlan &p = t->plan.tiled;
     TiledRun &run = t->tiled_run;
     const int nsub = p.ns1 * p.ns2;
     if (int rc = ensure_capacity(t, n)) return rc;
@@ -781,119 +574,70 @@ int launch_tiled(pdog_tracker *t, const Request &req, bool *launched)
     return PDOG_OK;
 }
 
-// Everything the tracker derives from its geometry, its switches and the pinned variant id (`forced`, or -1): the batch kernel
-// and its strips, the refinement's geometry, the fused and tiled kernels' plans, the two-pass task sizes, part_slots — and the
-// LDS limits of every kernel those may launch, which only ever rise.  pdog_create, pdog_set_variant and the pdog_set_tuning
-// keys that change an input call this and nothing else; no caller patches a derived field.  A variant that does not fit is
-// refused before anything changes.
-// Kernel lengths with a roll instance: l = 17 … 149 (dog_roll.hpp, roll_lengths.def; l = 101 … 149 at two waves per SIMD,
-// without spills); longer kernels take the two-pass path.
-int make_plan(pdog_tracker *t, int forced)
+Geometry geometry_of(const pdog_tracker *t) { return Geometry{t->fh, t->fw, t->n1, t->n2, t->L}; }
+
+// Makes `p` (make_plan's, for the switches `sw`) the tracker's plan: raises the LDS limit of every kernel the plan may launch
+// — they only ever rise — and asks the device how many workgroups of the tiled kernel it keeps resident.  Only then are the
+// plan, the switches it was made for and the device's answers assigned: a refusal leaves the tracker as it was.
+int apply_plan(pdog_tracker *t, const Switches &sw, const Plan &p)
 {
-    FusedPlan fused = plan_fused(t);
-    const Variant *best = nullptr;
-    double best_cost = 0;
-    for (int i = 0; i < kNumVariants; ++i) {
-        const Variant &v = kVariants[i];
-        if (forced >= 0 && v.id != forced) continue;
-        if (v.fused) { // never the tracker's batch kernel unless forced; small batches and chains reach it below
-            if (forced == v.id && fused.ok) best = &v;
-            continue;
-        }
-        if (v.LT != 0 && v.LT != t->L) continue;
-        if (v.lds(t->L) > kMaxLds) continue;
-        const bool roll_serves = has_roll_instance(t->L);
-        if (forced < 0 && t->L >= ROLL_LMIN && !roll_serves && !v.twopass) continue; // long kernels without a roll instance: two-pass path (measured 1.7× the ring kernel at l = 293)
-        if (v.twopass) {
-            const size_t hl = (size_t)HP_ROWS * twopass_pitch(t->n1, t->L) * sizeof(f2);
-            if (hl > kMaxLds - 1024) continue;
-            if (forced < 0 && (roll_serves || t->L < ROLL_LMIN)) continue; // the ring/roll kernels win where a spill-free roll instance exists
-            if (!best || forced >= 0) { best = &v; best_cost = 0.0; }
-            continue;
-        }
-        // crude cost: columns computed × per-column efficiency guess; compile-time L wins
-        const int strips = (t->n2 + v.tw() - 1) / v.tw();
-        double cost = (double)strips * v.tw() * (v.LT ? 1.0 : 1.6);
-        if (v.lds(t->L) > kMaxLds / 2) cost *= 1.3; // one workgroup per CU only
-        if (v.roll) {
-            // barrier-free rolling kernel: ≈2× the ring kernels per column (measured, cfg3); thin
-            // remainder columns cost next to nothing
-            const int r = t->n2 % v.tw();
-            const int cols = (t->n2 > v.tw() && r > 0 && r <= kThinMax) ? t->n2 - r : strips * v.tw();
-            cost = 0.5 * cols;
-        }
-        if (!best || cost < best_cost) { best = &v; best_cost = cost; }
+    const VariantKernels *k = kernels_of(*p.shape);
+    if (!k) return fail(PDOG_E_ARG, "kVariants and kVariantShapes name different variants in a row");
+    const bool flush = t->L >= TWOPASS_FLUSH_L;
+    if (p.lds.fused)
+        if (int rc = raise_lds_limits(lat_instances(t->L, p.fused.c).fused, p.lds.fused)) return rc;
+    int tiled_resident = 0;
+    if (p.lds.tiled) {
+        const LatInstances &tiled = lat_instances(t->L, p.tiled.c);
+        if (int rc = raise_lds_limits(tiled.tiled, p.lds.tiled)) return rc;
+        int per_cu = 0, cus = 0, coop = 0; // chains need every workgroup of a clip resident at once: a cooperative launch, if the device has them
+        if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, t->device) == hipSuccess && coop &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tiled.tiled[kLatPlain], FUSED_NT, p.lds.tiled) == hipSuccess && per_cu >= 1 &&
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess)
+            tiled_resident = per_cu * cus;
     }
-    if (!best) return fail(PDOG_E_ARG, "no kernel specialisation fits this target_width/window (LDS)");
-    t->var = best;
-    t->nstrips = (t->n2 + best->tw() - 1) / best->tw();
-    t->nthin = 0;
-    t->thin_x0 = 0;
-    t->forced_variant = forced >= 0;
-    t->small_twopass = false;
-    // Exact mode's refinement (dog_exact.hpp) works on blocks of `cbw` window columns whose row-pass result (two doubles
-    // per element in the Float64 stage) fits ≈24 KB of LDS; the block's pixels go through an LDS tile — all n1 + l − 1 rows
-    // resident when that fits 100 KB in total (l ≲ 150: a candidate's exact chain then reads LDS), otherwise ≈24 KB slices.
-    const int NA = t->n1 + t->L - 1;
-    t->ref_cbw = std::max(1, std::min({8, t->n2, (int)(24576 / ((size_t)NA * 16))}));
-    t->ref_rows = refine_lds_bytes(t->n1, t->L, t->ref_cbw, NA) <= 100 * 1024 ? NA : refine_slice_rows(NA, t->L, t->ref_cbw, 24576);
+    if (p.lds.tp_col16) { // (the three two-pass numbers are set together: small_twopass)
+        for (const void *f : {(const void *)dog_hpass_kernel<13, 16, false>, (const void *)dog_hpass_kernel<13, 16, true>}) {
+            if (int rc = raise_lds_limit(f, p.lds.tp_col16)) return rc;
+        }
+        for (bool resp : {false, true})
+            for (bool fin : {false, true})
+                if (int rc = raise_lds_limit((const void *)hpass8_kernel_for(p.tp_php, resp, fin, sw.hp_u, flush), p.lds.tp_col8)) return rc;
+        for (bool dcin : {false, true})
+            if (int rc = raise_lds_limit((const void *)h1_kernel_for(p.tp_ph1, dcin, sw.h1_u, flush), p.lds.tp_row)) return rc;
+    }
+    if (p.lds.thin)
+        for (kernel_fn f : {k->thin, k->thin_resp}) {
+            if (int rc = raise_lds_limit((const void *)f, p.lds.thin)) return rc;
+        }
+    if (p.lds.batch)
+        for (kernel_fn f : {k->fn, k->fn_resp}) {
+            if (int rc = raise_lds_limit((const void *)f, p.lds.batch)) return rc;
+        }
+    if (int rc = raise_lds_limit((const void *)dog_finish_kernel, p.lds.finish)) return rc;
     // (the count of resident workgroups stands while the instance and its LDS do; launch_fused asks again otherwise)
-    if (fused.c == t->fused.c && fused.lds == t->fused.lds) fused.resident = t->fused.resident;
-    t->fused = fused;
-    if (fused.ok)
-        if (int rc = raise_lds_limits(fused_instances(t).fused, fused.lds)) return rc;
-    if (int rc = plan_tiled(t)) return rc;
-    if (best->fused) { t->nstrips = 1; return PDOG_OK; }
-    {
-        // The two-pass kernels spread one window over dozens of workgroups, so they win whenever the batch
-        // cannot fill the GPU with one wave per strip (single-frame tracking: 36 µs vs 144 µs for one
-        // 257×257 window).  Set them up whenever their LDS tiles fit.
-        t->tp_ph1 = t->sw.tp_ph1 ? t->sw.tp_ph1 : pick_h1_outputs(t->n2);
-        t->tp_php = t->sw.tp_php ? t->sw.tp_php : pick_hpass_outputs(t->n1);
-        const size_t hl = (size_t)HP_ROWS * twopass_pitch(t->n1, t->L) * sizeof(f2);
-        const size_t h1l = (size_t)HP_ROWS * twopass_pitch_q(t->n2, t->L, 16 * t->tp_ph1) * sizeof(float);
-        const size_t hl8 = (size_t)8 * twopass_pitch_q(t->n1, t->L, 32 * t->tp_php) * sizeof(f2);
-        if (hl <= kMaxLds - 1024 && h1l <= kMaxLds - 1024 && hl8 <= kMaxLds - 1024) {
-            for (const void *f : {(const void *)dog_hpass_kernel<13, 16, false>, (const void *)dog_hpass_kernel<13, 16, true>}) {
-                if (int rc = raise_lds_limit(f, hl)) return rc;
-            }
-            for (bool resp : {false, true})
-                for (bool fin : {false, true})
-                    if (int rc = raise_lds_limit((const void *)hpass8_kernel(t, resp, fin), hl8)) return rc;
-            for (bool dcin : {false, true})
-                if (int rc = raise_lds_limit((const void *)h1_kernel(t, dcin), h1l)) return rc;
-            t->small_twopass = true;
-        }
-    }
-    if (best->twopass) {
-        t->nstrips = (t->n2 + HP_ROWS - 1) / HP_ROWS; // partial slots = 16-column blocks
-        if (!t->small_twopass) return fail(PDOG_E_ARG, "two-pass kernels: the window's rows do not fit LDS");
-        return PDOG_OK;
-    }
-    if (best->roll && best->thin && t->n2 > best->tw()) {
-        // width = 64·k + r: r ≤ kThinMax columns are cheaper one by one than as an extra strip
-        const int r = t->n2 % best->tw();
-        const size_t thin_lds = thin_lds_bytes(t->n1, t->L);
-        if (r > 0 && r <= kThinMax && thin_lds <= kMaxLds - 1024) {
-            for (kernel_fn f : {best->thin, best->thin_resp}) {
-                if (int rc = raise_lds_limit((const void *)f, thin_lds)) return rc;
-            }
-            t->nthin = r;
-            t->thin_x0 = t->n2 - r;
-            t->nstrips = t->thin_x0 / best->tw();
-        }
-    }
-    for (kernel_fn f : {best->fn, best->fn_resp}) {
-        if (int rc = raise_lds_limit((const void *)f, best->lds(t->L))) return rc;
-    }
+    if (!(p.fused.c == t->plan.fused.c && p.fused.lds == t->plan.fused.lds)) t->fused_resident = 0;
+    t->tiled_resident = tiled_resident;
+    t->kern = k;
+    t->sw = sw;
+    t->plan = p;
     return PDOG_OK;
+}
+
+// make_plan, then apply_plan: what pdog_create, pdog_set_variant and the pdog_set_tuning keys that change an input of the plan do.
+int replan(pdog_tracker *t, const Switches &sw, int forced)
+{
+    Plan p;
+    std::string why;
+    if (int rc = make_plan(geometry_of(t), sw, forced, &p, &why)) return fail(rc, why);
+    return apply_plan(t, sw, p);
 }
 
 // Room for the partials of n windows.  Growing drains the tracker's stream first, once (the four arrays grow together;
 // a failure leaves the later ones empty, so the smallest capacity decides).
 int ensure_capacity(pdog_tracker *t, int n)
 {
-    const size_t need = (size_t)n * t->part_slots;
+    const size_t need = (size_t)n * t->plan.part_slots;
     if (need <= std::min({t->d_part_val.capacity(), t->d_part_sec.capacity(), t->d_part_idx.capacity(), t->d_part_mask.capacity()})) return PDOG_OK;
     HIP_TRY(hipStreamSynchronize(t->stream));
     if (int rc = t->d_part_val.reserve(need, nullptr)) return rc;
@@ -902,64 +646,16 @@ int ensure_capacity(pdog_tracker *t, int n)
     return t->d_part_mask.reserve(need, nullptr);
 }
 
-// Which kernel family a batch of n windows runs on (kPathFused, kPathTiled, kPathTwoPass, otherwise the tracker's
-// batch kernel).  A batch of fewer than ≈1000 strip-waves cannot fill 256 CUs × 8 waves with one wave per strip:
-// windows that fit in LDS then go to the fused kernel (one workgroup per window, one launch), larger ones to the
-// two-pass kernels (dozens of workgroups per window).  pdog_set_variant pins the tracker's kernel.
-int path_for_batch(const pdog_tracker *t, int n)
-{
-    const Variant &v = *t->var;
-    if (v.fused) return kPathFused;
-    if (t->forced_variant) return v.twopass ? kPathTwoPass : v.id;
-    // (round 3, with the compile-time-l fused instances: 45×45 windows 1024 / 1536 / 2048 per batch: fused 53.8 / 77.3 / 101.9 µs, roll 79.2 / 75.7 / 103.6;
-    // 63×63: 80.9 / 117.5 / 155.8 against 91.6 / 88.7 / 117.2)
-    // (… and since a workgroup of the fused kernel walks several windows — dispatch, prologue and first tap loads once per workgroup — 45×45 windows:
-    // 1024 / 2048 / 4096 per batch 44.5 / 83 / 155 µs against the roll kernel's 79 / 103 / 163: windows below 3000 pixels stay on it at any batch size)
-    const bool few = v.twopass ? n <= 256 : ((long long)n * (t->nstrips + (t->nthin ? 1 : 0)) < 1200 || (long long)t->n1 * t->n2 < 3000);
-    if (t->sw.tiled_force && t->tiled.ok && n <= t->sw.tiled_batch) return kPathTiled; // experiment switch
-    if (few && t->fused.ok) return kPathFused;
-    if (t->tiled.ok && n <= t->sw.tiled_batch) return kPathTiled; // one or two windows too large for the fused kernel: one launch (dog_tiled.hpp)
-    if (v.twopass || (few && t->small_twopass)) return kPathTwoPass;
-    return v.id;
-}
-
-// ---- exact mode's FP32 error bounds: exact_factors (pdog_math.cpp) per kernel family, and here ----
-// the two-pass kernels' factor for the tracker's task sizes (hr8: the 8-row column-pass kernels, else the 16-row form <13, 16>)
-double twopass_factor(const pdog_tracker *t, bool hr8)
-{
-    if (!hr8 || t->L < TWOPASS_FLUSH_L) return t->F_sym_sep; // the plain instances: symmetric row pass, separate column chains
-    const int l = t->L, H = l / 2;
-    const int U1 = t->sw.h1_u, m_r = twopass_ring(t->tp_ph1, U1), U2 = hr8 ? t->sw.hp_u : 16, m_c = hr8 ? twopass_ring(t->tp_php, U2) : twopass_ring(13, 16);
-    auto blocked = [](const std::vector<double> &terms, int m, int n_full) { // chains of m terms (n_full of them), then ONE chain with the rest
-        double F = 0, total = 0;
-        const int n = (int)terms.size();
-        for (int c = 0, a = 0; c <= n_full; ++c) {
-            const int b = c < n_full ? std::min(a + m, n) : n; // (the column pass's last full trip may end in the table's zero padding: l = 113, 117, 137, …)
-            double w = 0;
-            for (int i = a; i < b; ++i) { w += terms[i]; F += w; } // the chain's own running sums, from zero
-            total += w;
-            F += total;                                             // the addition that takes the chain's sum into the running total
-            a = b;
-        }
-        return F;
-    };
-    auto row = [&](const std::vector<double> &g) {
-        std::vector<double> terms(H + 1);
-        for (int k = 0; k <= H; ++k) terms[k] = (k < H ? 2.0 : 1.0) * g[k];
-        return blocked(terms, m_r, (H / U1) / (m_r / U1)) + 1.0;
-    };
-    auto col = [&](const std::vector<double> &g) { return blocked(g, m_c, ((l + U2 - 1) / U2) / (m_c / U2)); };
-    return row(t->h_gp) + row(t->h_gm) + col(t->h_gp) + col(t->h_gm) + 4.0;
-}
+// ---- exact mode's FP32 error bounds per kernel family (exact_factors, pdog_math.cpp; twopass_factor and exact_thresholds, pdog_plan.hpp) ----
 ExactCtl exact_ctl(const pdog_tracker *t, KernelFamily fam)
 {
     ExactCtl x;
     x.stat = t->d_ref_stat.get();
     x.range_err = t->h_pinned.device() ? &t->h_pinned.device()->kernel : nullptr;
-    const double F = fam == kFamRoll ? t->F_sym_int : fam == kFamRing ? t->F_ring : fam == kFamFused ? t->F_sym_sep : twopass_factor(t, fam == kFamTwoPass8);
-    const double u = std::ldexp(1.0, -24);
-    x.T = t->exact_all ? __builtin_huge_valf() : std::nextafter((float)(2.0 * u * F * 1.02 + 2e-9), 1.0f);
-    x.T_rescan = t->exact_all ? __builtin_huge_valf() : std::nextafter((float)(u * (F + t->F_rescan) * 1.02 + 2e-9), 1.0f);
+    const double F = family_factor(fam, t->F_sym_int, t->F_sym_sep, t->F_ring, t->plan, t->sw, t->h_gp, t->h_gm);
+    const ExactThresholds th = exact_thresholds(F, t->F_rescan, t->exact_all);
+    x.T = th.T;
+    x.T_rescan = th.T_rescan;
     return x;
 }
 
@@ -986,8 +682,8 @@ int launch_finish(pdog_tracker *t, const LaunchGeo &g, const Finish &f)
     fg.g64 = t->d_g64.get();
     fg.dir = t->darker ? -1.0 : 1.0;
     fg.T64 = t->exact_T64;
-    fg.cbw = t->ref_cbw;
-    fg.tile_rows = t->ref_rows;
+    fg.cbw = t->plan.ref_cbw;
+    fg.tile_rows = t->plan.ref_rows;
     fg.slot_w = f.slot_w;
     fg.slot_last = f.slot_last;
     fg.nmain = g.nslots - g.nthin;
@@ -999,7 +695,7 @@ int launch_finish(pdog_tracker *t, const LaunchGeo &g, const Finish &f)
     fg.done_value = f.done_value;
     fg.seq_windows = (int)t->win_launched;
     t->win_launched += (unsigned)g.n;
-    size_t lds = t->exact ? refine_lds_bytes(t->n1, t->L, t->ref_cbw, t->ref_rows) : 0;
+    size_t lds = t->exact ? refine_lds_bytes(t->n1, t->L, t->plan.ref_cbw, t->plan.ref_rows) : 0;
     if (g.fold_r) { // the folded remainder column's R values, one slice per wave (a window each)
         lds = std::max(lds, (size_t)FINISH_WPB * (t->n1 + t->L - 1 + FOLD_GO) * sizeof(f2));
         if (int rc = raise_lds_limit((const void *)dog_finish_kernel, lds)) return rc;
@@ -1014,7 +710,7 @@ int launch_finish(pdog_tracker *t, const LaunchGeo &g, const Finish &f)
 int launch_fused(pdog_tracker *t, const Request &req)
 {
     const int n = req.n, chain_len = req.chain_len;
-    FusedPlan &p = t->fused;
+    const FusedPlan &p = t->plan.fused;
     FusedPredictGeo fg; // (a launch without a table takes its FusedGeo part, one without prediction its FusedTableGeo part)
     fg.pred = req.predict ? *req.predict : PredictCtl{0.f, 0, nullptr, nullptr};
     fg.tab = req.table;
@@ -1077,16 +773,16 @@ int launch_fused(pdog_tracker *t, const Request &req)
         return PDOG_OK;
     }
 #endif
-    if (p.resident <= 0) { // once per plan
+    if (t->fused_resident <= 0) { // once per plan
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, FUSED_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus < 1) cus = 256;
-        p.resident = per_cu * cus;
+        t->fused_resident = per_cu * cus;
     }
-    const dim3 grid(std::min(n, p.resident));
+    const dim3 grid(std::min(n, t->fused_resident));
     if (req.predict) {
         const fused_predict_fn_t fp = fused_instances(t).fused_predict;
-        if (int rc = raise_lds_limit((const void *)fp, lds)) return rc; // (here, not in make_plan: a tracker that never predicts sets nothing up)
+        if (int rc = raise_lds_limit((const void *)fp, lds)) return rc; // (here, not in apply_plan: a tracker that never predicts sets nothing up)
         hipLaunchKernelGGL(fp, grid, dim3(FUSED_NT), lds, t->stream, fg, tr, tc);
     } else if (req.table.index)
         hipLaunchKernelGGL((fused_table_fn_t)fused_instances(t).fused[kLatTable], grid, dim3(FUSED_NT), lds, t->stream, static_cast<const FusedTableGeo &>(fg), tr, tc);
@@ -1127,8 +823,8 @@ int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticke
     tg.NA = t->n1 + t->L - 1;
     tg.h1blocks_per_win = (tg.NA + HP_ROWS - 1) / HP_ROWS;
     tg.hblocks_per_win = tp_slots;
-    tg.pitchA = twopass_pitch_q(t->n2, t->L, 16 * t->tp_ph1);
-    tg.pitchV = hr == 8 ? twopass_pitch_q(t->n1, t->L, 32 * t->tp_php) : twopass_pitch(t->n1, t->L, hr);
+    tg.pitchA = twopass_pitch_q(t->n2, t->L, 16 * t->plan.tp_ph1);
+    tg.pitchV = hr == 8 ? twopass_pitch_q(t->n1, t->L, 32 * t->plan.tp_php) : twopass_pitch(t->n1, t->L, hr);
     const size_t per_win = (size_t)t->n2 * tg.NA; // f2 elements of HBM scratch for the transposed intermediate; larger batches go in chunks
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, t->sw.scratch_cap / (per_win * sizeof(f2))));
     if (int rc = t->d_V.reserve(per_win * chunk, &t->stream)) return rc;
@@ -1203,11 +899,11 @@ int launch_twopass(pdog_tracker *t, const Request &req, LaunchGeo g, bool *ticke
 constexpr int kPruneXcdGroup = PDOG_PRUNE_XCD_GROUP;
 static_assert(kPruneXcdGroup >= 1 && (kPruneXcdGroup & (kPruneXcdGroup - 1)) == 0, "a power of two");
 constexpr size_t kPruneMaxLds = 64 * 1024; // (the pre-pass's dynamic LDS without raising the kernel's limit; larger windows stay dense)
-bool use_pruning(pdog_tracker *t, const Variant &v, bool want_resp, int nslots)
+bool use_pruning(pdog_tracker *t, bool want_resp, int nslots)
 {
     // dense: the response-writing instances, pdog_set_exact(t, 2) (infinite thresholds), "no_prune", every other kernel family
     // (ahead of the policy: a launch that cannot prune is no observation)
-    if (!v.roll || !v.fn_prune || want_resp || t->exact_all || t->sw.no_prune || prune_lds(t->n1, t->n2, t->L, nslots).total > kPruneMaxLds) return false;
+    if (!t->kern->fn_prune || want_resp || t->exact_all || t->sw.no_prune || prune_lds(t->n1, t->n2, t->L, nslots).total > kPruneMaxLds) return false;
     return t->prune_policy.decide(__atomic_load_n(&t->h_pinned.get()->prune_pub, __ATOMIC_ACQUIRE));
 }
 
@@ -1215,7 +911,10 @@ bool use_pruning(pdog_tracker *t, const Variant &v, bool want_resp, int nslots)
 // them, then the finishing kernel.  `g` arrives as launch_detect filled it.
 int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
 {
-    const Variant &v = *t->var;
+    const VariantShape &v = *t->plan.shape;
+    const VariantKernels &k = *t->kern;
+    const Plan &plan = t->plan;
+    const bool roll = v.family == Family::Roll;
     const int n = req.n;
     int grid = round_up(g.nblocks, 8);
     // Exact mode: batches whose predecessors flagged many of their windows write their responses, and the finishing kernel
@@ -1239,8 +938,8 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     // 49 packed instructions per sub-chunk) and the finishing kernel gains the column pass — +2.7 % per cfg3 step (4 strips per
     // window), −0.8 % per cfg4 step (8 strips).  A variant that kept the R column in the strip's LDS and ran the column pass in
     // the strip's own wave cost a wave per SIMD (12.9 KB per wave) and +5 %.  So: folded from 8 strips per window on.
-    const bool prune = use_pruning(t, v, want_resp, g.nslots);
-    const bool fold = v.roll && roll_folds(v.LT) && t->nthin == 1 && !want_resp && !prune && !t->sw.no_fold && (t->nstrips >= 8 || t->sw.fold_always) &&
+    const bool prune = use_pruning(t, want_resp, g.nslots);
+    const bool fold = roll && roll_folds(v.LT) && plan.nthin == 1 && !want_resp && !prune && !t->sw.no_fold && (plan.nstrips >= 8 || t->sw.fold_always) &&
                       (size_t)FINISH_WPB * fold_wave_lds <= kMaxLds - 1024;
     const f2 *tr = t->d_taps_row.get(), *tc = t->d_taps_col.get();
     if (prune) { // the pre-pass leaves every slot's kept range in part_mask, ahead of the strips and (through the fork) the thin kernel
@@ -1271,12 +970,12 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     if (fold) {
         if (int rc = t->d_fold_r.reserve((size_t)n * NA, &t->stream)) return rc;
         g.fold_r = t->d_fold_r.get();
-    } else if (t->nthin) {
+    } else if (plan.nthin) {
         // fork: the thin kernel only reads the frames and writes its own partial slots
         HIP_TRY(hipEventRecord(t->ev_fork, t->stream));
         HIP_TRY(hipStreamWaitEvent(t->aux_stream, t->ev_fork, 0));
         const size_t thin_lds = thin_lds_bytes(t->n1, t->L);
-        hipLaunchKernelGGL(want_resp ? v.thin_resp : v.thin, dim3(round_up(n * t->nthin, 8)), dim3(256), thin_lds, t->aux_stream, g, tr, tc);
+        hipLaunchKernelGGL(want_resp ? k.thin_resp : k.thin, dim3(round_up(n * plan.nthin, 8)), dim3(256), thin_lds, t->aux_stream, g, tr, tc);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(t->ev_join, t->aux_stream));
     }
@@ -1284,11 +983,11 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
 #ifdef PDOG_ABLATIONS
     if (t->sw.lds_pad) { // occupancy experiments: extra LDS per workgroup
         lds_bytes += (size_t)t->sw.lds_pad;
-        (void)raise_lds_limit((const void *)(want_resp ? v.fn_resp : v.fn), lds_bytes);
+        (void)raise_lds_limit((const void *)(want_resp ? k.fn_resp : k.fn), lds_bytes);
     }
 #endif
-    kernel_fn fn = want_resp ? v.fn_resp : prune ? v.fn_prune : v.fn;
-    if (!want_resp && !prune && v.roll && v.LT == 65 && v.id == 100) { // instances with statically shortened epilogue bodies for the common window heights
+    kernel_fn fn = want_resp ? k.fn_resp : prune ? k.fn_prune : k.fn;
+    if (!want_resp && !prune && roll && v.LT == 65 && v.id == 100) { // instances with statically shortened epilogue bodies for the common window heights
         const int cls = roll_epi_class(t->n1, 65);
 #define PDOG_EPI_PICK(C) if (cls == C) fn = (kernel_fn)dog_roll_kernel<65, false, 0, C>;
         PDOG_EPI_CLASSES(PDOG_EPI_PICK)
@@ -1297,18 +996,18 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
     {
         LaunchGeo gs = g; // (the finishing kernel reads fold_r: the job list is the strips' alone)
         if (prune) gs.jobs = t->d_prune_jobs.get();
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(v.NT), lds_bytes, t->stream, gs, tr, v.roll ? (const f2 *)t->d_taps_roll.get() : tc);
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(v.NT), lds_bytes, t->stream, gs, tr, roll ? (const f2 *)t->d_taps_roll.get() : tc);
     }
     HIP_TRY(hipGetLastError());
-    if (t->nthin && !fold) HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0)); // join before the strip combine
+    if (plan.nthin && !fold) HIP_TRY(hipStreamWaitEvent(t->stream, t->ev_join, 0)); // join before the strip combine
     // roll: 64-column strips over the first `covered` columns, the last one shifted left to stay inside; ring: tw() columns each
-    const int covered = t->nthin ? t->thin_x0 : t->n2;
+    const int covered = plan.nthin ? plan.thin_x0 : t->n2;
     t->last_n = n;
     t->last_nslots = g.nslots;
     Finish fin;
     fin.slot_w = v.tw();
-    if (v.roll) fin.slot_last = std::max(0, covered - v.tw());
-    fin.use_mask = v.roll;
+    if (roll) fin.slot_last = std::max(0, covered - v.tw());
+    fin.use_mask = roll;
     fin.map = g.resp;
     fin.out_ij = req.out_ij;
     return launch_finish(t, g, fin);
@@ -1318,9 +1017,10 @@ int launch_strips(pdog_tracker *t, const Request &req, LaunchGeo g)
 // req.done_value at req.done_flag (the single-window paths).
 int launch_detect(pdog_tracker *t, const Request &req, bool *ticket_armed = nullptr)
 {
-    const Variant &v = *t->var;
+    const VariantShape &v = *t->plan.shape;
+    const Plan &plan = t->plan;
     if (ticket_armed) *ticket_armed = false;
-    const int path = path_for_batch(t, req.n);
+    const int path = path_for_batch(plan, t->sw, req.n);
     // windows that fit in LDS, in batches too small to fill the GPU any other way: the fused kernel, one workgroup per window,
     // one launch; one or a few windows too large for it: the tiled kernel, one launch (dog_tiled.hpp)
     if (path == kPathFused || path == kPathTiled) {
@@ -1337,14 +1037,14 @@ int launch_detect(pdog_tracker *t, const Request &req, bool *ticket_armed = null
     }
     LaunchGeo g = base_geo(t, req);
     use_partials(t, g);
-    g.ex = exact_ctl(t, (v.roll ? kFamRoll : kFamRing));
-    g.nstrips = t->nstrips;
+    g.ex = exact_ctl(t, (v.family == Family::Roll ? kFamRoll : kFamRing));
+    g.nstrips = plan.nstrips;
     g.RR = v.ring(t->L);
     g.pitchA = v.pa(t->L);
-    g.nblocks = req.n * t->nstrips;
-    g.nslots = t->nstrips + t->nthin;
-    g.thin_x0 = t->thin_x0;
-    g.nthin = t->nthin;
+    g.nblocks = req.n * plan.nstrips;
+    g.nslots = plan.nstrips + plan.nthin;
+    g.thin_x0 = plan.thin_x0;
+    g.nthin = plan.nthin;
     if (path == kPathTwoPass || path == kPathTiled) return launch_twopass(t, req, g, ticket_armed); // (a tiled launch that was not taken falls through to here)
     return launch_strips(t, req, g);
 }
@@ -1432,7 +1132,6 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
     std::unique_ptr<pdog_tracker> owner(new pdog_tracker()); // a failure below destroys what was built so far
     pdog_tracker *t = owner.get();
     t->device = device;
-    t->sw = read_switches();
     t->fh = frame_h; t->fw = frame_w;
     t->tw = target_width;
     t->sigma = sigma_of(target_width);             // :41
@@ -1443,7 +1142,7 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
     t->fill = fill;                                // :47
     if ((long long)t->n1 * t->n2 > 0x3fffffffLL) return fail(PDOG_E_ARG, "pdog_create: window too large");
 
-    if (int rc = make_plan(t, -1)) return rc;
+    if (int rc = replan(t, read_switches(), -1)) return rc;
 
     // taps: Float64 on the host, one rounding to f32
     std::vector<double> gp(t->L), gm(t->L);
@@ -1522,10 +1221,9 @@ int pdog_create(int device, int frame_h, int frame_w, double target_width, int w
             rp.T64 = t->exact_T64;
             if (int rc = upload(t->d_rp, std::vector<RefineParams>(1, rp))) return rc;
         }
-        t->exact = refine_lds_bytes(t->n1, t->L, 1, 8) <= kMaxLds - 8192;
+        t->exact = exact_fits(geometry_of(t));
         if (!t->exact) // (success all the same: pdog_last_error carries the note, pdog_get_exact reports the state)
             (void)fail(PDOG_OK, "pdog_create: window too tall for the refinement's LDS block (n1 + l beyond ~9000 rows): exact mode is OFF for this tracker");
-        if (raise_lds_limit((const void *)dog_finish_kernel, refine_lds_bytes(t->n1, t->L, t->ref_cbw, t->ref_rows))) return PDOG_E_HIP;
     }
     if (int rc = ensure_capacity(t, 1)) return rc;
     *out = owner.release();
@@ -1547,9 +1245,9 @@ int pdog_get_info(const pdog_tracker *t, pdog_info *o)
     o->kernel_len = t->L;
     o->fill = t->fill;
     o->darker_target = t->darker;
-    o->n_strips = t->nstrips;
-    o->strip_w = t->var->tw();
-    o->variant = t->var->id;
+    o->n_strips = t->plan.nstrips;
+    o->strip_w = t->plan.shape->tw();
+    o->variant = t->plan.shape->id;
     o->sigma = t->sigma;
     o->target_width = t->tw;
     const int64_t th = t->n1 + t->L - 1, tw = t->n2 + t->L - 1;
@@ -1561,7 +1259,7 @@ int pdog_get_info(const pdog_tracker *t, pdog_info *o)
 int pdog_kernel_for_batch(const pdog_tracker *t, int n, int *out_variant)
 {
     if (!t || !out_variant || n < 0) return fail(PDOG_E_ARG, "pdog_kernel_for_batch: bad argument");
-    *out_variant = path_for_batch(t, n);
+    *out_variant = path_for_batch(t->plan, t->sw, n);
     return PDOG_OK;
 }
 
@@ -1607,7 +1305,7 @@ int pdog_set_variant(pdog_tracker *t, int variant)
     if (!t) return fail(PDOG_E_ARG, "pdog_set_variant: null tracker");
     if (variant >= 0 && !find_variant(variant)) return fail(PDOG_E_ARG, "pdog_set_variant: unknown variant id");
     HIP_TRY(hipSetDevice(t->device));
-    return make_plan(t, variant);
+    return replan(t, t->sw, variant);
 }
 
 // Drain the tracker's stream and report what its kernels raised while they ran: every entry point that waits for the
@@ -1638,7 +1336,7 @@ int pdog_sync(pdog_tracker *t)
 int pdog_set_exact(pdog_tracker *t, int on)
 {
     if (!t) return fail(PDOG_E_ARG, "pdog_set_exact: null tracker");
-    if (on && refine_lds_bytes(t->n1, t->L, 1, 8) > kMaxLds - 8192)
+    if (on && !exact_fits(geometry_of(t)))
         return fail(PDOG_E_ARG, "pdog_set_exact: window too tall for the refinement's LDS block");
     HIP_TRY(hipStreamSynchronize(t->stream));
     t->exact = on != 0;
@@ -1669,8 +1367,9 @@ int pdog_set_tuning(pdog_tracker *t, const char *key, int value)
     else if (k == "peaks_no_list") t->peaks.no_list = on; // include/pawsome_peaks.h
     else if (k == "motion_lds") t->motion_lds = on;       // include/pawsome_motion.h
     else if (k == "no_fused_c" || k == "no_tiled") { // inputs of the plan: the latency kernels' instances and tile layouts
-        (k == "no_tiled" ? t->sw.no_tiled : t->sw.no_fused_c) = on;
-        return make_plan(t, t->forced_variant ? t->var->id : -1);
+        Switches sw = t->sw;
+        (k == "no_tiled" ? sw.no_tiled : sw.no_fused_c) = on;
+        return replan(t, sw, t->plan.forced ? t->plan.shape->id : -1);
     } else return fail(PDOG_E_ARG, "pdog_set_tuning: unknown key '" + k + "'");
     return PDOG_OK;
 }
@@ -1748,8 +1447,7 @@ int pdog_get_exact(pdog_tracker *t, int *out_on, double *out_threshold, uint64_t
     if (!t) return fail(PDOG_E_ARG, "pdog_get_exact: null tracker");
     if (out_on) *out_on = t->exact ? 1 : 0;
     if (out_threshold) { // 2δ of the tracker's batch kernel family (small batches may run another family with a tighter bound)
-        const Variant &v = *t->var;
-        *out_threshold = (double)exact_ctl(t, v.roll ? kFamRoll : v.twopass ? kFamTwoPass8 : v.fused ? kFamFused : kFamRing).T;
+        *out_threshold = (double)exact_ctl(t, batch_family(*t->plan.shape)).T;
     }
     if (out_refined) {
         if (int rc = drain_and_check(t, "pdog_get_exact")) return rc;
@@ -1769,7 +1467,7 @@ int pdog_detect_batch(pdog_tracker *t, const uint8_t *d_frames, int64_t frame_st
     if (!d_frames || !d_guesses || !d_out_ij) return fail(PDOG_E_ARG, "pdog_detect_batch: null pointer");
     if (int rc = check_stack("pdog_detect_batch", t->fw, n_frames, row_stride, frame_stride, n >= 0)) return rc;
     if (!d_frame_index && n > n_frames) return fail(PDOG_E_ARG, "pdog_detect_batch: more windows than frames and no frame index");
-    if ((long long)n * t->nstrips > 0x7ffffff0LL) return fail(PDOG_E_ARG, "pdog_detect_batch: batch too large");
+    if ((long long)n * t->plan.nstrips > 0x7ffffff0LL) return fail(PDOG_E_ARG, "pdog_detect_batch: batch too large");
     HIP_TRY(hipSetDevice(t->device));
     if (int rc = ensure_capacity(t, n)) return rc;
     Request req;
@@ -2076,14 +1774,13 @@ namespace {
 // row c looks at frame h_table[c*n_steps + k], `first` = 1 means that step 0 receives the start as given and the loop begins at
 // step 1; row c has table.len[c] steps on the StagedTable that was checked with it.
 
-int chain_strips(const pdog_tracker *t) { return (t->n2 + ROLL_TW - 1) / ROLL_TW; }
-
 // The persistent roll chain: one launch, a workgroup per clip (a wave per strip) walks the clip's req.chain_len frames,
 // contiguous or over req.table.
 int launch_persistent(pdog_tracker *t, const Request &req)
 {
-    const Variant &v = *t->var;
-    const int strips = chain_strips(t);
+    const VariantShape &v = *t->plan.shape;
+    const VariantKernels &k = *t->kern;
+    const int strips = chain_strips(t->plan.geo);
     ChainPredictGeo cg; // (a launch without a table takes its ChainGeo part, one without prediction its ChainTableGeo part)
     cg.pred = req.predict ? *req.predict : PredictCtl{0.f, 0, nullptr, nullptr};
     cg.tab = req.table;
@@ -2097,41 +1794,17 @@ int launch_persistent(pdog_tracker *t, const Request &req)
     cg.taps_col_plain = t->d_taps_col.get();
     // the strips' LDS doubles as the refinement's scratch
     const size_t lds = std::max((size_t)strips * roll_lds_bytes(v.LT), refine_lds_bytes(t->n1, t->L, 1, 8));
-    fit_refine_scratch(t, lds, &cg.ref_cbw, &cg.ref_rows);
-    if (int rc = raise_lds_limit(req.predict ? (const void *)v.chain_predict : req.table.index ? (const void *)v.chain_table : (const void *)v.chain, lds)) return rc;
+    fit_refine_scratch(t->plan.geo, t->plan.ref_cbw, lds, &cg.ref_cbw, &cg.ref_rows);
+    if (int rc = raise_lds_limit(req.predict ? (const void *)k.chain_predict : req.table.index ? (const void *)k.chain_table : (const void *)k.chain, lds)) return rc;
     const f2 *tr = t->d_taps_row.get(), *troll = t->d_taps_roll.get();
-    if (req.predict) hipLaunchKernelGGL(v.chain_predict, dim3(req.n), dim3(64 * strips), lds, t->stream, cg, tr, troll);
-    else if (req.table.index) hipLaunchKernelGGL(v.chain_table, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainTableGeo &>(cg), tr, troll);
-    else hipLaunchKernelGGL(v.chain, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainGeo &>(cg), tr, troll);
+    if (req.predict) hipLaunchKernelGGL(k.chain_predict, dim3(req.n), dim3(64 * strips), lds, t->stream, cg, tr, troll);
+    else if (req.table.index) hipLaunchKernelGGL(k.chain_table, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainTableGeo &>(cg), tr, troll);
+    else hipLaunchKernelGGL(k.chain, dim3(req.n), dim3(64 * strips), lds, t->stream, static_cast<const ChainGeo &>(cg), tr, troll);
     HIP_TRY(hipGetLastError());
     return PDOG_OK;
 }
 
-// What a chain runs on: a kernel that walks its clips itself, or the stepped walk below, a batch per step.
-enum class ChainPath { Fused, Persistent, Tiled, Stepped };
-
-// n_clips clips of n_steps steps, contiguous or over a table; progress: one clip whose kernel publishes k + 1 after frame k.
-ChainPath chain_path(const pdog_tracker *t, int n_clips, int n_steps, bool table, bool progress)
-{
-    const Variant &v = *t->var;
-    // a table of one step is no chain for the kernels that walk a clip themselves (their chain_len = 1 means independent windows)
-    if (table && n_steps == 1) return ChainPath::Stepped;
-    // Enough clips to fill the GPU with one wave per strip → ONE persistent launch (a workgroup per clip walks
-    // its frames).  Fewer clips are latency-bound by that single wave per strip; then each frame is a small
-    // batch that the two-pass kernels spread over many workgroups (21 µs vs 48 µs per frame, one 45×45 window).
-    // (round 3: the fused kernel's compile-time-l instances walk 256 … 4096 clips of 45×45 windows at 27–30 M frames/s, the persistent
-    // roll chain 19–28 M; at 63×63 the chain wins from ≈1400 clips: 23.5 against 18.0 M frames/s at 2048)
-    const long long strip_waves = (long long)n_clips * chain_strips(t);
-    const bool fused_wins = t->fused.ok && !t->forced_variant && ((long long)t->n1 * t->n2 < 3000 || strip_waves < 1400);
-    const bool persistent = !progress && v.roll && v.chain && chain_strips(t) <= 8 && !fused_wins && // (the chain kernel publishes no progress)
-                            (t->forced_variant || !t->small_twopass || strip_waves >= 1000);
-    if (v.fused || (!persistent && !t->forced_variant && t->fused.ok)) return ChainPath::Fused; // one launch: a workgroup per clip loops over its frames
-    if (persistent) return ChainPath::Persistent;
-    // the tiled kernel: one cooperative launch, every sub-window's workgroup of every clip resident (as many clips as that
-    // allows); with progress its combining workgroup publishes k + 1 after every frame
-    if (!t->forced_variant && tiled_serves(t, n_clips, n_steps)) return ChainPath::Tiled;
-    return ChainPath::Stepped;
-}
+// (What a chain runs on — a kernel that walks its clips itself, or the stepped walk below, a batch per step: chain_path, pdog_plan.hpp.)
 
 // The stepped walk of ONE clip: a launch per step, stream order the only dependency — step k's guess is step k − 1's
 // (clamped) answer, read straight from the output array (device or host-mapped), no host round trip per frame.  With a
@@ -2201,12 +1874,12 @@ int walk_clips(pdog_tracker *t, const Request &clips, const TableWalk *ct)
 // clips.n clips of clips.chain_len steps each: contiguous (ct null: clip c's step k is frame c*chain_len + k) or over a table.
 int run_chains(pdog_tracker *t, Request clips, const TableWalk *ct)
 {
-    if (t->sw.tiled_force && clips.n == 1 && !t->forced_variant && !ct && !clips.progress) { // experiment switch: the tiled kernel first
+    if (t->sw.tiled_force && clips.n == 1 && !t->plan.forced && !ct && !clips.progress) { // experiment switch: the tiled kernel first
         bool launched = false;
         if (int rc = launch_tiled(t, clips, &launched)) return rc;
         if (launched) return PDOG_OK;
     }
-    const ChainPath path = chain_path(t, clips.n, clips.chain_len, ct != nullptr, clips.progress);
+    const ChainPath path = chain_path(t->plan, t->sw, t->tiled_resident, clips.n, clips.chain_len, ct != nullptr, clips.progress);
     if (ct && path != ChainPath::Stepped) { // the kernels that walk a clip themselves read the table's rows
         if (int rc = t->table.upload(ct->h_table, TableShape{clips.chain_len, clips.n, ct->max_len, 0}, t->stream, nullptr, &clips.table.index, &clips.table.len)) return rc;
         clips.table.first = ct->first;
@@ -2262,8 +1935,8 @@ int pdog::launch_predicted(pdog_tracker *t, const PredictWalk &w, int *taken)
 {
     *taken = 0;
     const TableWalk &tw = w.walk;
-    const ChainPath path = chain_path(t, tw.n_rows, tw.n_steps, true, false);
-    if (path != ChainPath::Fused && !(path == ChainPath::Persistent && t->var->chain_predict)) return PDOG_OK;
+    const ChainPath path = chain_path(t->plan, t->sw, t->tiled_resident, tw.n_rows, tw.n_steps, true, false);
+    if (path != ChainPath::Fused && !(path == ChainPath::Persistent && t->kern->chain_predict)) return PDOG_OK;
     HIP_TRY(hipSetDevice(t->device));
     Request clips;
     clips.frames = w.d_frames; clips.frame_stride = tw.frame_stride; clips.row_stride = tw.row_stride;

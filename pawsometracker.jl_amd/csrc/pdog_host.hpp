@@ -3,13 +3,19 @@
 // (pdog_math.cpp, plain C++) and, for the units that hipcc compiles, the HIP-error macro and the owning buffer type.
 // Two more headers are plain C++ and carry no HIP either: pdog_mailbox.hpp, the layout of the tracker's host-coherent mailbox,
 // which the kernel headers and pawsome_dog.hip both include, and pdog_policy.hpp, the two adaptive policies of the roll batch
-// path, which pawsome_dog.hip includes alone; the host compiler tests both (tests/policy_main.cpp).
+// path, which pawsome_dog.hip includes alone; the host compiler tests both (tests/policy_main.cpp).  Two further ones carry the
+// arithmetic around the kernels: dog_layout.hpp, the kernels' size formulas (LDS pitches and byte counts), which every kernel
+// header includes and any host program may; and pdog_plan.hpp, the tracker's plan as a value (Switches, the variants' shapes,
+// make_plan, path_for_batch, chain_path, the exact-mode thresholds), which includes dog_layout.hpp and dog_roll_range.hpp, no
+// kernel header, and which pawsome_dog.hip and the host's test program (tests/plan_main.cpp) include.
 //
 // WHERE KERNELS LIVE.  The kernels of the tracker (dog_*.hpp) are templates or `static __global__` functions in headers, and
 // raise_lds_limit is keyed on a kernel's address: a second translation unit that included one of those headers would get
 // private copies whose LDS limit was never raised.  So every include of a dog_*.hpp header of the tracker, every launch of
 // its kernels and every raise_lds_limit stay in pawsome_dog.hip (the *_inst.hip units only hold explicit instantiations);
-// this header, pdog_walk.hpp and pdog_math.cpp include no kernel header.  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip,
+// this header, pdog_walk.hpp, pdog_plan.hpp and pdog_math.cpp include no kernel header: what names no kernel and makes no HIP
+// call — which variant, how many strips, which path, how much LDS — is pdog_plan.hpp's, and pawsome_dog.hip applies it
+// (apply_plan: the limits a plan lists, the occupancy questions, then the assignment).  (pawsome_diag.hip, pawsome_group.hip, pawsome_peaks.hip,
 // pawsome_exclusive.hip and pawsome_motion.hip launch their own kernels, dog_diag.hpp's, group_compact_kernel, dog_peaks.hpp's,
 // dog_assign.hpp's and dog_motion.hpp's, which no other unit names; the last two hold nothing but those launches and their
 // geometry: the walk around them — checks, scratch, staged table, the loop over pdog_detect_peaks — is pdog_walk.hpp's, which

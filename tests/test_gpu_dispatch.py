@@ -1,43 +1,24 @@
-"""What a caller can observe of the tracker's plan (pawsome_dog.hip, make_plan): pdog_get_info, pdog_get_exact's state and
-threshold and pdog_kernel_for_batch, plain and after sequences of pdog_set_variant / pdog_set_tuning calls, compared with
+"""What a caller can observe of the tracker's plan (make_plan, csrc/pdog_plan.hpp, as pawsome_dog.hip applies it):
+pdog_get_info, pdog_get_exact's state and threshold and pdog_kernel_for_batch, plain and after sequences of pdog_set_variant / pdog_set_tuning calls, compared with
 tests/golden/dispatch_paths.json.  That file was recorded ONCE by record() below from the library of the commit BEFORE the
 plan became one function (selected with PAWSOME_DOG_LIB; the file's header names the commit): this is a characterisation
 test, the recording is the reference and is not re-recorded to make a change pass.  Trackers are created and asked questions;
 only the last two tests launch anything."""
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "dispatch_paths.json")
 
-# name: (frame_h, frame_w, target_width, window)
-CASES = {
-    "45x45_l29": (1080, 1920, 10, (45, 45)),          # the default window at the reference test's target width
-    "45x45_l65": (1080, 1920, 25, (45, 45)),          # … and at the default one
-    "63x63_l65": (1080, 1920, 25, (63, 63)),          # past 3000 pixels: the batch-size threshold decides
-    "257x257_l65": (1080, 1920, 25, (257, 257)),      # cfg3: four strips and a thin column, tiled below three windows
-    "257x257_l109": (1080, 1920, 44, (257, 257)),
-    "513x513_l65_4k": (2160, 3840, 25, (513, 513)),   # cfg4
-    "271x481_l65": (1080, 1920, 25, (271, 481)),      # cfg2
-    "205x205_l293": (1080, 1920, 120, (205, 205)),    # cfg5: no roll instance, the two-pass path
-    "15x15_l153": (1080, 1920, 63, (15, 15)),         # a two-pass tracker whose window fits the fused kernel: 256 | 257
-    "45x45_l13": (1080, 1920, 4, (45, 45)),           # below ROLL_LMIN: a ring kernel
-    "9801x45_l29": (1080, 1920, 10, (9801, 45)),      # too tall for the refinement's LDS block: exact mode is off
-}
-V, T = "set_variant", "set_tuning"
-SEQUENCES = {
-    "variants": [(V, 0), (V, 10), (V, 100), (V, 200), (V, 300), (V, -1)],
-    "no_fused_c": [(T, "no_fused_c", 1), (T, "no_fused_c", 0)],
-    "no_tiled": [(T, "no_tiled", 1), (T, "no_tiled", 0)],
-    "v100_no_fused_c": [(V, 100), (T, "no_fused_c", 1)],
-    "no_fused_c_v100": [(T, "no_fused_c", 1), (V, 100)],
-}
-BATCHES = [1, 2, 3, 16, 17, 256, 257, 1024, 1200, 4096]
+from dispatch_cases import BATCHES, CASES, SEQUENCES  # shared with tests/test_plan_cpu.py, which replays them on the host
 
 
 @pytest.fixture(scope="module")
