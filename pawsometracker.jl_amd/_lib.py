@@ -188,6 +188,14 @@ BLOB_PROTOTYPES = {
 }
 BLOB_SYMBOLS = tuple(BLOB_PROTOTYPES)
 
+# the same for include/pawsome_split.h, a header of its own that includes pawsome_blob.h: every target's blob inside its
+# nearest-centre cell (tests/test_split_cpu.py holds this table against that header)
+SPLIT_PROTOTYPES = {
+    "pdog_blob_split": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _i, _i, _i64, _i64, _i, _i, _i, _p, _p]),
+}
+SPLIT_SYMBOLS = tuple(SPLIT_PROTOTYPES)
+SPLIT_MAX_TARGETS = 32       # PDOG_SPLIT_MAX_TARGETS
+
 # the same for include/pawsome_refine.h, the sixth header pawsome_dog.h includes: the ranges the pruned strips run, a test hook
 # (tests/test_prune_refine_cpu.py holds this table against that header)
 REFINE_PROTOTYPES = {
@@ -240,7 +248,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
                                       **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES,
-                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES, **REFINE_PROTOTYPES}.items():
+                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES, **SPLIT_PROTOTYPES, **REFINE_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -373,6 +373,42 @@ class BatchTracker(_lib.TrackerHandle):
             C.c_void_p(sums.data_ptr()) if want_sums else None, C.c_void_p(shape.data_ptr())))
         return (shape, sums) if want_sums else shape
 
+    def split_blobs(self, frames, ij, frame_index=None, radius=None, min_contrast=8, connectivity=8, targets_first=False, want_sums=False):
+        """blobs() for targets that may TOUCH (pdog_blob_split; the rule is stated in include/pawsome_split.h): positions come in
+        sets, the n_targets (1 ... 32) targets of one frame, and every target's blob is grown only inside its nearest-centre cell
+        — the pixels nearer to its own position than to any other position of its set (ties to the lower index) —, so two
+        animals in contact are measured one by one.  ij int32 cuda contiguous [n_sets, n_targets, 2], or [n_targets, n_sets, 2]
+        with targets_first (the layout of the chains' results); frame_index None (set s looks at frame s) or int32 cuda over the
+        same two leading dimensions.  Returns float64 cuda [..., ..., 6] as blobs() does, in ij's layout.  With want_sums
+        (shape, sums): sums int32 cuda [..., ..., 12], blobs()'s ten over the split blob (b, c and n_mask unchanged) and n_cell,
+        the mask pixels inside the cell, and n_contact, the blob pixels with an edge neighbour in the mask outside the cell
+        (n_contact > 0: the target touches a neighbour's side).  Alone in its set, or with every other target farther than 2 *
+        radius away, a target gets blobs()'s ten integers bit for bit."""
+        import torch
+        self.use_torch_stream()
+        radius, min_contrast, connectivity = blob_args(radius, min_contrast, connectivity)
+        if not isinstance(targets_first, bool):
+            raise TypeError("targets_first must be True or False")
+        device_frames(frames, "frames", 3, self._hw)
+        device_array(ij, "ij", torch.int32, (None, None, 2))
+        d0, d1 = int(ij.shape[0]), int(ij.shape[1])
+        n_sets, n_targets = (d1, d0) if targets_first else (d0, d1)
+        if not 1 <= n_targets <= 32:
+            raise ValueError(f"ij: {n_targets} targets per set, 1 ... 32 expected")
+        fi = None if frame_index is None else device_array(frame_index, "frame_index", torch.int32, (d0, d1)).data_ptr()
+        if fi is None and n_sets > frames.shape[0]:
+            raise ValueError(f"ij: {n_sets} sets, but {frames.shape[0]} frames and no frame_index")
+        shape = torch.empty((d0, d1, 6), dtype=torch.float64, device=frames.device)
+        sums = torch.empty((d0, d1, 12), dtype=torch.int32, device=frames.device) if want_sums else None
+        if n_sets == 0:         # (an empty tensor has no address to hand over)
+            return (shape, sums) if want_sums else shape
+        strides = (1, n_sets) if targets_first else (n_targets, 1)
+        _lib.check(_lib.lib().pdog_blob_split(
+            self._h, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0], fi,
+            C.c_void_p(ij.data_ptr()), n_sets, n_targets, *strides, radius, min_contrast, connectivity,
+            C.c_void_p(sums.data_ptr()) if want_sums else None, C.c_void_p(shape.data_ptr())))
+        return (shape, sums) if want_sums else shape
+
     def _clips_handle(self):
         """The pdog_clips handle behind clip_modes / track_clips: created on first use, closed with the tracker."""
         if self._clips is None:

@@ -529,8 +529,8 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, shape=False, shape_radius=None, shape_min_contrast=None, shape_connectivity=None, background=None,
-                background_chunk=256, predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
+                min_distance=None, shape=False, shape_radius=None, shape_min_contrast=None, shape_connectivity=None, shape_split=False,
+                background=None, background_chunk=256, predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
     decoded or copied: fps_table names the frames the reference's ffmpeg line (:155) would hand over, and every target's
@@ -594,12 +594,22 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     keyword is what it is today.
     `shape_connectivity` = 4 or 8 measures `shape` over the CONNECTED BLOB under every position instead
     (BatchTracker.blobs; include/pawsome_blob.h states the rule): a second object inside the radius is left out.  None is the
-    shape rule, bit for bit as before.  ValueError without shape."""
+    shape rule, bit for bit as before.  ValueError without shape.
+    `shape_split` = True measures every target's blob INSIDE ITS NEAREST-CENTRE CELL among the step's positions of all targets,
+    held ones included (BatchTracker.split_blobs; include/pawsome_split.h states the rule): two animals that touch are
+    measured one by one, where shape_connectivity alone reports one merged body for both.  The result then gains `contact`,
+    int32 cuda [n_targets, m], as its last element behind `shape`: the rule's n_contact, > 0 where the target's blob touches a
+    neighbour's side.  One call without background, one per chunk under it, independent of background_chunk.  ValueError
+    without shape=True and a shape_connectivity; with False every result is bit for bit what it is without the keyword."""
     import torch
     from ._args import background_k, device_frames, exclusive_args, motion_args, peaks_args, predict_args
     from .batch import BatchTracker, mode_device
     chunk = _check_sink(diagnostic, diagnostic_chunk)
     shape_kw = _shape_keywords(shape, shape_radius, shape_min_contrast, shape_connectivity)
+    if not isinstance(shape_split, bool):
+        raise TypeError("shape_split must be True or False")
+    if shape_split and (shape_kw is None or shape_kw[2] is None):
+        raise ValueError("shape_split belongs to shape=True with a shape_connectivity of 4 or 8")
     if isinstance(background_chunk, bool) or not isinstance(background_chunk, (int, np.integer)):
         raise TypeError("background_chunk must be an integer")
     if background_chunk < 1:
@@ -714,7 +724,15 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 finally:
                     bt4.close()
             # the loop from the second selected frame on, :161-167: every target over the same table
-            sub = shp = None
+            sub = shp = contact = None
+
+            def shapes_of(fr, o, fi):
+                """`shape` [nt, steps, 6] at the positions o [nt, steps, 2] — and the contact counts [nt, steps] under shape_split."""
+                if not shape_split:
+                    return _shapes_or_blobs(bt, fr, o.reshape(-1, 2), fi, shape_kw).view(nt, -1, 6), None
+                sh, words = bt.split_blobs(fr, o, fi.view(nt, -1), shape_kw[0] or None, shape_kw[1], shape_kw[2], targets_first=True, want_sums=True)
+                return sh, words[:, :, 11]
+
             if bg is None:
                 out, state, _ = walk(bt, frames, table, starts, 1, None)
                 if subpixel or shape_kw:
@@ -722,12 +740,13 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                 if subpixel:
                     sub = bt.measure(frames, out.view(-1, 2), fi).view(nt, m, 2)
                 if shape_kw:
-                    shp = _shapes_or_blobs(bt, frames, out.view(-1, 2), fi, shape_kw).view(nt, m, 6)
+                    shp, contact = shapes_of(frames, out, fi)
             else:                        # the same over the subtracted frames, a buffer of them at a time
                 out = torch.zeros((nt, m, 2), dtype=torch.int32, device=dev)
                 state = torch.zeros((nt, m), dtype=torch.int32, device=dev) if exclusive or motion or predict else None
                 sub = torch.empty((nt, m, 2), dtype=torch.float64, device=dev) if subpixel else None
                 shp = torch.empty((nt, m, 6), dtype=torch.float64, device=dev) if shape_kw else None
+                contact = torch.empty((nt, m), dtype=torch.int32, device=dev) if shape_split else None
                 mstate = None
                 for k0 in range(0, m, bstep):
                     nk = min(bstep, m - k0)
@@ -743,7 +762,9 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
                     if subpixel:
                         sub[:, k0:k0 + nk] = bt.measure(buf[:nk], o.reshape(-1, 2).contiguous(), fi).view(nt, nk, 2)
                     if shape_kw:
-                        shp[:, k0:k0 + nk] = _shapes_or_blobs(bt, buf[:nk], o.reshape(-1, 2).contiguous(), fi, shape_kw).view(nt, nk, 6)
+                        shp[:, k0:k0 + nk], part = shapes_of(buf[:nk], o.contiguous(), fi)
+                        if shape_split:
+                            contact[:, k0:k0 + nk] = part
             bt.sync()                    # what the kernels raised (PdogError) surfaces before the positions are handed out
             if diagnostic is not None:
                 from .diagnose import Diagnose
@@ -753,6 +774,8 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             res = (ts, out, sub) if subpixel else (ts, out)
             if exclusive or motion or predict:
                 res += (state,)
+            if shape_split:
+                return res + (shp, contact.contiguous())
             return res + (shp,) if shape_kw else res
         finally:
             if bt is not None:
