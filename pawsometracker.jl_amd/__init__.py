@@ -11,3 +11,4 @@ from .batch import BatchTracker, GroupTracker, gather_positions, mode_device, sh
 from .diagnose import DIAG_MAX_TARGETS, DIAG_SIZE, Diagnose, diag_point  # noqa: F401
 from .background import BG_MAX_SAMPLES, Background, background_samples  # noqa: F401
 from ._lib import SHAPE_MAX_RADIUS  # noqa: F401
+from .frame_blobs import FB_WORDS, FrameBlobs, frame_blobs_derive  # noqa: F401

@@ -180,6 +180,33 @@ def blob_args(radius, min_contrast, connectivity, prefix=""):
     return radius, min_contrast, int(connectivity)
 
 
+def _integer(v, name, lo, hi, what=None):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+    if not lo <= v <= hi:
+        raise ValueError(f"{name}: {v} " + (what or f"lies outside {lo} ... {hi}"))
+    return int(v)
+
+
+def frame_blobs_args(n_pix, level, darker_target, min_contrast, connectivity, min_area, max_area, cap):
+    """What pdog_frame_blobs takes beside its arrays, for frames of n_pix pixels: the level 0 ... 255, the sign (True or False),
+    the least contrast 1 ... 255, the connectivity 4 or 8, the area limits 1 <= min_area <= max_area (None: n_pix) and the number
+    of rows per step, cap >= 1.  Returns (level, darker, min_contrast, connectivity, min_area, max_area, cap) as the library
+    takes them."""
+    level = _integer(level, "level", 0, 255)
+    if not isinstance(darker_target, (bool, np.bool_)):
+        raise TypeError(f"darker_target must be True or False, not {type(darker_target).__name__}")
+    min_contrast = _integer(min_contrast, "min_contrast", 1, 255)
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)):
+        raise TypeError(f"connectivity must be the integer 4 or 8, not {type(connectivity).__name__}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity: {connectivity} is neither 4 nor 8")
+    min_area = _integer(min_area, "min_area", 1, 2**62, "is not an area >= 1")
+    max_area = int(n_pix) if max_area is None else _integer(max_area, "max_area", min_area, 2**62, f"lies below min_area = {min_area}")
+    cap = _integer(cap, "cap", 1, 2**31 - 1, "is not a number of rows >= 1")
+    return level, int(bool(darker_target)), min_contrast, int(connectivity), min_area, max_area, cap
+
+
 def host_samples(v, name):
     """The sample list of a background estimate: host_steps' row, of 1 ... 64 entries.  The entries are the library's to judge."""
     a = host_steps(v, name)

@@ -196,6 +196,18 @@ SPLIT_PROTOTYPES = {
 SPLIT_SYMBOLS = tuple(SPLIT_PROTOTYPES)
 SPLIT_MAX_TARGETS = 32       # PDOG_SPLIT_MAX_TARGETS
 
+# the same for include/pawsome_frame_blobs.h, a header of its own that includes pawsome_dog.h: every connected blob of a whole
+# frame (tests/test_frame_blobs_cpu.py holds this table against that header)
+FRAME_BLOBS_PROTOTYPES = {
+    "pdog_fb_create": (_i, [_i, _i, _i, _i, _pp]),
+    "pdog_fb_destroy": (_i, [_p]),
+    "pdog_frame_blobs": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _i, _i, _i, _i, _i, _i64, _i64, _i, _p, _p]),
+    "pdog_frame_blobs_derive": (_i, [_p, _p]),
+}
+FRAME_BLOBS_SYMBOLS = tuple(FRAME_BLOBS_PROTOTYPES)
+FB_WORDS = 12                # PDOG_FB_WORDS
+FB_MAX_IN_FLIGHT = 1024      # PDOG_FB_MAX_IN_FLIGHT
+
 # the same for include/pawsome_refine.h, the sixth header pawsome_dog.h includes: the ranges the pruned strips run, a test hook
 # (tests/test_prune_refine_cpu.py holds this table against that header)
 REFINE_PROTOTYPES = {
@@ -248,7 +260,8 @@ def lib():
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **VIDEO_PROTOTYPES, **PRUNE_PROTOTYPES, **OVERLAY_PROTOTYPES, **PEAKS_PROTOTYPES,
                                       **EXCLUSIVE_PROTOTYPES, **MOTION_PROTOTYPES, **PREDICT_PROTOTYPES, **BACKGROUND_PROTOTYPES,
-                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES, **SPLIT_PROTOTYPES, **REFINE_PROTOTYPES}.items():
+                                      **SHAPE_PROTOTYPES, **BLOB_PROTOTYPES, **SPLIT_PROTOTYPES, **FRAME_BLOBS_PROTOTYPES,
+                                      **REFINE_PROTOTYPES}.items():
         fn = getattr(L, name, None)     # a symbol the loaded build lacks (an older A/B build through PAWSOME_DOG_LIB) is skipped
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -5,9 +5,11 @@
 #include "pdog_exclusive.hpp"
 #include "pdog_motion.hpp"
 #include "pdog_shape.hpp"
+#include "pdog_frame_blobs.hpp"
 #include "../../include/pawsome_exclusive.h"
 #include "../../include/pawsome_motion.h"
 #include "../../include/pawsome_shape.h"
+#include "../../include/pawsome_frame_blobs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -553,6 +555,14 @@ int pdog_shape_headings(const double *theta, const int32_t *ij, int n_steps, dou
     if (n_steps == 0) return PDOG_OK;
     if (!theta || !ij || !out) return fail(PDOG_E_ARG, "pdog_shape_headings: null pointer");
     pdog::shape::headings(theta, ij, n_steps, min_step, out);
+    return PDOG_OK;
+}
+
+// ---- the frame-blob rule's Float64 part on the host (include/pawsome_frame_blobs.h, "Derived"; pdog_frame_blobs.hpp holds the arithmetic) ----
+int pdog_frame_blobs_derive(const int64_t words[12], double out[6])
+{
+    if (!words || !out) return fail(PDOG_E_ARG, "pdog_frame_blobs_derive: null pointer");
+    pdog::fblobs::derive(words, out);
     return PDOG_OK;
 }
 

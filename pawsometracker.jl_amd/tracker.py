@@ -529,7 +529,7 @@ def track_clips(frames, target_width=25, start_locations=None, window_size=None,
 
 def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=25, start_locations=None, window_size=None,
                 darker_target=True, sar=1.0, subpixel=False, diagnostic=None, diagnostic_chunk=256, n_targets=None,
-                min_distance=None, shape=False, shape_radius=None, shape_min_contrast=None, shape_connectivity=None, shape_split=False,
+                min_distance=None, find="window", shape=False, shape_radius=None, shape_min_contrast=None, shape_connectivity=None, shape_split=False,
                 background=None, background_chunk=256, predict=False, motion=False, coast=None, min_response=None, exclusive=False, min_ratio=None):
     """The reference's `track(file; start, stop, fps, ...)` (src/PawsomeTracker.jl:130-173) on ONE device-resident video at
     its native rate: frames is a uint8 cuda tensor [n_frames, h, w] recorded at `rate` frames per second.  Nothing is
@@ -554,6 +554,14 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
     order: target 0 starts where the reference's own bootstrap puts its one target.  ValueError when fewer than K picks
     have a positive response, or when n_targets comes with start_locations.  Everything after the starts is what a list of
     K start locations gets.
+    `find` = "frame" (with n_targets; "window", the default, is the rule above, bit for bit) finds the K starts in the WHOLE first
+    selected frame instead (this library's addition; include/pawsome_frame_blobs.h states the rule and the choices): the frame's
+    connected blobs (FrameBlobs.find) whose contrast against the level — 128 under `background`, the fill otherwise — reaches
+    shape_min_contrast (None: 8), at shape_connectivity (None: 8), with max(1, W * W // 5) <= n <= 3 * W * W pixels,
+    W = ceil(target_width); the K largest (ties to the one that comes first in raster order; target 0 is the largest) give their
+    centroids, rounded half to even, as guesses, and every guess is refined by the tracker's own detection on that frame, exactly
+    like a given start location.  Animals near the walls are found, where the centre window sees none of them.  ValueError
+    naming both numbers when fewer than K blobs are kept, for find="frame" without n_targets and for any other value.
     `exclusive` = True keeps the targets apart (this library's addition; include/pawsome_exclusive.h states the rule): the
     loop from the second selected frame on is BatchTracker.detect_chains_exclusive over all targets as one group — per step
     every target's window yields its best separated peaks and the targets share them out, so that no two take the same blob;
@@ -626,6 +634,10 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
         start_locations = [None] * n_targets
     elif min_distance is not None and not exclusive and motion is not True:
         raise ValueError("min_distance belongs to n_targets and exclusive")
+    if not isinstance(find, str) or find not in ("window", "frame"):
+        raise ValueError(f'find: {find!r} is neither "window" nor "frame"')
+    if find != "window" and n_targets is None:
+        raise ValueError("find belongs to n_targets")
     if not isinstance(exclusive, bool):
         raise TypeError("exclusive must be True or False")
     if not isinstance(motion, bool):
@@ -704,7 +716,24 @@ def track_video(frames, rate, start=0, stop=DEFAULT_STOP, fps=24, target_width=2
             on_f0 = torch.full((nt,), f0, dtype=torch.int32, device=dev)
             starts = bt.detect(seen, guesses, on_f0)                                                      # :95
             auto = torch.tensor([loc is None for loc in locs], device=dev)
-            if n_targets is not None:
+            if n_targets is not None and find == "frame":
+                from .frame_blobs import FrameBlobs, frame_start_guesses
+                W = int(np.ceil(target_width))
+                with FrameBlobs(h, w, dev.index, steps_in_flight=1) as fb:
+                    kw = dict(table=[f0], level=128 if bg is not None else int(fill), darker_target=bool(darker_target),
+                              min_contrast=shape_kw[1] if shape_kw else 8, connectivity=(shape_kw[2] if shape_kw else None) or 8,
+                              min_area=max(1, W * W // 5), max_area=3 * W * W)
+                    count, words = fb.find(seen, cap=64, **kw)
+                    kept = int(count[0, 0])
+                    if kept > words.shape[1]:        # the list is cut: once more with room for all of them
+                        count, words = fb.find(seen, cap=kept, **kw)
+                    words = words[0, :kept].cpu().numpy()
+                if kept < n_targets:
+                    raise ValueError(f"n_targets = {n_targets}, but the first frame holds only {kept} blob(s) of "
+                                     f"{kw['min_area']} ... {kw['max_area']} pixels")
+                guesses = torch.tensor(frame_start_guesses(words, n_targets), dtype=torch.int32, device=dev).reshape(nt, 2)
+                starts = bt.detect(seen, guesses, on_f0)
+            elif n_targets is not None:
                 bt4 = BatchTracker(h, w, target_width, (h // 4, w // 4), darker_target, fill, device=dev.index)   # :102-103
                 try:
                     ij, peak, _ = bt4.detect_peaks(seen, guesses[:1], n_targets, md or None, on_f0[:1])           # :104, and K - 1 more
