@@ -138,7 +138,7 @@ __host__ __device__ inline PruneLds prune_lds(int n1, int n2, int L, int nslots,
 //     the whole tile are dealt out to the threads in order (consecutive lanes read consecutive cells of a row: coalesced;
 //     94 % of the lanes busy at cfg3, where a lane per dword of ONE row left 17 of 64 busy in its second pass);
 //     (band, cell) advance by the constant (NT ÷ ncx, NT mod ncx): no division in the loop.  A first version dealt out
-//     single dwords and paired them by DPP: its per-item index, mask and segment work outweighed the 13 instructions per
+//     single dwords and paired them by DPP: its per-item index, mask and segment work outweighed the 11 instructions per
 //     dword of the sums themselves (1.81e4 VALU instructions per window); per cell that work is paid once per 16.
 //   * How partial sums meet: the lane STORES its cell's sum (every cell has exactly one item: no atomic, no zeroing) and adds
 //     the cell's moments to its (band, segment) with two LDS atomics — per wave-instruction 64 lanes on about nine
@@ -309,7 +309,7 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
     __syncthreads();
     PRUNE_STAMP(0); // DC level, segment table
 
-    // ---- energy pass (above).  Per dword: the two substituted words, two dots, four ands, four packed min / max.  The loads
+    // ---- energy pass (above).  Per dword: the two substituted words, two dots, two ands, four packed min / max.  The loads
     // of the thread's next cell are requested before the sums of this one (sixteen registers each) ----
     PwAcc ext = pw_init(); // (its extremes only: the thread's pixels of all its items)
     auto cell_sums = [&](int band, int cx, const uint32_t (&w)[2 * CH]) {
@@ -488,65 +488,139 @@ static __global__ __launch_bounds__(PRUNE_NT) __attribute__((amdgpu_waves_per_eu
         uint32_t *pw32 = reinterpret_cast<uint32_t *>(patch);
         int a = tid / PQ, q = tid - a * PQ;
         const int astep = NT / PQ, qstep = NT - astep * PQ;
-        for (int e0 = tid; e0 < PH * PQ; e0 += PU * NT) {
-            int pa[PU], pq[PU];
-            uint32_t w[PU];
+        // The patch lies around the target: unless that is within about l ÷ 2 of the frame's edge, all its rows and whole
+        // dwords lie inside the frame (workgroup-uniform: scalars) and the words go to LDS as loaded.
+        const int pi0 = ti0 + oy, pj0 = wj0 + ox;
+        const bool patch_in = !NARROW && __builtin_amdgcn_readfirstlane((int)(pi0 >= 0 && pi0 + PH <= g.fh && pj0 >= 0 && pj0 + 4 * PQ <= g.fw));
+        if (patch_in) {
+            const uint8_t *src = frame + ((unsigned long long)(unsigned)pi0 * rs + (unsigned)pj0);
+            for (int e0 = tid; e0 < PH * PQ; e0 += PU * NT) {
+                int at[PU];
+                uint32_t w[PU];
 #pragma unroll
-            for (int j = 0; j < PU; ++j) {
-                pa[j] = a;
-                pq[j] = q;
-                q += qstep;
-                a += astep;
-                if (q >= PQ) { q -= PQ; ++a; }
+                for (int j = 0; j < PU; ++j) { // (an element past the patch's end is loaded at element 0's address and not stored)
+                    const bool on = e0 + j * NT < PH * PQ;
+                    at[j] = on ? a * (PP / 4) + q : -1;
+                    __builtin_memcpy(&w[j], src + (on ? (uint32_t)a * rs + 4u * (uint32_t)q : 0u), 4);
+                    q += qstep;
+                    a += astep;
+                    if (q >= PQ) { q -= PQ; ++a; }
+                }
+#pragma unroll
+                for (int j = 0; j < PU; ++j)
+                    if (at[j] >= 0) pw32[at[j]] = w[j];
             }
-            if (!narrow4) {
+        } else {
+            for (int e0 = tid; e0 < PH * PQ; e0 += PU * NT) {
+                int pa[PU], pq[PU];
+                uint32_t w[PU];
 #pragma unroll
-                for (int j = 0; j < PU; ++j) __builtin_memcpy(&w[j], frame_at(ti0 + oy + pa[j], pw_clamp_col(wj0 + ox + 4 * pq[j], g.fw, 4)), 4);
-            } else {
+                for (int j = 0; j < PU; ++j) {
+                    pa[j] = a;
+                    pq[j] = q;
+                    q += qstep;
+                    a += astep;
+                    if (q >= PQ) { q -= PQ; ++a; }
+                }
+                if (!narrow4) {
+#pragma unroll
+                    for (int j = 0; j < PU; ++j) __builtin_memcpy(&w[j], frame_at(ti0 + oy + pa[j], pw_clamp_col(wj0 + ox + 4 * pq[j], g.fw, 4)), 4);
+                } else {
+                    for (int j = 0; j < PU; ++j) {
+                        const int gi = ti0 + oy + pa[j], gj = wj0 + ox + 4 * pq[j];
+                        w[j] = tile_word(gi, gj, row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u);
+                    }
+                }
+#pragma unroll
                 for (int j = 0; j < PU; ++j) {
                     const int gi = ti0 + oy + pa[j], gj = wj0 + ox + 4 * pq[j];
-                    w[j] = tile_word(gi, gj, row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u);
+                    const uint32_t in = row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u;
+                    const PwShift sh = narrow4 ? PwShift{0u, 0u} : pw_shift(pw_clamp_col(gj, g.fw, 4) - gj, 4);
+                    if (e0 + j * NT < PH * PQ) pw32[pa[j] * (PP / 4) + pq[j]] = pw_words(pw_rebuild32(w[j], sh), in, 0xffffffffu, fill4).wz;
                 }
-            }
-#pragma unroll
-            for (int j = 0; j < PU; ++j) {
-                const int gi = ti0 + oy + pa[j], gj = wj0 + ox + 4 * pq[j];
-                const uint32_t in = row_in(gi) ? pw_mask(gj, 0, g.fw) : 0u;
-                const PwShift sh = narrow4 ? PwShift{0u, 0u} : pw_shift(pw_clamp_col(gj, g.fw, 4) - gj, 4);
-                if (e0 + j * NT < PH * PQ) pw32[pa[j] * (PP / 4) + pq[j]] = pw_words(pw_rebuild32(w[j], sh), in, 0xffffffffu, fill4).wz;
             }
         }
     }
     __syncthreads();
     PRUNE_STAMP(4); // patch
-    // Row pass in the strips' order: pairs k ascending, centre last.  A thread is (input row, output column xo); the pixels
-    // of four pairs come as two unaligned dwords (v_alignbyte_b32 over two aligned LDS dwords each): p[xo + 4i … + 3] and
-    // p[xo + l − 4 − 4i … + 3], the second read from its last byte down.  A pair's input is the integer
-    // p[k] + p[l−1−k] − 2·dc converted once: bit-equal to ((float)p[k] − fdc) + ((float)p[l−1−k] − fdc), because every term
-    // there is an exact integer of at most ten bits (and a zero sum is +0 either way).
+    // Row pass in the strips' order, per output: pairs k ascending, centre last, the taps of four pairs as one scalar load.
+    // A thread is (input row, NC = 4 neighbouring outputs x0 … x0 + 3).  The outputs of a row read the same pixels, so a pixel
+    // is centred ONCE, (float)p − fdc (pw_centred: two instructions), and a pair's input is one add of two centred pixels
+    // (pw_pair_input), bit-equal to the (float)(p[k] + p[l−1−k] − 2·dc) this pass formed before, per output and pair, from
+    // two byte extractions, an integer sum and a conversion.  Only a sliding window of centred pixels is held: the four
+    // pairs k0 … k0 + 3 of the four outputs read pixels x0 + k0 … + 6 at the low end and T − 6 … T, T = x0 + l + 2 − k0, at
+    // the high end — eight floats each, as two quads; a group later the window has moved by one quad, which alone is
+    // loaded (low end: an aligned LDS dword; high end: v_alignbyte_b32 over the new aligned dword and the one before) and
+    // converted.  Two groups per loop pass, so that the quads change roles and are never copied.
+    // READS OUTSIDE THE ROW, all inside this workgroup's LDS, converted and never used: the high end's first aligned pair
+    // (dprev = dn[1]) ends up to 3 bytes past the row's pitch where (l − 1) mod 4 = 0 and x0 = 4 — the next row, or for the last
+    // row the 8 bytes of slack behind the patch (prune_lds; the pass before this one read the same dword); the high end's
+    // read-ahead reaches at most two dwords below the row's start and the low end's one dword past its pitch where l < 17
+    // (row 0: the end of R, which lies before the patch).
     {
+        constexpr int NC = 4;
         const uint32_t *pw32 = reinterpret_cast<const uint32_t *>(patch);
-        const int xo = tid & (PB - 1), twodc = 2 * dc;
-        const unsigned sh_up = xo & 3, sh_dn = (xo + L) & 3; // (l − 4 − 4i ≡ l mod 4)
-        if (xo < nx)
-            for (int a = tid / PB; a < PH; a += NT / PB) {
-                const uint32_t *up = pw32 + a * (PP / 4) + (xo >> 2), *dn = pw32 + a * (PP / 4) + ((xo + L - 4) >> 2);
-                f2 acc = f2{0.f, 0.f};
-                int k0 = 0;
-                for (; k0 + 4 <= H; k0 += 4, ++up, --dn) { // (whole groups without a test per pair: their four taps come as one scalar load)
-                    const uint32_t u = __builtin_amdgcn_alignbyte(up[1], up[0], sh_up), v = __builtin_amdgcn_alignbyte(dn[1], dn[0], sh_dn);
+        const float fdc = (float)dc;
+        const unsigned sh_dn = (unsigned)(L - 1) & 3u; // (x0 is a multiple of 4)
+        auto quad = [&](uint32_t w, float (&c)[4]) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        acc = fma_bcast((float)((int)((u >> (8 * i)) & 0xffu) + (int)((v >> (24 - 8 * i)) & 0xffu) - twodc), trow[k0 + i], acc);
-                }
-                if (k0 < H) { // l ÷ 2 mod 4 pairs more
-                    const uint32_t u = __builtin_amdgcn_alignbyte(up[1], up[0], sh_up), v = __builtin_amdgcn_alignbyte(dn[1], dn[0], sh_dn);
-                    for (int i = 0; k0 + i < H; ++i)
-                        acc = fma_bcast((float)((int)((u >> (8 * i)) & 0xffu) + (int)((v >> (24 - 8 * i)) & 0xffu) - twodc), trow[k0 + i], acc);
-                }
-                acc = fma_bcast((float)((int)patch[a * PP + xo + H] - dc), trow[H], acc);
-                R[a * PB + xo] = acc;
+            for (int i = 0; i < 4; ++i) c[i] = pw_centred((w >> (8 * i)) & 0xffu, fdc);
+        };
+        for (int it = tid; it < PH * (PB / NC); it += NT) {
+            const int a = it / (PB / NC), x0 = (it - a * (PB / NC)) * NC;
+            if (x0 >= nx) continue;
+            const uint32_t *up = pw32 + a * (PP / 4) + (x0 >> 2), *dn = pw32 + a * (PP / 4) + ((x0 + L - 1) >> 2);
+            uint32_t dprev = dn[1];
+            auto next_lo = [&](float (&c)[4]) { quad(*up++, c); };
+            auto next_hi = [&](float (&c)[4]) {
+                const uint32_t d = *dn--;
+                quad(__builtin_amdgcn_alignbyte(dprev, d, sh_dn), c);
+                dprev = d;
+            };
+            // np ≤ 4 pairs from k0 on: the low window is l0 | l1 (pixels x0 + k0 … + 7), the high one h0 | h1 (T − 7 … T)
+            auto group = [&](f2 (&acc)[NC], const float (&l0)[4], const float (&l1)[4], const float (&h0)[4], const float (&h1)[4], int k0, int np) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < np) {
+                        const f2 t = trow[k0 + i];
+#pragma unroll
+                        for (int o = 0; o < NC; ++o) {
+                            const int li = i + o, hi = 4 + o - i;
+                            acc[o] = fma_bcast(pw_pair_input(li < 4 ? l0[li] : l1[li - 4], hi < 4 ? h0[hi] : h1[hi - 4]), t, acc[o]);
+                        }
+                    }
+            };
+            float lA[4], lB[4], hA[4], hB[4];
+            next_lo(lA);
+            next_lo(lB);
+            next_hi(hB);
+            next_hi(hA);
+            f2 acc[NC];
+#pragma unroll
+            for (int o = 0; o < NC; ++o) acc[o] = f2{0.f, 0.f};
+            int k0 = 0;
+            for (; k0 + 8 <= H; k0 += 8) { // (whole groups without a test per pair)
+                group(acc, lA, lB, hA, hB, k0, 4);
+                next_lo(lA);
+                next_hi(hB);
+                group(acc, lB, lA, hB, hA, k0 + 4, 4);
+                next_lo(lB);
+                next_hi(hA);
             }
+            if (k0 < H) { // l ÷ 2 mod 8 pairs more
+                group(acc, lA, lB, hA, hB, k0, min(H - k0, 4));
+                if (k0 + 4 < H) {
+                    next_lo(lA);
+                    next_hi(hB);
+                    group(acc, lB, lA, hB, hA, k0 + 4, H - k0 - 4);
+                }
+            }
+#pragma unroll
+            for (int o = 0; o < NC; ++o) {
+                acc[o] = fma_bcast(pw_centred(patch[a * PP + x0 + o + H], fdc), trow[H], acc[o]);
+                if (x0 + o < nx) R[a * PB + x0 + o] = acc[o];
+            }
+        }
     }
     __syncthreads();
     PRUNE_STAMP(5); // row pass of L

@@ -97,7 +97,7 @@ constexpr uint32_t PW_EVEN = 0x00ff00ffu, PW_ODD = 0xff00ff00u;
 // Σ p², Σ p and the packed extremes of the pixels counted so far
 struct PwAcc {
     uint32_t s2, s1;
-    uint32_t max_e, max_o, min_e, min_o; // even / odd bytes, two 16-bit halves each
+    uint32_t max_e, max_o, min_e, min_o; // two 16-bit halves each: the even bytes; the odd bytes in the halves' high bytes (the low bytes: anything)
 };
 PW_HD PwAcc pw_init() { return PwAcc{0u, 0u, 0u, 0u, PW_EVEN, PW_ODD}; }
 
@@ -107,13 +107,15 @@ PW_HD void pw_moments(uint32_t &s2, uint32_t &s1, uint32_t wz)
     s2 = pw_dot4(wz, wz, s2);
     s1 = pw_dot4(wz, 0x01010101u, s1);
 }
-// the extremes of one dword: two ands and two packed min / max per word
+// the extremes of one dword: one and and two packed min / max per word.  Only the even bytes are masked: a 16-bit half orders
+// by its high byte first, so the unmasked word leaves the largest (smallest) odd byte in the high byte of max_o (min_o)
+// whatever the low bytes hold, and pw_pmax / pw_pmin read that byte alone.
 PW_HD void pw_extremes(PwAcc &a, PwWords x)
 {
     a.max_e = pw_pk_max(a.max_e, x.wz & PW_EVEN);
-    a.max_o = pw_pk_max(a.max_o, x.wz & PW_ODD);
+    a.max_o = pw_pk_max(a.max_o, x.wz);
     a.min_e = pw_pk_min(a.min_e, x.wo & PW_EVEN);
-    a.min_o = pw_pk_min(a.min_o, x.wo & PW_ODD);
+    a.min_o = pw_pk_min(a.min_o, x.wo);
 }
 PW_HD void pw_update(PwAcc &a, PwWords x)
 {
@@ -134,6 +136,13 @@ PW_HD int pw_pmin(const PwAcc &a)
     const uint32_t o = (a.min_o & 0xffffu) < (a.min_o >> 16) ? (a.min_o & 0xffffu) : (a.min_o >> 16);
     return (int)(e < (o >> 8) ? e : (o >> 8));
 }
+
+// THE PAIR INPUT of L's row pass.  The strips feed a pair of taps with ((float)pa − fdc) + ((float)pb − fdc), fdc = (float)dc.
+// Every term is an exact integer of at most ten bits, so that equals (float)(pa + pb − 2·dc) bit for bit, a zero sum being +0
+// either way (tests/prune_fast_main.cpp, all 2²⁴ triples).  A pixel is centred once (pw_centred) and serves every pair and
+// output that reads it; a pair input is one add.
+PW_HD float pw_centred(uint32_t p, float fdc) { return (float)p - fdc; }
+PW_HD float pw_pair_input(float ca, float cb) { return ca + cb; }
 
 // Σ (p − dc)² of n pixels from their moments (RANGE above)
 PW_HD uint32_t pw_energy(uint32_t s2, uint32_t s1, int n, int dc) { return (s2 + (uint32_t)n * (uint32_t)(dc * dc)) - 2u * (uint32_t)dc * s1; }
