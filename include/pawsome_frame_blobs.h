@@ -20,8 +20,18 @@
  *                first                      r * frame_w + c of its first pixel in raster order;
  *                Ss                         the sum of its pixels' contrasts.
  *              The words are 64-bit because the sums need it: Syy of a blob that covers a 3840 x 2160 frame is 1.3e13, far
- *              beyond 32 bits.  No word of a frame below 2^30 pixels leaves 63 bits.
- *   Filter.    The blobs with min_area <= n <= max_area are KEPT.
+ *              beyond 32 bits.
+ *   Sizes.     The largest words a frame can produce are those of the one blob of a full mask: Syy = w * S2(h),
+ *              Sxx = h * S2(w) and Syx = T(h) * T(w), with S2(k) = (k-1)k(2k-1)/6 and T(k) = k(k-1)/2.  A frame size h x w is
+ *              ADMITTED when all of these hold, so that no word of an admitted frame leaves 63 bits:
+ *                h >= 1 and w >= 1;   h * w <= 2^30;   w <= PDOG_MAX_ROW_STRIDE (a call's row_stride is at least w);
+ *                w * S2(h) <= 2^63 - 1;   h * S2(w) <= 2^63 - 1;   T(h) * T(w) <= 2^63 - 1.
+ *              The largest h admitted, by width:
+ *                w          1          2          64       1920     3840     16 384   32 768   2^21
+ *                h      3 024 617  2 400 640   756 154   243 353  193 149   65 536   32 768     3
+ *              (at w = 16 384 and 32 768 the pixel limit binds first).  pdog_fb_create refuses every other size: beyond these
+ *              the 64-bit atomics would wrap modulo 2^64 without a sign, and the derived values would be garbage.
+ *   Filter.   The blobs with min_area <= n <= max_area are KEPT.
  *   Order.     Kept blobs are listed in ascending `first` — the order in which scipy.ndimage.label numbers components.  It is a
  *              property of the frame alone, so the result does not depend on how the kernels are scheduled.
  *   Count.     Per step, count = the number of kept blobs and n_mask = the number of mask pixels.  At most `cap` blobs are
@@ -58,9 +68,10 @@ extern "C" {
 
 typedef struct pdog_fb pdog_fb; /* opaque: the label and area scratch of one device for steps_in_flight frames, the staged table */
 
-/* A handle on HIP device `device` for frames of frame_h x frame_w (at most 2^30 pixels) that labels up to steps_in_flight
- * frames (1 ... PDOG_FB_MAX_IN_FLIGHT) per round of kernels; it owns 8 bytes of scratch per pixel and step in flight.
- * PDOG_E_ARG for a size or a number outside its range or a device ordinal out of range, PDOG_E_NODEV without a device,
+/* A handle on HIP device `device` for frames of frame_h x frame_w (an admitted size: "Sizes" above) that labels up to
+ * steps_in_flight frames (1 ... PDOG_FB_MAX_IN_FLIGHT) per round of kernels; it owns 8 bytes of scratch per pixel and step in
+ * flight.  PDOG_E_ARG for a size that is not admitted (before any device is asked for; the text names the size and the word
+ * that would not fit), a number outside its range or a device ordinal out of range, PDOG_E_NODEV without a device,
  * PDOG_E_ALLOC when the scratch does not fit. */
 int pdog_fb_create(int device, int frame_h, int frame_w, int steps_in_flight, pdog_fb **out);
 /* Waits for the last stream the handle worked on, then frees it. */

@@ -24,7 +24,7 @@ struct pdog_fb {
 
 namespace {
 
-constexpr int64_t kMaxPixels = 1ll << 30;
+static_assert(fblobs::kMaxWidth == PDOG_MAX_ROW_STRIDE, "size_refusal's width limit is the row stride's");
 
 // The device made current and `s` ordered behind the stream that used the scratch last.
 int begin(pdog_fb *fb, hipStream_t s)
@@ -47,8 +47,8 @@ int pdog_fb_create(int device, int frame_h, int frame_w, int steps_in_flight, pd
 {
     if (!out) return fail(PDOG_E_ARG, "pdog_fb_create: out is null");
     *out = nullptr;
-    if (frame_h <= 0 || frame_w <= 0 || (int64_t)frame_h * frame_w > kMaxPixels)
-        return fail(PDOG_E_ARG, "pdog_fb_create: bad frame size " + num(frame_h) + " x " + num(frame_w));
+    if (const char *why = fblobs::size_refusal(frame_h, frame_w))
+        return fail(PDOG_E_ARG, "pdog_fb_create: bad frame size " + num(frame_h) + " x " + num(frame_w) + ": " + why);
     if (steps_in_flight < 1 || steps_in_flight > PDOG_FB_MAX_IN_FLIGHT)
         return fail(PDOG_E_ARG, "pdog_fb_create: steps_in_flight " + num(steps_in_flight) + " outside 1 ... " + num(PDOG_FB_MAX_IN_FLIGHT));
     int ndev = 0;

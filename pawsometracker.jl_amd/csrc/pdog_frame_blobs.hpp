@@ -114,6 +114,27 @@ inline int64_t block_offsets(const int32_t *counts, int n_blocks, int32_t *offse
     return run;
 }
 
+// THE ADMITTED FRAME SIZES (include/pawsome_frame_blobs.h, "Sizes"): nullptr for a size the rule admits, otherwise what of it
+// does not fit — the text pdog_fb_create's refusal ends on.  The one blob of a full mask holds the largest words a frame can
+// produce: Syy = w * S2(h), Sxx = h * S2(w) and Syx = T(h) * T(w), with S2(k) = (k-1)k(2k-1)/6 and T(k) = k(k-1)/2, and the
+// device's 64-bit atomics would wrap without a sign where one of them passes 2^63 - 1.  The checks run in this order, and behind
+// the pixel limit both sides are at most 2^30, so that the 128-bit products cannot wrap themselves.
+constexpr int64_t kMaxPixels = 1ll << 30;
+constexpr int64_t kMaxWidth = 1ll << 21; // PDOG_MAX_ROW_STRIDE: a call's row_stride is at least the frame's width
+inline const char *size_refusal(int64_t h, int64_t w)
+{
+    if (h < 1 || w < 1) return "a side is not positive";
+    if ((__int128)h * w > kMaxPixels) return "more than 2^30 pixels";
+    if (w > kMaxWidth) return "frame_w exceeds PDOG_MAX_ROW_STRIDE";
+    const __int128 most = INT64_MAX;
+    const auto s2 = [](__int128 k) { return (k - 1) * k * (2 * k - 1) / 6; };
+    const auto t = [](__int128 k) { return k * (k - 1) / 2; };
+    if (w * s2(h) > most) return "Syy of a full frame leaves 63 bits";
+    if (h * s2(w) > most) return "Sxx of a full frame leaves 63 bits";
+    if (t(h) * t(w) > most) return "Syx of a full frame leaves 63 bits";
+    return nullptr;
+}
+
 constexpr double kPi = 3.14159265358979323846;
 
 // The rule's derived values: pdog_shape.hpp's step 7 on 64-bit sums, rows and columns 0-based in, 1-based out.

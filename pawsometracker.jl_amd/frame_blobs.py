@@ -50,9 +50,33 @@ def frame_start_guesses(words, k):
     return [(int(np.rint(r)), int(np.rint(c))) for r, c in rc]
 
 
+def frame_size_refusal(frame_h, frame_w):
+    """The admitted frame sizes (include/pawsome_frame_blobs.h, "Sizes"; size_refusal in csrc/pdog_frame_blobs.hpp) in Python
+    integers: None for a size the rule admits, otherwise what of it does not fit.  h, w >= 1, h * w <= 2^30,
+    w <= PDOG_MAX_ROW_STRIDE, and the words of the one blob of a full mask — Syy = w * S2(h), Sxx = h * S2(w),
+    Syx = T(h) * T(w), S2(k) = (k-1)k(2k-1)/6, T(k) = k(k-1)/2 — at most 2^63 - 1."""
+    h, w, most = int(frame_h), int(frame_w), 2**63 - 1
+    s2, t = (lambda k: (k - 1) * k * (2 * k - 1) // 6), (lambda k: k * (k - 1) // 2)
+    if h < 1 or w < 1:
+        return "a side is not positive"
+    if h * w > 2**30:
+        return "more than 2^30 pixels"
+    if w > _lib.PDOG_MAX_ROW_STRIDE:
+        return "frame_w exceeds PDOG_MAX_ROW_STRIDE"
+    if w * s2(h) > most:
+        return "Syy of a full frame leaves 63 bits"
+    if h * s2(w) > most:
+        return "Sxx of a full frame leaves 63 bits"
+    if t(h) * t(w) > most:
+        return "Syx of a full frame leaves 63 bits"
+    return None
+
+
 class FrameBlobs(_lib.Handle):
     """The scratch of one frame size on one device (pdog_fb): 8 bytes per pixel and step in flight.  find() runs on torch's
-    current stream, with no host synchronisation."""
+    current stream, with no host synchronisation.  The sizes admitted are those whose full-frame sums fit an int64
+    (frame_size_refusal): at most 2^30 pixels, frame_w <= PDOG_MAX_ROW_STRIDE = 2^21, and w * S2(h), h * S2(w) and T(h) * T(w)
+    at most 2^63 - 1 — 3 024 617 rows of one pixel, 243 353 rows of 1920, 3 rows of 2^21; ValueError beyond."""
 
     def __init__(self, frame_h, frame_w, device=0, steps_in_flight=8):
         for name, v in (("frame_h", frame_h), ("frame_w", frame_w), ("steps_in_flight", steps_in_flight)):
@@ -62,8 +86,9 @@ class FrameBlobs(_lib.Handle):
                 raise ValueError(f"{name}: {v} is not a positive number")
         if steps_in_flight > _lib.FB_MAX_IN_FLIGHT:
             raise ValueError(f"steps_in_flight: {steps_in_flight} lies outside 1 ... {_lib.FB_MAX_IN_FLIGHT}")
-        if frame_h * frame_w > 2**30:
-            raise ValueError(f"frames of {frame_h} x {frame_w} exceed 2^30 pixels")
+        why = frame_size_refusal(frame_h, frame_w)
+        if why:
+            raise ValueError(f"frames of {frame_h} x {frame_w} are not admitted: {why}")
         self._hw = (int(frame_h), int(frame_w))
         self.device = int(device)
         self.steps_in_flight = int(steps_in_flight)

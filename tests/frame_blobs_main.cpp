@@ -6,8 +6,9 @@
 //      tiles of 64 x 64 labelled by runs and links, the border merge's three item sets, the flatten, the compaction through
 //      block counts and block_offsets, the sums by stretches of 64 lanes — against a pixel flood fill and direct sums, on
 //      patterns and noise, at frame sizes around the tile size and at both connectivities;
-//   3. derive against long double arithmetic on drawn ellipses.
-// Prints "<n> checks, <m> mismatches"; exit status 1 on any mismatch.
+//   3. derive against long double arithmetic on drawn ellipses;
+//   4. the admitted frame sizes (size_refusal) at their edges, where a product formed in 64 bits would wrap (UBSan watches).
+// With the argument `sizes` it only prints size_refusal's verdict on the sizes it reads.  Otherwise prints "<n> checks, <m> mismatches"; exit status 1 on any mismatch.
 #include "pdog_frame_blobs.hpp"
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 
 using namespace pdog::fblobs;
@@ -265,8 +267,22 @@ static Frame make_frame(int h, int w, int kind, std::mt19937_64 &rng)
     return f;
 }
 
-int main()
+// `frame_blobs sizes`: reads "h w" pairs from standard input and prints, for each, "h w admitted" or "h w refused: <what does
+// not fit>" — size_refusal's verdict, which the pytest compares with the rule in Python integers.
+static int sizes_mode()
 {
+    long long h, w;
+    while (std::scanf("%lld %lld", &h, &w) == 2) {
+        const char *why = size_refusal(h, w);
+        if (why) std::printf("%lld %lld refused: %s\n", h, w, why);
+        else std::printf("%lld %lld admitted\n", h, w);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && std::string(argv[1]) == "sizes") return sizes_mode();
     std::mt19937_64 rng(20261021);
     // 1. row words
     const uint64_t patterns[] = {0, ~0ull, 1, 1ull << 63, 0x5555555555555555ull, 0xaaaaaaaaaaaaaaaaull, 0x8000000000000001ull, 0x00ff00ff00ff00ffull, 0x7ffffffffffffffeull};
@@ -332,6 +348,12 @@ int main()
             CHECK(std::fabs((double)(out[k] - want[k])) <= 1e-9 * std::max(1.0, std::fabs((double)want[k])), "derive value %d: %.17g, expected %.17Lg", k, out[k], want[k]);
         }
     }
+    // 4. the admitted sizes: the last admitted and the first refused of three widths, and sides whose 64-bit products would wrap
+    CHECK(!size_refusal(3024617, 1) && size_refusal(3024618, 1), "sizes at width 1");
+    CHECK(!size_refusal(243353, 1920) && size_refusal(243354, 1920), "sizes at width 1920");
+    CHECK(!size_refusal(3, 1 << 21) && size_refusal(4, 1 << 21) && size_refusal(1, (1 << 21) + 1), "sizes at width 2^21");
+    CHECK(!size_refusal(32768, 32768) && size_refusal(32769, 32768) && !size_refusal(1, 1), "sizes at the pixel limit");
+    CHECK(size_refusal(INT64_MAX, INT64_MAX) && size_refusal(INT64_MAX, 2) && size_refusal(INT64_MIN, 1) && size_refusal(0, 5) && size_refusal(5, -1), "sizes outside every range");
     std::printf("%ld frames replayed\n%ld checks, %ld mismatches\n", frames, n_checks, n_bad);
     return n_bad ? 1 : 0;
 }

@@ -99,6 +99,22 @@ def pattern(name, h, w):
     return SCENES[name](h, w)
 
 
+# The shapes beyond the tile's neighbourhood, each the smallest that reaches a path of the kernels, with the scenes it runs:
+#   (520, 520)      1057 blocks of 256 pixels: the scan of the blocks' counts (1024 at a time) has a second pass; 9 x 9 tiles,
+#                   a width that is a multiple of 4; the checkerboard has 135 200 blobs at connectivity 4
+#   (1037, 1041)    4217 blocks: five passes; 17 x 17 tiles, both sides odd
+#   (3, 2^21)       the widest size admitted: 32 768 tile columns, single addends of 2^48, a full frame's Sxx at 0.9999993 of 2^63
+#   (9000, 64)      141 tile rows and ONE tile column: no vertical border
+#   (3 024 617, 1)  the tallest size admitted: 47 260 tile rows, a full frame's Syy at 0.99999993 of 2^63
+LARGE = (
+    ((520, 520), NAMES),
+    ((1037, 1041), ("full", "spiral", "comb", "checkerboard", "lattice", "staircases", "noise 0.41", "noise 0.59")),
+    ((3, 1 << 21), ("full", "comb", "noise 0.59")),
+    ((9000, 64), ("full", "spiral", "lattice", "noise 0.59")),
+    ((3024617, 1), ("full", "checkerboard", "noise 0.59")),
+)
+
+
 def draw(mask, darker=True, seed=0):
     """The frame of a pattern: uint8 [h, w]."""
     h, w = mask.shape
@@ -106,6 +122,11 @@ def draw(mask, darker=True, seed=0):
     s = np.where(mask, rng.integers(8, 69, (h, w)), rng.integers(-5, 8, (h, w)))          # the contrast of every pixel
     f = (128 - s).astype(np.uint8)
     return f if darker else (255 - f).astype(np.uint8)
+
+
+def noise_frames(density, n, h, w, darker=True):
+    """n frames of noise at h x w, every one with a mask and contrasts of its own: uint8 [n, h, w]."""
+    return np.stack([draw(_noise(density, 1000 + k)(h, w), darker, k) for k in range(n)])
 
 
 def frames(h, w, darker=True):

@@ -1,7 +1,9 @@
 """The frame-blob rule (include/pawsome_frame_blobs.h) as far as no GPU is needed: the header against
 _lib.FRAME_BLOBS_PROTOTYPES and the library's exports, the header alone under a C and a C++ compiler, the binding's argument
 checks on host tensors, the kernels' host-only pieces and their steps replayed in a stand-alone program
-(tests/frame_blobs_main.cpp, built plain and with AddressSanitizer and UBSan), pdog_frame_blobs_derive through the library
+(tests/frame_blobs_main.cpp, built plain and with AddressSanitizer and UBSan), the admitted frame sizes (the header's "Sizes")
+of that program, of the binding and of pdog_fb_create against the rule in Python integers at the edge of thirteen widths, the
+restatement's int64 sums and the derived values at the two largest admitted sizes, pdog_frame_blobs_derive through the library
 against NumPy on drawn ellipses, the restatement (tests/frame_blobs_restatement.py, which the GPU must equal bit for bit:
 tests/test_gpu_frame_blobs.py) against a plain pixel flood fill on every scene of tests/frame_blobs_scenes.py, what the scenes
 claim to contain, and — on the oracle alone — the bootstrap scene: three discs outside the centre window, of which today's
@@ -32,15 +34,119 @@ NAMES = ["pdog_fb_create", "pdog_fb_destroy", "pdog_frame_blobs", "pdog_frame_bl
 
 
 # ---- the kernels' host-only pieces under the host compiler ----
-@pytest.mark.parametrize("flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]], ids=["plain", "asan_ubsan"])
-def test_kernel_steps_replayed_on_the_host_match_the_flood_fill(tmp_path, flags):
-    exe = tmp_path / "frame_blobs"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, "-I", CSRC,
-                           os.path.join(ROOT, "tests", "frame_blobs_main.cpp"), "-o", str(exe)])
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+BUILDS = pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g")], ids=["plain", "asan_ubsan"])
+_EXES = {}
+
+
+def _program(tmp_path_factory, flags):
+    """tests/frame_blobs_main.cpp under the host compiler, built once per set of flags for the tests of this file."""
+    if flags not in _EXES:
+        exe = tmp_path_factory.mktemp("frame_blobs") / "frame_blobs"
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *flags, "-I", CSRC,
+                               os.path.join(ROOT, "tests", "frame_blobs_main.cpp"), "-o", str(exe)])
+        _EXES[flags] = str(exe)
+    return _EXES[flags]
+
+
+@BUILDS
+def test_kernel_steps_replayed_on_the_host_match_the_flood_fill(tmp_path_factory, flags):
+    p = subprocess.run([_program(tmp_path_factory, flags)], capture_output=True, text=True, timeout=300)
     print(p.stdout)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert re.search(r"\b[1-9][0-9]* checks, 0 mismatches", p.stdout) and "1120 frames replayed" in p.stdout
+
+
+# ---- the admitted frame sizes ----
+T = lambda k: k * (k - 1) // 2  # noqa: E731
+S2 = lambda k: (k - 1) * k * (2 * k - 1) // 6  # noqa: E731
+MOST = 2**63 - 1
+EDGE_WIDTHS = (1, 2, 3, 63, 64, 65, 520, 1920, 3840, 16384, 32768, 2**21 - 1, 2**21)
+
+
+def _rule(h, w):
+    """The header's "Sizes" in Python integers: None for an admitted size, otherwise what does not fit."""
+    checks = ((h >= 1 and w >= 1, "a side is not positive"), (h * w <= 2**30, "more than 2^30 pixels"),
+              (w <= _lib.PDOG_MAX_ROW_STRIDE, "frame_w exceeds PDOG_MAX_ROW_STRIDE"), (w * S2(h) <= MOST, "Syy of a full frame leaves 63 bits"),
+              (h * S2(w) <= MOST, "Sxx of a full frame leaves 63 bits"), (T(h) * T(w) <= MOST, "Syx of a full frame leaves 63 bits"))
+    return next((text for ok, text in checks if not ok), None)
+
+
+def _largest_h(w):
+    lo, hi = 0, 2**31                      # admitted sizes are downward closed in h: every word grows with h
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if _rule(mid, w) is None else (lo, mid)
+    return lo
+
+
+def _full_words(h, w):
+    return [h * w, w * T(h), h * T(w), w * S2(h), T(h) * T(w), h * S2(w), 0, h - 1, 0, w - 1, 0]
+
+
+def test_the_header_s_table_of_largest_heights_is_the_rule_s():
+    table = {1: 3024617, 2: 2400640, 64: 756154, 1920: 243353, 3840: 193149, 16384: 65536, 32768: 32768, 2**21: 3}
+    assert {w: _largest_h(w) for w in table} == table
+    assert _rule(65537, 16384) == _rule(32769, 32768) == "more than 2^30 pixels"      # where the pixel limit binds first
+    text = " ".join(open(HDR).read().replace(" *", " ").split())
+    assert "No word of a frame below 2^30 pixels" not in text and "ADMITTED" in text
+    assert "w 1 2 64 1920 3840 16 384 32 768 2^21 h " + " ".join(f"{x:,}".replace(",", " ") for x in table.values()) in text  # its small table
+    assert "3 024 617" in inspect.getdoc(pt.FrameBlobs) and "2^63 - 1" in inspect.getdoc(pt.FrameBlobs)
+
+
+@BUILDS
+def test_size_rule_of_the_library_equals_python_integers(tmp_path_factory, flags):
+    from pawsometracker_jl_amd.frame_blobs import frame_size_refusal
+    cases = []
+    for w in EDGE_WIDTHS:
+        h = _largest_h(w)
+        assert h >= 1 and _rule(h, w) is None and _rule(h + 1, w) is not None
+        cases += [(h, w), (h + 1, w)]
+    cases.append((1, 2**21 + 1))
+    cases += [(w, h) for h, w in cases if h * w <= 2**30]                   # the transposes that the pixel limit allows
+    cases += [(0, 5), (5, 0), (-1, -1), (2**31 - 1, 2**31 - 1), (2**40, 2**40), (2**62, 4), (-2**63, 3)]
+    assert len(set(cases)) > 45 and {_rule(h, w) for h, w in cases} >= {None, "more than 2^30 pixels", "frame_w exceeds PDOG_MAX_ROW_STRIDE",
+                                                                         "Syy of a full frame leaves 63 bits", "Sxx of a full frame leaves 63 bits"}
+    p = subprocess.run([_program(tmp_path_factory, flags), "sizes"], input="".join(f"{h} {w}\n" for h, w in cases), capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    want = [f"{h} {w} " + ("admitted" if _rule(h, w) is None else "refused: " + _rule(h, w)) for h, w in cases]
+    assert p.stdout.splitlines() == want
+    for h, w in cases:                                                      # and the binding's mirror
+        assert frame_size_refusal(h, w) == _rule(h, w), (h, w)
+
+
+def test_refused_sizes_are_refused_without_a_device():
+    L = pt.lib()
+    for w, text in ((1, "Syy"), (1920, "Syy"), (2**21, "Sxx")):
+        h = _largest_h(w) + 1
+        out = C.c_void_p(1)
+        assert L.pdog_fb_create(0, h, w, 1, C.byref(out)) == _lib.PDOG_E_ARG and not out.value
+        msg = L.pdog_last_error().decode()
+        assert msg.startswith(f"pdog_fb_create: bad frame size {h} x {w}: ") and text in msg, msg
+        with pytest.raises(ValueError, match=f"{h} x {w}.*{text}"):
+            pt.FrameBlobs(h, w)
+    assert L.pdog_fb_create(0, 1, 2**21 + 1, 1, C.byref(out)) == _lib.PDOG_E_ARG and b"PDOG_MAX_ROW_STRIDE" in L.pdog_last_error()
+    with pytest.raises(ValueError, match="PDOG_MAX_ROW_STRIDE"):
+        pt.FrameBlobs(1, 2**21 + 1)
+
+
+@pytest.mark.parametrize("h,w", [(3024617, 1), (3, 2**21)])
+def test_restatement_and_derive_hold_at_the_largest_admitted_sizes(h, w):
+    assert _rule(h, w) is None and (_rule(h + 1, w) is not None) and max(_full_words(h, w)) > 0.999999 * 2**63
+    # the restatement's int64 sums do not wrap on the full frame
+    frame = FS.draw(FS.pattern("full", h, w))
+    words, n_mask = FR.all_blobs(frame, connectivity=4)
+    assert n_mask == h * w and len(words) == 1 and words[0, :11].tolist() == _full_words(h, w)
+    assert int(words[0, FR.SS]) == int((128 - frame.astype(np.int64)).sum())
+    # the derived values of the closed forms.  The axes come from mxx + myy -+ hypot(0, mxx - myy), with the larger moment
+    # L^2 / 12, L = max(h, w): one ulp of it (2^-13 at L = 3 024 617) is what the SHORT axis, 4 sqrt(1/12 ...), is known to,
+    # about 1e-3 — inside the 4K case's bound of 1e-9 L.  Nothing is cancelled in the other values.
+    got = pt.frame_blobs_derive(np.array(_full_words(h, w) + [0], np.int64))
+    long_, short = max(h, w), min(h, w)
+    want = np.array([(h + 1) / 2, (w + 1) / 2, np.pi / 2 if h > w else 0.0, 4 * np.sqrt(long_ * long_ / 12), 4 * np.sqrt(short * short / 12),
+                     2 * np.sqrt(h * w / np.pi)])
+    assert np.abs(got - want).max() <= 1e-9 * long_, (got, want)
+    assert np.abs(got[[0, 1, 3, 5]] - want[[0, 1, 3, 5]]).max() <= 1e-12 * long_, (got, want)
+    assert np.array_equal(got, FR.derive(_full_words(h, w) + [0])) or np.abs(got - FR.derive(_full_words(h, w) + [0])).max() <= 1e-12 * long_
 
 
 # ---- the header, the table, the exports ----

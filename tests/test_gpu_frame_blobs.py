@@ -8,8 +8,20 @@ noise either side of the percolation thresholds — at both connectivities and b
 270 x 480 through a table that names a frame twice; the area filter and the cap from both ends; strided, offset, poisoned,
 overlapping and aliased stacks of tests/layout_frames.py against their contiguous twins; every refusal, with nothing written;
 and track_video(n_targets=3, find="frame") on the bootstrap video, with and without `background`.  The whole file fails on a
-library without the symbols."""
+library without the symbols.
+
+THE LARGE SHAPES (frame_blobs_scenes.LARGE, the smallest that reach each path): 520 x 520 and 1037 x 1041, where the scan of
+the blocks' counts takes two and five passes of 1024 blocks; 3 x 2^21 and 3 024 617 x 1, the widest and the tallest size the
+handle admits, whose full frames' Sxx and Syy stand within a millionth of 2^63; 9000 x 64, a single column of 141 tiles.  On
+them the words are held to the restatement AND, on the full mask, to the closed forms in Python integers, so that a sum that
+wrapped on both sides alike could not pass; every shape must produce a word above 2^32.  Kept blobs are ranked across all scan
+passes with a cap above the count (every row compared) and with a cap that cuts the list inside the first pass.  The largest
+round a handle takes, 1024 steps in flight, and 1023; a host table overwritten straight after the call returns; outputs one
+element into sentinel-filled tensors; the edges of the admitted sizes on the device.
+NOT REACHED HERE: a single addend to Syx beyond 2^32 needs y * c > 6.7e7 inside one frame, a frame of more than 6.7e7 pixels,
+and frames near 2^30 pixels are out for the same reason — neither runs in seconds."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -246,3 +258,167 @@ def test_window_rule_is_what_it_is_without_the_keyword(pt):
         a, b = pt.track_video(d, **args, **kw), pt.track_video(d, find="window", **args, **kw)
         assert len(a) == len(b) and np.array_equal(a[0], b[0]) and all(torch.equal(x, y) for x, y in zip(a[1:], b[1:])), kw
     assert [tuple(p) for p in a[1][:, 0].cpu().tolist()] != []            # (three starts inside the window)
+
+
+# ---- the large shapes ----
+SCAN_BLOCK, SCAN_PASS = 256, 1024          # pixels per block of the raster, blocks per pass of the scan (dog_frame_blobs.hpp)
+T = lambda k: k * (k - 1) // 2  # noqa: E731
+S2 = lambda k: (k - 1) * k * (2 * k - 1) // 6  # noqa: E731
+
+
+@functools.lru_cache(maxsize=None)
+def _large_stack(shape):
+    """The scenes of one shape of FS.LARGE, drawn once for all the tests below (they do not write to it)."""
+    return np.stack([FS.draw(FS.pattern(name, *shape), True, k) for k, name in enumerate(dict(FS.LARGE)[shape])])
+
+
+@functools.lru_cache(maxsize=None)
+def _large_want(shape, conn):
+    want = FR.find(_large_stack(shape), connectivity=conn, cap=64)
+    for a in want:
+        a.setflags(write=False)
+    return want
+
+
+def _full_frame_words(h, w):
+    """The one blob of a full mask, in Python integers: the eleven words that do not depend on the contrasts."""
+    return [h * w, w * T(h), h * T(w), w * S2(h), T(h) * T(w), h * S2(w), 0, h - 1, 0, w - 1, 0]
+
+
+@pytest.mark.parametrize("shape", [s for s, _ in FS.LARGE], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_large_shapes_equal_the_restatement_and_the_closed_forms(pt, shape):
+    (h, w), names = shape, dict(FS.LARGE)[shape]
+    stack = _large_stack(shape)
+    k = names.index("full")
+    closed = _full_frame_words(h, w)
+    assert max(closed) <= 2**63 - 1                                        # an admitted size: the closed forms fit
+    with pt.FrameBlobs(h, w, steps_in_flight=2) as fb:                      # every stack takes more than one round
+        d = _cuda(stack)
+        for conn in (4, 8):
+            want = _large_want(shape, conn)
+            got = fb.find(d, connectivity=conn, cap=64)
+            _same(got, want, (shape, conn))
+            count, words = (v.cpu().numpy() for v in got)
+            assert count[k].tolist() == [1, h * w]
+            assert words[k, 0, :11].tolist() == closed, (shape, conn, words[k, 0].tolist(), closed)
+            assert int(words[k, 0, FR.SS]) == int((128 - stack[k].astype(np.int64)).sum()) and not words[k, 1:].any()
+            assert int(want[1].max()) > 2**32, (shape, conn)               # the upper halves of the 64-bit words are in use
+
+
+RANKED = (((520, 520), "checkerboard", 1, 135200), ((1037, 1041), "noise 0.41", 20, 3469), ((1037, 1041), "noise 0.59", 200, 214))
+
+
+@pytest.mark.parametrize("shape,name,min_area,n_kept", RANKED, ids=[f"{s[0]}x{s[1]} {n}" for s, n, _, _ in RANKED])
+def test_kept_blobs_are_ranked_across_every_scan_pass(pt, shape, name, min_area, n_kept):
+    h, w = shape
+    k = dict(FS.LARGE)[shape].index(name)
+    stack = _large_stack(shape)[k:k + 1]
+    cap = n_kept + 3
+    kw = dict(connectivity=4, min_area=min_area)
+    want = FR.find(stack, cap=cap, **kw)
+    # what makes this a test of the later passes: the list is not cut, and it has kept blobs in every pass of the scan
+    n_passes = ((h * w + SCAN_BLOCK - 1) // SCAN_BLOCK + SCAN_PASS - 1) // SCAN_PASS
+    assert want[0][0, 0] == n_kept <= cap and n_passes == {(520, 520): 2, (1037, 1041): 5}[shape]
+    passes = want[1][0, :n_kept, FR.FIRST] // SCAN_BLOCK // SCAN_PASS
+    assert sorted(set(passes.tolist())) == list(range(n_passes)), np.bincount(passes).tolist()
+    assert n_kept > 64 and passes[63] == 0                                  # cap = 64 cuts the list inside the first pass
+    with pt.FrameBlobs(h, w, steps_in_flight=2) as fb:
+        d = _cuda(stack)
+        _same(fb.find(d, cap=cap, **kw), want, (shape, name, cap))         # every row, and the zero rows behind the count
+        _same(fb.find(d, cap=64, **kw), (want[0], want[1][:, :64]), (shape, name, 64))
+
+
+def test_large_shape_behind_a_layout_equals_its_twin(pt):
+    shape = (520, 520)
+    stack = _large_stack(shape)
+    table = [9, 3, 0, 10, 3, 5, 1]                                          # a frame named twice, three rounds and a half
+    lay = LF.make(stack, 3, 5, 7, LF.poison_for(True))
+    assert lay.row_stride == 523 and lay.base == 5 and lay.frame_stride == 520 * 523 + 7
+    with pt.FrameBlobs(*shape, steps_in_flight=2) as fb:
+        d, twin = LF.to_device(lay), _cuda(stack)
+        for conn in (4, 8):
+            want = tuple(a[table] for a in _large_want(shape, conn))
+            _same(fb.find(d, table, connectivity=conn, cap=64), want, ("layout", conn))
+            _same(fb.find(twin, table, connectivity=conn, cap=64), want, ("twin", conn))
+
+
+# ---- the largest round ----
+def test_the_largest_round_a_handle_holds(pt):
+    from pawsometracker_jl_amd import _lib
+    h, w, n_steps = 5, 7, 1030
+    assert _lib.FB_MAX_IN_FLIGHT == 1024 < n_steps
+    stack = FS.noise_frames(0.59, n_steps, h, w)
+    assert len({f.tobytes() for f in stack}) == n_steps                     # the steps differ
+    d = _cuda(stack)
+    want = {conn: FR.find(stack, connectivity=conn, cap=8) for conn in (4, 8)}
+    assert len({tuple(c) for c in want[4][0].tolist()}) > 20
+    for in_flight in (1024, 1023):                                          # one full round and 6 steps; 1023 and 7
+        with pt.FrameBlobs(h, w, steps_in_flight=in_flight) as fb:
+            for conn in (4, 8):
+                _same(fb.find(d, connectivity=conn, cap=8), want[conn], (in_flight, conn))
+
+
+# ---- direct calls ----
+def _direct(L, fb, frames, table, cap, words_ptr, count_ptr, h, w, conn=8):
+    return L.pdog_frame_blobs(fb._h, None, C.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1), frames.shape[0],
+                              C.c_void_p(table.ctypes.data), len(table), 128, 1, 8, conn, 1, h * w, cap, C.c_void_p(words_ptr), C.c_void_p(count_ptr))
+
+
+def test_host_table_is_consumed_before_the_call_returns(pt):
+    import torch
+    from pawsometracker_jl_amd import _lib
+    shape = (520, 520)
+    stack = _large_stack(shape)
+    d = _cuda(stack)
+    first = np.array([1, 5, 7, 2, 9], np.int32)
+    other = np.array([8, 0, 3, 10, 4], np.int32)
+    want = tuple(a[first] for a in _large_want(shape, 8))
+    assert not np.array_equal(want[1], _large_want(shape, 8)[1][other])
+    words = torch.empty((len(first), 64, 12), dtype=torch.int64, device="cuda")
+    count = torch.empty((len(first), 2), dtype=torch.int32, device="cuda")
+    with pt.FrameBlobs(*shape, steps_in_flight=2) as fb:
+        fb.find(d, connectivity=4)                                          # (the staging has its size; the stream is drained)
+        torch.cuda.synchronize()
+        assert torch.cuda.current_stream().cuda_stream == 0                 # find and the direct call share the null stream
+        fb.find(d, connectivity=8)                                          # work in front of the call: its upload has to wait
+        table = first.copy()
+        assert _direct(pt.lib(), fb, d, table, 64, words.data_ptr(), count.data_ptr(), *shape) == _lib.PDOG_OK
+        table[:] = other                                                    # the caller's array is the caller's again
+        torch.cuda.synchronize()
+        _same((count, words), want, "table overwritten after return")
+
+
+def test_outputs_inside_sentinel_margins(pt):
+    import torch
+    from pawsometracker_jl_amd import _lib
+    shape, cap = (520, 520), 64
+    stack = _large_stack(shape)
+    d = _cuda(stack)
+    table = np.arange(len(stack), dtype=np.int32)
+    n_words, n_count = len(table) * cap * 12, len(table) * 2
+    big_words = torch.full((n_words + 2,), -SENTINEL, dtype=torch.int64, device="cuda")
+    big_count = torch.full((n_count + 2,), -SENTINEL, dtype=torch.int32, device="cuda")
+    p_words, p_count = big_words.data_ptr() + 8, big_count.data_ptr() + 4
+    assert p_words % 16 == 8 and p_count % 16 == 4                          # off a 16-byte boundary, at the natural alignment
+    with pt.FrameBlobs(*shape, steps_in_flight=2) as fb:
+        for conn in (4, 8):
+            assert _direct(pt.lib(), fb, d, table, cap, p_words, p_count, *shape, conn=conn) == _lib.PDOG_OK
+            torch.cuda.synchronize()
+            _same((big_count[1:-1].view(-1, 2), big_words[1:-1].view(-1, cap, 12)), _large_want(shape, conn), ("margins", conn))
+            assert [int(big_words[0]), int(big_words[-1]), int(big_count[0]), int(big_count[-1])] == [-SENTINEL] * 4
+
+
+# ---- the edges of the admitted sizes ----
+def test_sizes_one_past_the_admitted_ones_are_refused_on_the_device(pt):
+    from pawsometracker_jl_amd import _lib
+    L = pt.lib()
+    # (handles of 3 024 617 x 1 and 3 x 2^21, the last admitted ones, are made by the large shapes above)
+    assert {(3024617, 1), (3, 1 << 21)} <= {s for s, _ in FS.LARGE}
+    for (h, w), text in (((3024618, 1), "Syy"), ((4, 1 << 21), "Sxx"), ((1, (1 << 21) + 1), "PDOG_MAX_ROW_STRIDE")):
+        out = C.c_void_p()
+        assert L.pdog_fb_create(0, h, w, 1, C.byref(out)) == _lib.PDOG_E_ARG and not out.value
+        msg = L.pdog_last_error().decode()
+        assert msg.startswith("pdog_fb_create: ") and f"{h} x {w}" in msg and text in msg, msg
+        with pytest.raises(ValueError, match=text) as e:
+            pt.FrameBlobs(h, w)
+        assert f"{h} x {w}" in str(e.value)
